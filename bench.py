@@ -7,11 +7,12 @@ restored noise), classifier-free guidance (2 denoiser passes per step), batch 8 
 Synthetic weights + inputs (no checkpoints/datasets offline).  One "step" = one p_sample:
 2 x FiLMTransformer forward over 8 samples + guidance + posterior update.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision fp16|bf16|fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision fp16|bf16|fp32] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Defaults: N=1, K=200 timed steps per region behind W=20 warm-up steps, 3 regions (the median is reported); the whole default run,
-legs, parity and CPU baseline included, takes ~35 s on the GPU box.
+Defaults: N=1, K=200 timed steps behind W=20 warm-up steps, in one timed region (--repeats R: R regions of K steps, the median
+is reported); `ms_per_step` = region time / K.  The whole default run, legs, parity and CPU baseline included, takes ~35 s on
+the GPU box.  --dump-outputs DIR writes the outputs of the last timed step as .npy files (dump_outputs).
 
 The ONE JSON line rank 0 prints carries, next to the contract fields:
   roofline      dominant kernel class, algorithmic FLOPs / measured launch time (HIP events on the launch stream) vs the bf16 peak
@@ -191,7 +192,7 @@ class Case:
                 out = d.p_sample(self.cfg, st["x"], self.steps_idx[st["i"]], clip_denoised=False, model_kwargs={"y": self.y}, noise=noise)
             else:
                 out = d.ddim_sample(self.cfg, st["x"], self.steps_idx[st["i"]], clip_denoised=False, model_kwargs={"y": self.y})
-            st["x"] = out["sample"]
+            st["x"], self.last_out = out["sample"], out
             st["i"] = st["i"] - 1 if st["i"] > 0 else self.n_chain - 1
 
     def step_flops(self):
@@ -211,6 +212,30 @@ def time_case(case, steps, warmup, repeats, barrier):
             barrier()
             dts.append(time.perf_counter() - t0)
     return dts
+
+
+DUMP_DATA_BYTES = 63 * 10 ** 6   # --dump-outputs writes at most 64 MB: the array data plus one .npy header per array
+
+
+def dump_outputs(outdir, arrays):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy, float32 (float64 stays float64), so that two builds run with the same
+    arguments can be compared output for output.  Arrays that together exceed DUMP_DATA_BYTES are each replaced by the same fixed
+    sample of their flattened elements (seed 0, indices ascending), sized in proportion.  Returns what was written, per array."""
+    import numpy as np
+    arrays = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32) for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    os.makedirs(outdir, exist_ok=True)
+    written = {}
+    for name, v in arrays.items():
+        rec = {"shape": list(v.shape), "dtype": str(v.dtype).replace("torch.", "")}
+        if total > DUMP_DATA_BYTES:
+            keep = v.numel() * DUMP_DATA_BYTES // total
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            v = v.reshape(-1)[idx]
+            rec["sampled_elements"] = keep
+        np.save(os.path.join(outdir, name + ".npy"), v.numpy())
+        written[name] = rec
+    return written
 
 
 def kernel_breakdown(case, ksteps):
@@ -884,7 +909,8 @@ def main():
     ap.add_argument("--steps", type=int, default=200,
                     help="timed steps per region (default 200: a region costs ~0.6 ms on top of its steps -- clocks and queues leaving idle -- which is 1.5 %% of a 20-step region; profiles/r03_steps_sweep.txt)")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of exactly --steps steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed regions of exactly --steps steps each; the median is reported (default 1: --steps is the number of timed steps)")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--frames", type=int, default=600)
     ap.add_argument("--precision", default="fp16", choices=["bf16", "fp16", "fp32"],
@@ -912,7 +938,15 @@ def main():
     ap.add_argument("--no-legs", action="store_true", help="skip the face B=32 and body B=16 sub-records")
     ap.add_argument("--chain-steps", type=int, default=1000, help="length of the bf16-vs-fp32 drift chain (0 = skip)")
     ap.add_argument("--write-parity", default=None, help="also write the parity record to this JSON file (profiles/r02_parity.json)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (p_sample / ddim_sample: sample, pred_xstart; "
+                         "N > 1: the gathered samples) as DIR/<name>.npy, float32, at most 64 MB in all (larger outputs: a fixed seeded "
+                         "sample of their elements); the inputs depend on the arguments only, so two builds can be compared output for output")
     a = ap.parse_args()
+    if a.steps < 1 or a.repeats < 1:
+        ap.error("--steps and --repeats must be at least 1")
+    if a.dump_outputs and a.pipeline:
+        ap.error("--dump-outputs covers the step benchmark, not --pipeline")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` started directly (the form the driver uses at N=1): launch the N ranks ourselves, one process per
@@ -1016,6 +1050,11 @@ def main():
         torch.cuda.synchronize()
         gather_ms = (time.perf_counter() - t0) * 1e3
         assert allx.shape[0] == total and bool(torch.isfinite(allx).all())
+    # the last timed step's outputs, before the measurement legs below step the same case further
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, {"sample": allx} if world > 1 else
+                              {"sample": case.last_out["sample"], "pred_xstart": case.last_out["pred_xstart"]})
 
     kernels, roofline = {}, None
     under_load = load_probe(case, dev) if rank == 0 and not a.no_kernel_timing else None   # after the timed regions (not under a profiler): power / clock / temperature while the steps run
@@ -1096,6 +1135,7 @@ def main():
                             if world > 1 else None),
             "box": box_record(dev), "under_load": under_load,
             "roofline": roofline, "kernels": kernels, "cpu_baseline": cpu, "parity": parity, "legs": legs or None,
+            "dump_outputs": dumped and {"dir": a.dump_outputs, "arrays": dumped},
         }
         print(json.dumps(line), flush=True)
     if world > 1:

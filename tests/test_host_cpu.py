@@ -668,3 +668,24 @@ def test_one_escalating_shard_moves_every_rank_to_fp32(tmp_path, world):
             assert runs == ["fp32"] and not warns                     # the hot shard escalated inside its own loop
         else:
             assert runs == ["fp16", "fp32"] and any("repeats its shard in fp32" in x for x in warns)
+
+
+# ----------------------------------------------------------------------------- bench.py --dump-outputs
+def test_bench_dump_outputs_stays_within_64_mb_with_a_fixed_sample(tmp_path):
+    """`bench.py --dump-outputs DIR`: outputs that fit are written whole as float32 .npy files; larger ones as the same seeded sample of
+    their elements on every run, the files together at most 64 MB."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    small = {"sample": torch.randn(2, 4, 1, 6, generator=g, dtype=torch.float64).half(), "pred_xstart": torch.randn(2, 4, 1, 6, generator=g)}
+    rec = bench.dump_outputs(str(tmp_path / "small"), small)
+    for k, v in small.items():
+        got = np.load(tmp_path / "small" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v.float().numpy()) and "sampled_elements" not in rec[k]
+    big = {"sample": torch.randn(64, 256, 1, 600, generator=g), "pred_xstart": torch.randn(64, 256, 1, 600, generator=g)}
+    runs = [bench.dump_outputs(str(tmp_path / d), big) for d in ("a", "b")]
+    assert runs[0] == runs[1] and runs[0]["sample"]["shape"] == [64, 256, 1, 600]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 * 10 ** 6
+    for k, v in big.items():
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert np.array_equal(a, b) and a.size == runs[0][k]["sampled_elements"] > 0
+        assert np.isin(a[:1000], v.numpy()).all()                  # sampled values, not recomputed ones

@@ -123,7 +123,7 @@ def test_plms_first_steps_and_ddim_reverse_vs_reference(golden_plms):
 
 
 
-def test_chain_fixture_is_what_the_committed_generator_produces():
+def test_chain_fixture_is_what_the_committed_generator_produces(tmp_path):
     """tests/golden/golden_chain_body_v1.npz (the oracle's ddim100 chain of the body workload, gated against by the GPU suite) must be reproducible from
     tests/tools/chain_vs_oracle.py --side oracle: the first 10 steps re-run here (3 s) land on the stored state after step 10; the face fixture (21
     CPU-minutes) is checked for its layout only."""
@@ -134,7 +134,7 @@ def test_chain_fixture_is_what_the_committed_generator_produces():
     import chain_vs_oracle as CVO
 
     class A:
-        workload, T, threads, steps, out = "body", 600, 4, 10, os.path.join(os.environ.get("TMPDIR", "/tmp"), "chain_body_first10.npz")
+        workload, T, threads, steps, out = "body", 600, 4, 10, str(tmp_path / "chain_body_first10.npz")
     CVO.side_oracle(A)
     got, want = np.load(A.out), np.load(CVO.golden_path("body"))
     assert sorted(k for k in want.files if k.startswith("step")) == ["step10", "step100", "step50", "step90"]
