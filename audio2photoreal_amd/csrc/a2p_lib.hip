@@ -27,6 +27,7 @@
 #include "kernels_attn.h"
 #include "kernels_attn2.h"
 #include "kernels_attn3.h"
+#include "kernels_audio.h"
 #include "kernels_chain.h"
 #include "kernels_chain4.h"
 #include "kernels_gemm.h"

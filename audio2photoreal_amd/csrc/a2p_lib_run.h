@@ -1386,6 +1386,71 @@ extern "C" int a2p_q_sample(const float* x_start, const int64_t* t_idx, const fl
 }
 
 // ------------------------------------------------------------------------------------------------
+// recording -> y["audio"] (kernels_audio.h)
+// ------------------------------------------------------------------------------------------------
+static int64_t gcd64(int64_t a, int64_t b) {
+  while (b) {
+    const int64_t t = a % b;
+    a = b;
+    b = t;
+  }
+  return a;
+}
+
+static int grid_for(int64_t work) { return (int)std::min<int64_t>((work + 255) / 256, 8192); }
+
+extern "C" int a2p_resample(const float* in, int32_t batch, int64_t len, int32_t in_channels, int32_t orig_freq, int32_t new_freq,
+                            const float* table, int32_t n_phase, int32_t n_taps, int32_t width, float* out, void* stream) {
+  ARG(in && out, "resample: null argument");
+  ARG(batch >= 1 && len >= 1 && len <= ((int64_t)1 << 40), "resample: bad input size (batch=%d len=%lld)", batch, (long long)len);
+  ARG(in_channels >= 1 && in_channels <= A2P_RESAMPLE_MAX_CHANNELS, "resample: in_channels=%d outside [1, %d]", in_channels,
+      A2P_RESAMPLE_MAX_CHANNELS);
+  ARG(orig_freq > 0 && new_freq > 0, "resample: rates must be positive (orig=%d new=%d)", orig_freq, new_freq);
+  hipStream_t s = (hipStream_t)stream;
+  if (orig_freq == new_freq) {
+    const int64_t total = (int64_t)batch * len;
+    resample_sinc_kernel<<<grid_for(total), 256, 0, s>>>(in, len, in_channels, 1, 1, nullptr, 0, 0, len, total, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  const int64_t g = gcd64(orig_freq, new_freq);
+  const int o = (int)(orig_freq / g), n = (int)(new_freq / g);
+  ARG(table, "resample: null table");
+  ARG(n_phase == n && width >= 0 && n_taps == 2 * (int64_t)width + o,
+      "resample: table [%d, %d] with width %d does not fit rates %d -> %d (want [%d, 2 * width + %d])", n_phase, n_taps, width, orig_freq,
+      new_freq, n, o);
+  ARG((int64_t)n_phase * n_taps * (int64_t)sizeof(float) <= A2P_RESAMPLE_MAX_TABLE_BYTES, "resample: table of %lld bytes exceeds %d",
+      (long long)n_phase * n_taps * (long long)sizeof(float), A2P_RESAMPLE_MAX_TABLE_BYTES);
+  const int64_t out_len = (n * len + o - 1) / o;
+  const int64_t total = (int64_t)batch * out_len;
+  resample_sinc_kernel<<<grid_for(total), 256, 0, s>>>(in, len, in_channels, o, n, table, n_taps, width, out_len, total, out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int a2p_dual_audio(const float* mono, int64_t len, float* peak_scratch, const double* noise, double mean0, double mean1,
+                              double std_flat, int32_t reps, float* out, void* stream) {
+  ARG(mono && peak_scratch && noise && out, "dual_audio: null argument");
+  ARG(len >= 1 && len <= ((int64_t)1 << 40) && reps >= 1, "dual_audio: len=%lld reps=%d", (long long)len, reps);
+  ARG(std_flat > 0.0 && isfinite(std_flat) && isfinite(mean0) && isfinite(mean1), "dual_audio: bad statistics (std %g, mean %g %g)",
+      std_flat, mean0, mean1);
+  static_assert(kPeakPartials + 1 == A2P_DUAL_AUDIO_SCRATCH, "peak scratch size");
+  hipStream_t s = (hipStream_t)stream;
+  peak_partial_kernel<<<kPeakPartials, 256, 0, s>>>(mono, len, peak_scratch);
+  HIPCHK(hipGetLastError());
+  peak_final_kernel<<<1, kPeakPartials, 0, s>>>(peak_scratch);
+  HIPCHK(hipGetLastError());
+  float peak = 0.f;
+  HIPCHK(hipMemcpyAsync(&peak, peak_scratch + kPeakPartials, sizeof(float), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  // the demo would divide by zero or flip the signal: a silent (or non-finite) recording is refused before the assembly
+  ARG(peak > 0.f && isfinite(peak), "dual_audio: the recording's peak is %g (silent or non-finite input)", (double)peak);
+  dual_audio_kernel<<<grid_for(len), 256, 0, s>>>(mono, len, peak, noise, mean0, mean1, std_flat, reps, reinterpret_cast<float2*>(out));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // unit entry points
 // ------------------------------------------------------------------------------------------------
 extern "C" int a2p_gemm(a2p_ctx* c, const float* A, const float* W, const float* bias, float* C, int32_t M, int32_t N, int32_t K,

@@ -87,16 +87,19 @@ def load_results(npy_path: str) -> Dict[str, np.ndarray]:
     return np.load(npy_path, allow_pickle=True).item()
 
 
-def _replace_keyframes(model_kwargs, model, uniforms: Optional[torch.Tensor] = None) -> torch.Tensor:
+def _replace_keyframes(model_kwargs, model, uniforms: Optional[torch.Tensor] = None, top_p: Optional[float] = None) -> torch.Tensor:
     """Keyframes predicted by the guide transformer instead of ground truth (reference sample/generate.py:51-71):
     `model.transformer.generate` -> `[B, T, residual_depth]` tokens -> `model.tokenizer.decode`.  The condition is
-    `y["cond_embed"]` (audio features) when present, else `y["audio"]` through the transformer's `audio_frontend`."""
+    `y["cond_embed"]` (audio features) when present, else `y["audio"]` through the transformer's `audio_frontend`.
+    `top_p`: the nucleus of the token sampling (None = `generate`'s default, as reference sample/generate.py:60-65 leaves it;
+    the demo passes 0.97, demo/demo.py:77-83)."""
     y = model_kwargs["y"]
     B, T = y["keyframes"].shape[0], y["keyframes"].shape[1]
     cond = y["cond_embed"] if "cond_embed" in y else y["audio"]
+    nucleus = {} if top_p is None else {"top_p": float(top_p)}
     with torch.no_grad():
         tokens = model.transformer.generate(cond, T, layers=model.tokenizer.residual_depth, n_sequences=B, max_key_len=T,
-                                            max_seq_len=30 * T, uniforms=uniforms)
+                                            max_seq_len=30 * T, uniforms=uniforms, **nucleus)
     tokens = tokens.reshape((B, -1, model.tokenizer.residual_depth))
     pred = model.tokenizer.decode(tokens).detach().cpu()
     assert y["keyframes"].shape == pred.shape, f"{y['keyframes'].shape} vs {pred.shape}"

@@ -1,0 +1,237 @@
+"""From a recording to face codes and body poses: the library form of the demo's `generate_results` (demo/demo.py:156-216),
+without gradio and rendering.
+
+`prepare_recording` turns a waveform at any sample rate into the models' `y["audio"]` on the GPU (resample to 48 kHz, whole
+4 s blocks, peak-normalised channel 0 + N(0, 0.001) partner channel, z-normalisation: csrc/kernels_audio.h);
+`generate_from_recording` runs the face model and guide transformer -> VQ keyframes -> body model on it, with the audio
+features computed once when the models' front ends are identical, and face / body on two HIP streams (`overlap=True`).
+"""
+from __future__ import annotations
+
+from typing import Dict, NamedTuple
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..audio import _resample_rows, resampled_length, sinc_resample_table
+from ..sample_parallel import derive_seed, per_sample_noise
+from .generate import _replace_keyframes
+
+SAMPLE_RATE = 48_000                  # the models' audio rate
+BLOCK = 4 * SAMPLE_RATE               # the demo keeps whole 4 s blocks (demo/demo.py:169-171)
+SAMPLES_PER_FRAME = SAMPLE_RATE // 30
+MAX_FRAMES = 600                      # the denoisers' seq_len: null embeddings of 1998 audio tokens / 20 keyframes (20 s)
+
+
+class PreparedRecording(NamedTuple):
+    audio: torch.Tensor               # y["audio"]: z-normalised dual audio, fp32 [R, Lc, 2] on the GPU
+    T: int                            # frames at 30 fps = Lc / 1600
+    dual_audio: np.ndarray            # the demo's un-normalised dual audio, float64 [2, Lc] (demo/demo.py:212-216, before its float32 cast)
+
+
+def _channels_last(waveform) -> torch.Tensor:
+    """float32 [L, C] on the host, the demo's layout rule: 2-D input is averaged over dim 0 when it has 2 rows, else over dim 1."""
+    t = waveform.detach().cpu() if torch.is_tensor(waveform) else torch.from_numpy(np.ascontiguousarray(np.asarray(waveform)))
+    t = t.to(torch.float32)           # torch.Tensor(y)
+    if t.dim() == 1:
+        return t[:, None]
+    if t.dim() == 2:
+        return t.t() if t.shape[0] == 2 else t
+    raise ValueError(f"a recording is [L] or 2-D [channels, L] / [L, channels] (got shape {tuple(t.shape)})")
+
+
+def _audio_stats(stats):
+    mean = np.asarray(stats["audio_mean"], dtype=np.float64).reshape(-1)
+    std = np.asarray(stats["audio_std_flat"], dtype=np.float64).reshape(-1)
+    if mean.size not in (1, 2) or std.size != 1:
+        raise ValueError(f"audio_mean must hold 1 or 2 values and audio_std_flat 1 (got {mean.size}, {std.size})")
+    return float(mean[0]), float(mean[-1]), float(std[0])
+
+
+def prepare_recording(waveform, sr: int, stats: Dict[str, np.ndarray], num_repetitions: int, seed: int = 10, device="cuda",
+                      max_frames: int = MAX_FRAMES) -> PreparedRecording:
+    """demo/demo.py:159-186: mono -> torchaudio-style resample to 48 kHz -> whole 4 s blocks -> dual audio, tiled over the
+    `num_repetitions` samples.  The partner channel is `np.random.RandomState(seed).normal(0, 0.001, (1, Lc, 2))[..., 1]`.
+
+    `waveform`: [L], or 2-D averaged over `dim = 0 if shape[0] == 2 else 1` (numpy or torch, any numeric dtype, e.g. `read_wav`'s
+    output).  Raises A2PError, before any GPU work, for recordings shorter than 4 s or longer than `max_frames` frames after
+    resampling (long-form generation is out of scope) and for num_repetitions < 1; ValueError for sr <= 0."""
+    if sr <= 0 or int(sr) != sr:
+        raise ValueError(f"sr must be a positive integer rate (got {sr})")
+    sr = int(sr)
+    if num_repetitions < 1:
+        raise _lib.A2PError(f"num_repetitions must be at least 1 (got {num_repetitions})")
+    x = _channels_last(waveform)
+    L, C = x.shape
+    if C > _lib.RESAMPLE_MAX_CHANNELS:
+        raise ValueError(f"{C} channels: at most {_lib.RESAMPLE_MAX_CHANNELS}")
+    Lr = resampled_length(L, sr, SAMPLE_RATE)
+    if Lr < BLOCK:
+        raise _lib.A2PError(f"the recording lasts {Lr / SAMPLE_RATE:.2f} s: at least 4 s are needed")
+    Lc = (Lr // BLOCK) * BLOCK
+    T = Lc // SAMPLES_PER_FRAME
+    if T > max_frames:
+        raise _lib.A2PError(f"the recording keeps {Lc // SAMPLE_RATE} s ({T} frames) but the models take at most {max_frames} frames "
+                            f"({max_frames // 30} s); cut it into shorter clips")
+    mean0, mean1, std = _audio_stats(stats)
+    if sr != SAMPLE_RATE:
+        sinc_resample_table(sr, SAMPLE_RATE)          # size check of the filter table on the host (A2PError) before any upload
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.A2PError(f"prepare_recording runs on the MI355X (got device {device}); there is no CPU implementation")
+
+    xd = x.to(device).contiguous()
+    mono = _resample_rows(xd, L, C, sr, SAMPLE_RATE)[0]                      # [Lr]
+    noise = np.random.RandomState(seed).normal(0, 0.001, (1, Lc, 2))
+    noise_d = torch.from_numpy(noise[0]).to(device)                          # float64 [Lc, 2]
+    out = torch.empty(int(num_repetitions), Lc, 2, device=device, dtype=torch.float32)
+    scratch = torch.empty(_lib.DUAL_AUDIO_SCRATCH, device=device, dtype=torch.float32)
+    with _lib.on_device_of(mono):
+        _lib.check(_lib.load().a2p_dual_audio(_lib.ptr(mono), Lc, _lib.ptr(scratch), _lib.ptr(noise_d), mean0, mean1, std,
+                                              int(num_repetitions), _lib.ptr(out), _lib.current_stream(device)), "a2p_dual_audio")
+    # the demo's float64 dual audio on the host (its return value, un-normalised again: demo/demo.py:178-186, 212-216)
+    y = mono[:Lc].cpu().numpy()
+    dual = noise.copy()
+    dual[:, :, 0] = y / y.max()
+    dual = (dual - stats["audio_mean"]) / stats["audio_std_flat"]
+    dual = dual * stats["audio_std_flat"] + stats["audio_mean"]
+    return PreparedRecording(out, T, np.ascontiguousarray(dual[0].T))
+
+
+def _denoiser(m):
+    return getattr(m, "model", m)
+
+
+def _same_bits(a: torch.Tensor, b: torch.Tensor) -> bool:
+    if a.dtype != b.dtype or a.shape != b.shape or a.device != b.device:
+        return False
+    return bool(torch.equal(a.detach().contiguous().reshape(-1).view(torch.uint8), b.detach().contiguous().reshape(-1).view(torch.uint8)))
+
+
+def can_share_features(face_model, pose_model) -> bool:
+    """True when the two denoisers' native front ends compute the same `encode_audio` features: the same geometry, resampling,
+    precision and bitwise-equal `audio_model.*` parameters (the reference loads one vq-wav2vec.pt into each model)."""
+    from ..model.audio_frontend import NativeAudioFrontend
+    fm, pm = _denoiser(face_model), _denoiser(pose_model)
+    ff, pf = getattr(fm, "audio_frontend", None), getattr(pm, "audio_frontend", None)
+    if not (isinstance(ff, NativeAudioFrontend) and isinstance(pf, NativeAudioFrontend)):
+        return False
+    if fm.precision != pm.precision or ff._precision() != pf._precision() or ff.geometry != pf.geometry or ff.resample != pf.resample:
+        return False
+    a, b = fm.audio_model.state_dict(), pm.audio_model.state_dict()
+    return a.keys() == b.keys() and all(_same_bits(a[k], b[k]) for k in a)
+
+
+def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: int, num_repetitions: int = 1, top_p: float = 0.97,
+                            face_scale: float = 10.0, pose_scale: float = 2.0, seed: int = 10, overlap: bool = True,
+                            share_features: bool = True) -> Dict[str, object]:
+    """`generate_results` (demo/demo.py:156-216) for `num_repetitions` samples of one recording.
+
+    `face` / `pose`: (ClassifierFreeSampleModel, SpacedDiffusion) pairs as `sample.generate._setup_model` builds them, the pose
+    model with its guide transformer and VQ tokenizer attached (`setup_guide_predictor`) and both with an audio front end.
+    Face: ddim_sample_loop at `face_scale`; body: keyframes from the guide transformer (nucleus `top_p`), all-true mask,
+    ddim_sample_loop at `pose_scale`.  Every random draw is a function of `seed` and the repetition index (derive_seed /
+    per_sample_noise), so the result does not depend on `overlap`.
+
+    `share_features`: compute `encode_audio` once and give it to the guide, the body model and the face model's lip input when
+    `can_share_features` holds (else each model runs its own front end on y["audio"]; a guide transformer without a front end
+    of its own takes the body model's features).  `overlap`: face on one HIP stream, guide -> VQ decode -> body on another;
+    False runs face, then body, as the demo does.
+
+    Returns {"face": [R, T, 256], "pose": [R, T, 104], "keyframes": [R, T / 30, 104] (un-normalised with the code_* / pose_*
+    statistics: * std + mean), "audio": the un-normalised dual audio float64 [2, Lc], "T", "sr": 48000}."""
+    from ..model.audio_frontend import NativeAudioFrontend
+    face_m, face_d = face
+    pose_m, pose_d = pose
+    fm, pm = _denoiser(face_m), _denoiser(pose_m)
+    for name, m in (("face", fm), ("pose", pm)):
+        if getattr(m, "audio_frontend", None) is None:
+            raise _lib.A2PError(f"the {name} model has no audio front end: construct it with audio_frontend=\"native\"")
+    if getattr(pm, "transformer", None) is None or getattr(pm, "tokenizer", None) is None:
+        raise _lib.A2PError("the pose model has no guide transformer: attach it with setup_guide_predictor(transformer, tokenizer)")
+    device = fm.null_cond_embed.device
+    R = int(num_repetitions)
+    prep = prepare_recording(waveform, sr, stats, R, seed, device, max_frames=min(fm.seq_len, pm.seq_len))
+    audio, T = prep.audio, prep.T
+    nk = len(range(T)[::30])
+
+    uniforms = torch.stack([torch.rand(nk * pm.tokenizer.residual_depth, generator=torch.Generator().manual_seed(derive_seed(seed, 1, r)))
+                            for r in range(R)], dim=1)                    # [n, R]: column r belongs to repetition r
+    noise_pose = per_sample_noise((R, pm.nfeats, 1, T), [derive_seed(seed, 2, r) for r in range(R)]).to(device)
+    noise_face = per_sample_noise((R, fm.nfeats, 1, T), [derive_seed(seed, 3, r) for r in range(R)]).to(device)
+
+    with torch.no_grad():
+        if share_features and can_share_features(face_m, pose_m):
+            feats = pm.audio_frontend.encode_audio(audio)
+            guide_cond = {"cond_embed": feats}
+            body_cond = {"cond_embed": pm.audio_frontend.encode_lip(audio, feats) if pm.audio_frontend.has_lip else feats}
+            face_cond = {"cond_embed": fm.audio_frontend.encode_lip(audio, feats) if fm.audio_frontend.has_lip else feats}
+        else:
+            body_cond, face_cond = {"audio": audio}, {"audio": audio}
+            if getattr(pm.transformer, "audio_frontend", None) is not None:
+                guide_cond = {"audio": audio}
+            elif isinstance(pm.audio_frontend, NativeAudioFrontend):
+                guide_cond = {"cond_embed": pm.audio_frontend.encode_audio(audio)}
+            else:
+                raise _lib.A2PError("the guide transformer has no audio front end and the pose model's is not the native one: "
+                                    "construct GuideTransformer(audio_frontend=callable)")
+        y_face = {**face_cond, "scale": torch.full((R,), float(face_scale), device=device)}
+        y_body = {**body_cond, "mask": torch.ones(R, 1, 1, T, dtype=torch.bool, device=device),
+                  "scale": torch.full((R,), float(pose_scale), device=device)}
+
+        def run_face():
+            return face_d.ddim_sample_loop(face_m, (R, fm.nfeats, 1, T), noise=noise_face, clip_denoised=False, model_kwargs={"y": y_face})
+
+        def run_body():
+            guide_y = {**guide_cond, "keyframes": torch.zeros(R, nk, pm.nfeats, device=device)}
+            y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p).to(device)
+            return pose_d.ddim_sample_loop(pose_m, (R, pm.nfeats, 1, T), noise=noise_pose, clip_denoised=False, model_kwargs={"y": y_body})
+
+        if overlap:
+            face_s, body_s = _overlapped(face, pose, run_face, run_body, device)
+        else:
+            face_s = run_face()
+            body_s = run_body()
+
+    face_np = face_s.squeeze(2).cpu().numpy().transpose(0, 2, 1)
+    pose_np = body_s.squeeze(2).cpu().numpy().transpose(0, 2, 1)
+    kf = y_body["keyframes"].cpu().numpy()
+    return {"face": face_np * stats["code_std"] + stats["code_mean"],
+            "pose": pose_np * stats["pose_std"] + stats["pose_mean"],
+            "keyframes": kf * stats["pose_std"] + stats["pose_mean"],
+            "audio": prep.dual_audio, "T": T, "sr": SAMPLE_RATE}
+
+
+def _overlapped(face, pose, run_face, run_body, device):
+    """Face on one HIP stream, guide -> VQ decode -> body on another, from this host thread (bench.py PipelineSubject.overlapped).
+    The loops' once-per-call non-finite check waits for its stream, so it is deferred until both streams are loaded and then
+    made per stream; a model that escalates to fp32 there (FiLMTransformer.check_finite) has its loop repeated, as the
+    non-deferred loops do."""
+    main = torch.cuda.current_stream(device)
+    s_face, s_body = torch.cuda.Stream(device), torch.cuda.Stream(device)
+    s_face.wait_stream(main)
+    s_body.wait_stream(main)
+    diffs = (face[1], pose[1])
+    for d in diffs:
+        d.defer_finite_check = True
+    try:
+        with torch.cuda.stream(s_face):               # enqueued first: nothing on this stream blocks the host
+            face_s = run_face()
+        with torch.cuda.stream(s_body):
+            body_s = run_body()
+        with torch.cuda.stream(s_face):
+            redo_face = face[0].a2p_check_finite() == "escalated"
+        with torch.cuda.stream(s_body):
+            redo_body = pose[0].a2p_check_finite() == "escalated"
+    finally:
+        for d in diffs:
+            d.defer_finite_check = False
+    main.wait_stream(s_face)
+    main.wait_stream(s_body)
+    torch.cuda.synchronize(device)
+    if redo_face:
+        face_s = run_face()
+    if redo_body:
+        body_s = run_body()
+    return face_s, body_s

@@ -13,7 +13,8 @@
  *  - tensors are dense row-major fp32 unless stated; int64 for timesteps
  *    (the reference passes torch.long, gaussian_diffusion.py:911);
  *  - all work is enqueued on `stream` (a hipStream_t passed as void*); nothing
- *    synchronises the device except a2p_ctx_destroy and a2p_kernel_time_ms;
+ *    synchronises the device except a2p_ctx_destroy, a2p_kernel_time_ms and a2p_dual_audio
+ *    (which reads one float back);
  *  - return value: 0 = ok, negative = A2P_ERR_* (no exceptions cross the ABI);
  *    a2p_last_error() returns a static thread-local message;
  *  - inputs are borrowed for the duration of the enqueued work, outputs are
@@ -160,6 +161,25 @@ int a2p_ddim_reverse_update(const float* pred_xstart, const float* x, const int6
 /* q_sample (gaussian_diffusion.py:215-233). */
 int a2p_q_sample(const float* x_start, const int64_t* t_idx, const float* tables, int32_t n_steps,
                  const float* noise, int32_t batch, int64_t per_sample, float* out, void* stream);
+
+/* ---- recording -> y["audio"] (demo/demo.py:156-189, generate_results; audio2photoreal_amd/audio.py) ----------
+ * torchaudio.functional.resample (sinc_interp_hann / sinc_interp_kaiser): in fp32 [batch, len, in_channels] (channels
+ * interleaved and averaged to mono on the way in; in_channels = 1: [batch, len]) -> out fp32 [batch, ceil(n len / o)], with
+ * o = orig_freq / g, n = new_freq / g, g = gcd.  table fp32 [n_phase = n, n_taps = 2 width + o]: the filter bank of
+ * _get_sinc_resample_kernel, built by the caller.  out[b][m] = sum_j table[m mod n][j] xpad[(m div n) o + j], xpad = the mono
+ * row with `width` zeros on the left.  orig_freq == new_freq: table may be NULL and out = the (averaged) input. */
+#define A2P_RESAMPLE_MAX_TABLE_BYTES (16 << 20)
+#define A2P_RESAMPLE_MAX_CHANNELS 64
+int a2p_resample(const float* in, int32_t batch, int64_t len, int32_t in_channels, int32_t orig_freq, int32_t new_freq,
+                 const float* table, int32_t n_phase, int32_t n_taps, int32_t width, float* out, void* stream);
+/* The demo's dual audio from the resampled mono signal mono fp32 [len] (already cut to whole 4 s blocks):
+ * peak = max(mono) (A2P_ERR_ARG when it is not > 0: silent input), then for every repetition r < reps
+ *   out[r][i][0] = float(((double)(mono[i] / peak) - mean0) / std_flat),  out[r][i][1] = float((noise[i][1] - mean1) / std_flat)
+ * with noise fp64 [len, 2] (the caller's N(0, 0.001) draws); out fp32 [reps, len, 2].  peak_scratch: A2P_DUAL_AUDIO_SCRATCH
+ * floats of device memory.  Synchronises `stream` once, to read the peak. */
+#define A2P_DUAL_AUDIO_SCRATCH 257
+int a2p_dual_audio(const float* mono, int64_t len, float* peak_scratch, const double* noise, double mean0, double mean1,
+                   double std_flat, int32_t reps, float* out, void* stream);
 
 /* ---- unit entry points (parity tests of single kernels / one decoder layer) -----
  * FiLMTransformerDecoderLayer.forward (model/modules/transformer_modules.py:178-217):
