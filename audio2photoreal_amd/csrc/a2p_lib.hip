@@ -423,8 +423,12 @@ static int launch_ln_rope(a2p_ctx* c, bool as_f32, const float* x, int64_t ldx, 
   return 0;
 }
 
-static int launch_attn(a2p_ctx* c, const AttnP& p0, int nseq, int kind, hipStream_t s, bool ksplit = false) {
+// nseq_rule: the sequence count the size rule below decides attn3_kernel vs attn_kernel from (0: nseq).  Denoiser forwards pass
+// the count of the UNSHARDED batch (hinted_nseq, a2p_set_batch_hint): the two kernels differ in rounding, and a shard must take
+// the kernel of the single-process run.  Grids and p.nseq stay local.
+static int launch_attn(a2p_ctx* c, const AttnP& p0, int nseq, int kind, hipStream_t s, bool ksplit = false, int nseq_rule = 0) {
   AttnP p = p0;
+  if (nseq_rule <= 0) nseq_rule = nseq;
   // small forwards (decoder_layer_small): the waves of a workgroup split the keys instead of the queries (kernels_attn.h)
   if ((ksplit || c->opt.force_ksplit) && c->bf16 && !c->opt.no_ksplit && (c->DH == 64 || c->DH == 32) && p.ldvt % 8 == 0 && p.S_tail <= 2) {
     // waves x query tiles per wave: A2P_KSPLIT_NW / A2P_KSPLIT_QT (experiment switches)
@@ -475,14 +479,15 @@ static int launch_attn(a2p_ctx* c, const AttnP& p0, int nseq, int kind, hipStrea
   if (c->bf16 && c->opt.attn3 && !c->opt.attn2 && (c->DH == 64 || c->DH == 32) && p.ldvt % 8 == 0) {
     const int nq3 = (p.Tq + 319) / 320;
     const int64_t wgs = (int64_t)nq3 * c->H * nseq;
+    const int64_t wgs_rule = (int64_t)nq3 * c->H * nseq_rule;
     // v5 (row sums on the matrix pipe; profiles/r06_attn3_bench_v5.txt): also x1.19 on the body model's cross attention (head_dim 32, 2000 keys, 512 workgroups:
     // 81 vs 97 us); its self attention (600 keys) and the B=32 face self attention stay x0.9
     const int S3 = p.S_main + p.S_tail;
     // ... and NOT below one attn_kernel workgroup per CU (profiles/r06_attn3_small_batch.txt: up to 6 sequences of 600 frames attn_kernel's 128-query workgroups
     // are one round of <= 240 and finish in 32-36 us (cross) / 13-14 us (self) where attn3's 320-query workgroups take their fixed 41-44 / 19 us: x0.7-0.8;
     // from 8 sequences on attn_kernel needs a second round and attn3 leads x1.18 / x1.02)
-    const int64_t wgs1 = (int64_t)p.nq * c->H * nseq;   // attn_kernel's grid
-    const bool wins = p.Tq >= 160 && wgs1 > 256 && ((c->DH == 64 && (S3 >= 1024 || wgs <= 256)) || (c->DH == 32 && S3 >= 1024));
+    const int64_t wgs1_rule = (int64_t)p.nq * c->H * nseq_rule;   // attn_kernel's grid (of the unsharded batch)
+    const bool wins = p.Tq >= 160 && wgs1_rule > 256 && ((c->DH == 64 && (S3 >= 1024 || wgs_rule <= 256)) || (c->DH == 32 && S3 >= 1024));
     if (c->opt.attn3 >= 2 || wins) {
       p.nq = nq3;
       dim3 grid3((unsigned)wgs);
@@ -695,6 +700,7 @@ extern "C" int a2p_ctx_create(const a2p_config* cfg, a2p_ctx** out) {
 
 extern "C" int a2p_set_batch_hint(a2p_ctx* c, int32_t global_batch) {
   ARG(c && global_batch >= 0, "bad arguments");
+  if (global_batch != c->batch_hint) ++c->graph_epoch;   // a captured forward (A2P_GRAPH) carries the attention kernels of the hint it was captured under
   c->batch_hint = global_batch;
   return 0;
 }

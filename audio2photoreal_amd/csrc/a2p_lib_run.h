@@ -39,9 +39,14 @@ static int film_gemm(a2p_ctx* c, const void* A, int64_t lda, const std::string& 
   return launch_gemm(c, p, s);
 }
 
+// The sequence count launch_attn's size rule decides from (its nseq_rule): n sequences of a batch of B samples, scaled to the
+// UNSHARDED batch when the host names it (a2p_set_batch_hint) -- the scaling run_forward's rows_eff applies to the kernel family.
+// B = 0 (the layer / attention entry points called directly through the ABI): n, whatever the hint.
+static int hinted_nseq(const a2p_ctx* c, int n, int B) { return (B > 0 && c->batch_hint > B) ? n / B * c->batch_hint : n; }
+
 // self attention block on the residual stream c->x: x += FiLM(out_proj(MHA(rot(LN x), rot(LN x), LN x)))
 static int self_attn_block(a2p_ctx* c, const std::string& p, const std::string& norm, int N, int T, const FilmRef& fr, int film_idx,
-                           hipStream_t s) {
+                           hipStream_t s, int nseq_rule = 0) {
   const int d = c->d, M = N * T;
   const int Tld = rup(T, 64);
   CHK(launch_ln_rope(c, false, c->x.f(), d, W32(c, norm + ".weight"), W32(c, norm + ".bias"), c->xn.p, c->xr.p, d, M, T, 0, s));
@@ -62,12 +67,12 @@ static int self_attn_block(a2p_ctx* c, const std::string& p, const std::string& 
   a.O = c->ao.p; a.o_seq_stride = (int64_t)T * d; a.ldo = d;
   a.tail_mod = 1; a.Tq = T; a.S_main = T; a.S_tail = 0;
   a.scale_log2e = 1.4426950408889634f / sqrtf((float)c->DH);
-  CHK(launch_attn(c, a, N, A2P_KERNEL_ATTN_SELF, s));
+  CHK(launch_attn(c, a, N, A2P_KERNEL_ATTN_SELF, s, false, nseq_rule));
   return film_gemm(c, c->ao.p, d, p + ".out_proj.weight", W32(c, p + ".out_proj.bias"), d, fr, film_idx, M, T, s);
 }
 
 static int cross_attn_block(a2p_ctx* c, const std::string& p, const std::string& norm, int N, int T, const CrossKV& kv,
-                            const FilmRef& fr, int film_idx, hipStream_t s) {
+                            const FilmRef& fr, int film_idx, hipStream_t s, int nseq_rule = 0) {
   const int d = c->d, M = N * T;
   CHK(launch_ln_rope(c, false, c->x.f(), d, W32(c, norm + ".weight"), W32(c, norm + ".bias"), nullptr, c->xr.p, d, M, T, 0, s));
   GemmP pq = gemm_base(c->xr.p, d, c->wt.at(p + ".in_proj_weight").p, d, W32(c, p + ".in_proj_bias"), c->qk.p, d, M, d, d);
@@ -83,7 +88,7 @@ static int cross_attn_block(a2p_ctx* c, const std::string& p, const std::string&
   a.slot_rule = kv.slot_rule; a.slot_b = kv.slot_b;
   a.kv_stream = kv.slots && !c->opt.kv_cached ? 1 : 0;
   a.scale_log2e = 1.4426950408889634f / sqrtf((float)c->DH);
-  CHK(launch_attn(c, a, N, A2P_KERNEL_ATTN_CROSS, s));
+  CHK(launch_attn(c, a, N, A2P_KERNEL_ATTN_CROSS, s, false, nseq_rule));
   return film_gemm(c, c->ao.p, d, p + ".out_proj.weight", W32(c, p + ".out_proj.bias"), d, fr, film_idx, M, T, s);
 }
 
@@ -632,7 +637,7 @@ static int launch_chain(a2p_ctx* c, int mode, const ChainP& p, hipStream_t s) {
   return 0;
 }
 
-static int launch_self_attention(a2p_ctx* c, int N, int T, hipStream_t s, bool ksplit = false) {
+static int launch_self_attention(a2p_ctx* c, int N, int T, hipStream_t s, bool ksplit = false, int nseq_rule = 0) {
   const int d = c->d, Tld = rup(T, 64);
   AttnP a;
   memset(&a, 0, sizeof(a));
@@ -642,10 +647,10 @@ static int launch_self_attention(a2p_ctx* c, int N, int T, hipStream_t s, bool k
   a.O = c->ao.p; a.o_seq_stride = (int64_t)T * d; a.ldo = d;
   a.tail_mod = 1; a.Tq = T; a.S_main = T; a.S_tail = 0;
   a.scale_log2e = 1.4426950408889634f / sqrtf((float)c->DH);
-  return launch_attn(c, a, N, A2P_KERNEL_ATTN_SELF, s, ksplit);
+  return launch_attn(c, a, N, A2P_KERNEL_ATTN_SELF, s, ksplit, nseq_rule);
 }
 
-static int launch_cross_attention(a2p_ctx* c, int N, int T, const CrossKV& kv, hipStream_t s, bool ksplit = false) {
+static int launch_cross_attention(a2p_ctx* c, int N, int T, const CrossKV& kv, hipStream_t s, bool ksplit = false, int nseq_rule = 0) {
   const int d = c->d;
   AttnP a;
   memset(&a, 0, sizeof(a));
@@ -658,16 +663,17 @@ static int launch_cross_attention(a2p_ctx* c, int N, int T, const CrossKV& kv, h
   a.slot_rule = kv.slot_rule; a.slot_b = kv.slot_b;
   a.kv_stream = kv.slots && !c->opt.kv_cached ? 1 : 0;
   a.scale_log2e = 1.4426950408889634f / sqrtf((float)c->DH);
-  return launch_attn(c, a, N, A2P_KERNEL_ATTN_CROSS, s, ksplit);
+  return launch_attn(c, a, N, A2P_KERNEL_ATTN_CROSS, s, ksplit, nseq_rule);
 }
 
 // FiLMTransformerDecoderLayer.forward as PRE? | self attention | MID | cross attention | (MID | cross attention 2) | POST
 // shared_half: classifier-free guidance, layer 0 -- both halves of the 2B sequences start from the same x (one input
 // projection) and therefore share norm1 / Q,K,V / the self attention: those run on the first N/2 sequences only, and the MID
 // kernel of the second half reads the first half's rows (ChainP::src_rows)
+// rule_B: the batch the N sequences belong to, for the attention kernels' size rule (hinted_nseq; 0: N alone) -- also below
 static int decoder_layer_chain(a2p_ctx* c, int l, int N, int T, const CrossKV& kv, const CrossKV* kv2, const FilmRef& fr, bool first,
                                bool has_next, hipStream_t s, hipEvent_t film_ready = nullptr, bool fuse_final = false,
-                               bool shared_half = false, bool* fused_x3 = nullptr, const float* x_in_fused = nullptr) {
+                               bool shared_half = false, bool* fused_x3 = nullptr, const float* x_in_fused = nullptr, int rule_B = 0) {
   const int d = c->d;
   const std::string pf = "seqTransDecoder.stack." + std::to_string(l) + ".";
   ChainP p;
@@ -693,7 +699,7 @@ static int decoder_layer_chain(a2p_ctx* c, int l, int N, int T, const CrossKV& k
     }
   }
   if (film_ready && join_at == 2) HIPCHK(hipStreamWaitEvent(s, film_ready, 0));
-  CHK(launch_self_attention(c, Nsa, T, s));
+  CHK(launch_self_attention(c, Nsa, T, s, false, hinted_nseq(c, Nsa, rule_B)));
   if (film_ready && join_at >= 3) HIPCHK(hipStreamWaitEvent(s, film_ready, 0));  // FiLM / time-token K,V of this step (side stream)
   auto mid = [&](int kind, const std::string& attn_done, int film_idx, const std::string& norm) -> int {
     chain_base(c, p, N, T, ch_index(l, kind), d);
@@ -711,7 +717,7 @@ static int decoder_layer_chain(a2p_ctx* c, int l, int N, int T, const CrossKV& k
     return launch_chain(c, CHAIN_MID, p, s);
   };
   CHK(mid(CH_MID, "self_attn", 0, "norm2"));
-  CHK(launch_cross_attention(c, N, T, kv, s));
+  CHK(launch_cross_attention(c, N, T, kv, s, false, hinted_nseq(c, N, rule_B)));
   // body model: MID2 | keyframe attention | POST as ONE kernel (kernels_chain.h CHAIN_MIDPOST) when the keyframes fit one 32-key chunk
   // (T <= 960 frames at the reference's keyframe step of 30); A2P_NO_FUSED_KF=1 keeps the three launches (A/B, tests)
   // The fused attention phase is written for 8 heads x 32 (the reference's pose configuration): wave w = head w, K / V^T fragments of
@@ -721,7 +727,7 @@ static int decoder_layer_chain(a2p_ctx* c, int l, int N, int T, const CrossKV& k
                        kv2->S_tail == 0 && !c->opt.no_fused_kf && !fuse_final;
   if (kv2 && !fuse_kf) {
     CHK(mid(CH_MID2, "multihead_attn", 1, "norm2a"));
-    CHK(launch_cross_attention(c, N, T, *kv2, s));
+    CHK(launch_cross_attention(c, N, T, *kv2, s, false, hinted_nseq(c, N, rule_B)));
   }
   chain_base(c, p, N, T, ch_index(l, fuse_kf ? CH_MIDPOST : CH_POST), c->ff + (has_next ? 3 * d : 0));
   if (fuse_kf) {
@@ -761,11 +767,13 @@ static int decoder_layer_chain(a2p_ctx* c, int l, int N, int T, const CrossKV& k
 }
 
 // FiLMTransformerDecoderLayer.forward (transformer_modules.py:178-217) on c->x
-static int decoder_layer(a2p_ctx* c, int l, int N, int T, const CrossKV& kv, const CrossKV* kv2, const FilmRef& fr, hipStream_t s) {
+static int decoder_layer(a2p_ctx* c, int l, int N, int T, const CrossKV& kv, const CrossKV* kv2, const FilmRef& fr, hipStream_t s,
+                         int rule_B = 0) {
   const std::string p = "seqTransDecoder.stack." + std::to_string(l) + ".";
-  CHK(self_attn_block(c, p + "self_attn", p + "norm1", N, T, fr, 0, s));
-  CHK(cross_attn_block(c, p + "multihead_attn", p + "norm2", N, T, kv, fr, 1, s));
-  if (kv2) CHK(cross_attn_block(c, p + "multihead_attn2", p + "norm2a", N, T, *kv2, fr, 3, s));
+  const int n_rule = hinted_nseq(c, N, rule_B);
+  CHK(self_attn_block(c, p + "self_attn", p + "norm1", N, T, fr, 0, s, n_rule));
+  CHK(cross_attn_block(c, p + "multihead_attn", p + "norm2", N, T, kv, fr, 1, s, n_rule));
+  if (kv2) CHK(cross_attn_block(c, p + "multihead_attn2", p + "norm2a", N, T, *kv2, fr, 3, s, n_rule));
   return ffn_block(c, p, p + "norm3", N * T, T, fr, 2, s);
 }
 
@@ -787,7 +795,7 @@ static int launch_small(a2p_ctx* c, const SmallP& p, hipStream_t s) {
 }
 
 static int decoder_layer_small(a2p_ctx* c, int l, int N, int T, const CrossKV& kv, const FilmRef& fr, hipStream_t s,
-                               hipEvent_t film_ready = nullptr) {
+                               hipEvent_t film_ready = nullptr, int rule_B = 0) {
   const int d = c->d, ff = c->ff, M = N * T, Tld = rup(T, 64);
   const std::string pf = "seqTransDecoder.stack." + std::to_string(l) + ".";
   SmallP base;
@@ -807,7 +815,7 @@ static int decoder_layer_small(a2p_ctx* c, int l, int N, int T, const CrossKV& k
     p.out_t = reinterpret_cast<h16_t*>(c->vt.p); p.ld_t = Tld; p.t_seq_stride = (int64_t)d * Tld;
     CHK((launch_small<512, 64, 1, SMALL_STORE>(c, p, s)));
   }
-  CHK(launch_self_attention(c, N, T, s, true));
+  CHK(launch_self_attention(c, N, T, s, true, hinted_nseq(c, N, rule_B)));
   if (film_ready) HIPCHK(hipStreamWaitEvent(s, film_ready, 0));   // FiLM / time-token K,V of this step come from the side stream
   {  // out_proj + FiLM + residual
     SmallP p = base;
@@ -823,7 +831,7 @@ static int decoder_layer_small(a2p_ctx* c, int l, int N, int T, const CrossKV& k
     p.N = d; p.out = reinterpret_cast<h16_t*>(c->qk.p); p.ldo = d; p.n_store = d;
     CHK((launch_small<512, 64, 1, SMALL_STORE>(c, p, s)));
   }
-  CHK(launch_cross_attention(c, N, T, kv, s, true));
+  CHK(launch_cross_attention(c, N, T, kv, s, true, hinted_nseq(c, N, rule_B)));
   {
     SmallP p = base;
     p.a = reinterpret_cast<const h16_t*>(c->ao.p); p.lda = d; p.W = reinterpret_cast<const h16_t*>(c->wt.at(pf + "multihead_attn.out_proj.weight").p);
@@ -885,7 +893,7 @@ extern "C" int a2p_prepare_cond(a2p_ctx* c, const float* cond_embed, int32_t B, 
     FilmRef none;
     for (int i = 0; i < 2; ++i) {
       const std::string p = "cond_encoder." + std::to_string(i) + ".";
-      CHK(self_attn_block(c, p + "self_attn", p + "norm1", B, S0, none, 0, s));
+      CHK(self_attn_block(c, p + "self_attn", p + "norm1", B, S0, none, 0, s, hinted_nseq(c, B, B)));   // (a shard's encoder rows: the unsharded batch's kernel)
       CHK(ffn_block(c, p, p + "norm2", M, S0, none, 0, s));
     }
   }
@@ -1083,9 +1091,10 @@ static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, in
     fr.seq_stride = (int64_t)L * F * 2 * d;
     if (use_chain)
       CHK(decoder_layer_chain(c, l, N, T, kv, c->pose ? &kv2 : nullptr, fr, l == 0, l + 1 < L, s, (overlap_tpath && l == 0) ? c->ev_join : nullptr,
-                              /*fuse_final=*/!c->pose && !c->tail32, /*shared_half=*/l == 0 && N == 2 * B && !c->opt.no_shared_half, &fused_x3, (l == 0 && fuse_in) ? x_in : nullptr));
-    else if (use_small) CHK(decoder_layer_small(c, l, N, T, kv, fr, s, (overlap_tpath && l == 0) ? c->ev_join : nullptr));
-    else CHK(decoder_layer(c, l, N, T, kv, c->pose ? &kv2 : nullptr, fr, s));
+                              /*fuse_final=*/!c->pose && !c->tail32, /*shared_half=*/l == 0 && N == 2 * B && !c->opt.no_shared_half, &fused_x3, (l == 0 && fuse_in) ? x_in : nullptr,
+                              /*rule_B=*/B));
+    else if (use_small) CHK(decoder_layer_small(c, l, N, T, kv, fr, s, (overlap_tpath && l == 0) ? c->ev_join : nullptr, B));
+    else CHK(decoder_layer(c, l, N, T, kv, c->pose ? &kv2 : nullptr, fr, s, B));
   }
   // (the family calibration times the decoder stack INCLUDING final_layer: the tall last-layer kernel may contain it)
   struct TuneEnd { hipEvent_t e; hipStream_t s; ~TuneEnd() { if (e) (void)hipEventRecord(e, s); } } tune_end{tune1, s};

@@ -212,10 +212,13 @@ int a2p_attention(a2p_ctx* ctx, const float* q, const float* k, const float* v, 
 int a2p_kernel_timing(a2p_ctx* ctx, int32_t kind, int32_t enable);
 int a2p_kernel_time_ms(a2p_ctx* ctx, double* total_ms, int64_t* launches);
 
-/* ---- sample-parallel runs: which kernel family a forward takes (fused row-panel chains for large forwards, small-tile GEMMs for
- * small ones) depends on its row count, and the families differ in operand rounding.  A rank that denoises a BLOCK of a larger
- * batch names the size of the whole batch here, so that every shard takes the family the unsharded run takes and the gathered
- * samples equal the single-process samples bit for bit (sample_parallel.py does this; 0 = no hint). */
+/* ---- sample-parallel runs: the kernel family and attention kernel a forward takes depend on its size, and both choices differ in
+ * operand rounding: fused row-panel chains for large forwards, small-tile GEMMs for small ones (row count); attn3_kernel or
+ * attn_kernel (sequence count).  A rank that denoises a BLOCK of a larger batch names the size of the whole batch here, so that
+ * every shard takes the kernel family and attention kernel the unsharded run takes -- in the denoiser forwards and the face model's
+ * cond encoder (a2p_prepare_cond) -- and the gathered samples equal the single-process samples bit for bit (sample_parallel.py does
+ * this; 0 = no hint: every choice follows the local batch).  Only the decisions follow the hint; grids stay local.  Entry points
+ * called directly (a2p_attention, a2p_decoder_layer_forward, the audio front end) ignore it. */
 int a2p_set_batch_hint(a2p_ctx* ctx, int32_t global_batch);
 
 /* ---- non-finite detection ------------------------------------------------------

@@ -3,7 +3,10 @@
 Launched as `python -m torch.distributed.run --nproc-per-node 2 tests/dist_worker_gpu.py`: every rank opens its own HIP
 context on cuda:0 (single-GPU box), collectives go over gloo (host memory), the sampler is the product's HIP path driven
 through `sample_parallel` exactly like sample/generate.py does.  Production differs only in `cuda:LOCAL_RANK` + backend
-"nccl" (= RCCL over xGMI)."""
+"nccl" (= RCCL over xGMI).
+
+A2P_DIST_GEOMETRY="samples,frames,layers,respacing" (face model) selects another geometry; the default is DEFAULT_GEOMETRY
+(tests/test_shard_invariance_hip.py runs the full-size face configuration over 4 ranks)."""
 import os
 import sys
 
@@ -13,17 +16,24 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-TOTAL, T, LAYERS = 4, 240, 2
+DEFAULT_GEOMETRY = "4,240,2,ddim10"
 
 
-def run_sampler(precision, dev, world, rank):
+def parse_geometry(geometry=None):
+    total, frames, layers, respacing = (geometry or os.environ.get("A2P_DIST_GEOMETRY") or DEFAULT_GEOMETRY).split(",")
+    return int(total), int(frames), int(layers), respacing
+
+
+def run_sampler(precision, dev, world, rank, geometry=None):
     from audio2photoreal_amd.model.cfg_sampler import ClassifierFreeSampleModel
     from audio2photoreal_amd.model_util import create_model_and_diffusion, default_args, load_model
     from audio2photoreal_amd.sample_parallel import per_sample_noise, sample_parallel
     from audio2photoreal_amd.spec import face_spec
     from audio2photoreal_amd.synthetic import cond_tokens_for_frames, synthetic_state_dict, synthetic_tensor
+    TOTAL, T, LAYERS, respacing = parse_geometry(geometry)
+    steps = int(respacing[len("ddim"):])
     spec = face_spec(num_layers=LAYERS)
-    model, diffusion = create_model_and_diffusion(default_args("face", layers=LAYERS, timestep_respacing="ddim10"), "test",
+    model, diffusion = create_model_and_diffusion(default_args("face", layers=LAYERS, timestep_respacing=respacing), "test",
                                                   precision=precision, max_batch=TOTAL)
     load_model(model, synthetic_state_dict(spec, 10))
     cfg = ClassifierFreeSampleModel(model.to(dev).eval())
@@ -33,7 +43,7 @@ def run_sampler(precision, dev, world, rank):
          "scale": torch.full((TOTAL,), 10.0, device=dev)}
     shape = (TOTAL, spec.nfeats, 1, T)
     noise = per_sample_noise(shape, [1000 + g for g in range(TOTAL)])          # row g depends only on the global sample id
-    step_noise = [per_sample_noise(shape, [77 * (n + 1) + g for g in range(TOTAL)]).to(dev) for n in range(10)]
+    step_noise = [per_sample_noise(shape, [77 * (n + 1) + g for g in range(TOTAL)]).to(dev) for n in range(steps)]
     with torch.no_grad():
         out = sample_parallel(diffusion.ddim_sample_loop, cfg, shape, {"y": y}, noise=noise.to(dev), step_noise=step_noise,
                               clip_denoised=False, eta=0.5)                    # eta > 0: the per-step noise path is exercised too

@@ -259,14 +259,19 @@ def test_config0_ddim10_16bit_vs_reference_golden(dev, golden, precision):
     assert e < {"bf16": 6e-3, "fp16": 1e-3}[precision], e
 
 
-@pytest.mark.parametrize("attn3", ["0", "2"])
+@pytest.mark.parametrize("attn3", ["0", "2", "default"])
 def test_properties_full_size(dev, attn3, monkeypatch):
     """Size-independent properties at BASELINE config-1 size (face, B=8, T=600), bf16 mode:
     batch independence (sample b does not depend on its neighbours) and determinism.
     With the attention kernel pinned (A2P_ATTN3=0: attn_kernel everywhere, 2: attn3_kernel wherever it is legal): launch_attn's default rule sends a launch to one or the other
     by its SIZE (round 6: attn_kernel while its grid is one round -- the sub-batch's launches, and layer 0's shared-half self attention of a small guided batch), and the two
-    are different 16-bit roundings of the same softmax (4e-4 in fp16, 2e-3 in bf16), not the same bits.  The property is about batch POSITION: same kernels on both sides."""
-    monkeypatch.setenv("A2P_ATTN3", attn3)
+    are different 16-bit roundings of the same softmax (4e-4 in fp16, 2e-3 in bf16), not the same bits.  The property is about batch POSITION: same kernels on both sides.
+    `default` (A2P_ATTN3 unset): the sub-batch names the batch it belongs to (global_batch_hint = 8, what sample_parallel does), so the default rule
+    picks the full batch's kernels for it and its rows must be the full batch's bits."""
+    if attn3 == "default":
+        monkeypatch.delenv("A2P_ATTN3", raising=False)
+    else:
+        monkeypatch.setenv("A2P_ATTN3", attn3)
     spec, _ = get_model("face", "bf16", dev)
     args = default_args("face", timestep_respacing="")
     model, _ = create_model_and_diffusion(args, "test", precision="bf16", max_batch=8)
@@ -280,10 +285,14 @@ def test_properties_full_size(dev, attn3, monkeypatch):
     again = cfg(x, t, y)
     assert torch.equal(full, again)
     y2 = {"cond_embed": y["cond_embed"][2:4].contiguous(), "scale": y["scale"][2:4].contiguous()}
+    model.global_batch_hint = 8 if attn3 == "default" else 0
     part = cfg(x[2:4].contiguous(), t[2:4], y2)
+    model.global_batch_hint = 0
     model.release()
     monkeypatch.delenv("A2P_ATTN3", raising=False)
     assert rel_l2(part.cpu(), full[2:4].cpu()) < 1e-6
+    if attn3 == "default":
+        assert torch.equal(part, full[2:4])
     assert torch.isfinite(full).all()
 
 
