@@ -34,6 +34,7 @@
 #include "kernels_misc.h"
 #include "kernels_small.h"
 #include "kernels_tail.h"
+#include "kernels_window.h"
 
 static thread_local char g_err[1024] = "";
 static void set_err(const char* fmt, ...) {

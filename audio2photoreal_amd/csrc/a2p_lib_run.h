@@ -1265,6 +1265,71 @@ extern "C" int a2p_sample_step(a2p_ctx* c, int32_t sampler, const float* x, cons
   return launch_step_tail(c, sp, s);
 }
 
+// Window starts on the host: ascending, the first at 0, the last ending at T_total, no gaps (every frame covered).
+static int check_windows(const int32_t* starts, int32_t W, int32_t Tw, int32_t Ttot) {
+  ARG(starts, "null window starts");
+  ARG(W >= 1 && W <= A2P_WINDOW_MAX, "%d windows: 1 .. %d", W, A2P_WINDOW_MAX);
+  ARG(Tw >= 1 && Ttot >= Tw, "window of %d frames over %d frames", Tw, Ttot);
+  ARG(starts[0] == 0, "the first window starts at %d, not 0", starts[0]);
+  for (int w = 1; w < W; ++w)
+    ARG(starts[w] > starts[w - 1] && starts[w] <= starts[w - 1] + Tw, "window %d starts at %d after %d: not ascending or leaves a gap", w,
+        starts[w], starts[w - 1]);
+  ARG(starts[W - 1] + Tw == Ttot, "the last window ends at %d, not at T_total = %d", starts[W - 1] + Tw, Ttot);
+  return 0;
+}
+
+extern "C" int a2p_sample_step_windowed(a2p_ctx* c, int32_t sampler, const float* x_win, const int64_t* t_idx,
+                                        const int64_t* timestep_map, const float* tables, int32_t n_steps, const float* scale,
+                                        const float* noise_global, float eta, int32_t clip_denoised, const int32_t* win_starts_host,
+                                        const float* win_weights, int32_t W, int32_t T_total, float* x_next_win, float* x0_win,
+                                        float* x_global, float* x0_global, void* stream) {
+  ARG(c && x_win && t_idx && timestep_map && tables && x_next_win && x0_win, "null argument");
+  ARG(sampler == A2P_SAMPLER_DDIM || sampler == A2P_SAMPLER_DDPM, "bad sampler");
+  ARG(sampler == A2P_SAMPLER_DDIM || noise_global, "DDPM step needs noise");
+  ARG(scale, "classifier-free guidance scale required");
+  ARG(win_weights, "null window weights");
+  ARG(c->pB > 0 && W >= 1 && c->pB % W == 0, "prepared batch %d is not repetitions x %d windows", c->pB, W);
+  CHK(check_windows(win_starts_host, W, c->pT, T_total));
+  hipStream_t s = (hipStream_t)stream;
+  int64_t* t_orig = reinterpret_cast<int64_t*>(c->tmpa.p);
+  map_timesteps_kernel<<<1, 256, 0, s>>>(t_idx, timestep_map, t_orig, c->pB);
+  int rows = 0;
+  CHK(run_forward(c, x_win, t_orig, A2P_PASS_CFG, &rows, s));
+  WinStepP wp;
+  memset(&wp, 0, sizeof(wp));
+  wp.mo = c->mo.f(); wp.mo_seq_rows = rows; wp.R = c->pB / W; wp.W = W; wp.C = c->C; wp.Tw = c->pT; wp.Ttot = T_total;
+  wp.scale = scale; wp.weights = win_weights; wp.sampler = sampler; wp.x = x_win; wp.t_idx = t_idx; wp.tables = tables;
+  wp.n_steps = n_steps; wp.noise = noise_global; wp.eta = eta; wp.clip = clip_denoised; wp.x_next = x_next_win; wp.x0 = x0_win;
+  wp.x_glob = x_global; wp.x0_glob = x0_global; wp.nonfinite = reinterpret_cast<int*>(c->nonfinite.p);
+  memcpy(wp.starts, win_starts_host, sizeof(int32_t) * W);
+  dim3 grid((T_total + 31) / 32, (c->C + 31) / 32, wp.R);
+  windowed_step_tail_kernel<<<grid, 256, 0, s>>>(wp);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int a2p_window_gather(const float* src, int32_t reps, int32_t T_total, int32_t k, int32_t ch, int32_t channels_first,
+                                 const int32_t* win_starts_host, int32_t W, int32_t T_w, float* dst, void* stream) {
+  ARG(src && dst, "null argument");
+  ARG(reps >= 1 && k >= 1 && ch >= 1, "bad geometry: reps %d, k %d, ch %d", reps, k, ch);
+  ARG(!channels_first || k == 1, "channels-first gather takes k = 1 (got %d)", k);
+  CHK(check_windows(win_starts_host, W, T_w, T_total));
+  WinGatherP gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.src = src; gp.dst = dst; gp.R = reps; gp.W = W;
+  gp.rows = channels_first ? ch : 1;
+  const int64_t per_frame = channels_first ? 1 : (int64_t)k * ch;
+  gp.src_len = (int64_t)T_total * per_frame; gp.dst_len = (int64_t)T_w * per_frame; gp.unit = per_frame;
+  memcpy(gp.starts, win_starts_host, sizeof(int32_t) * W);
+  const int64_t seqs = (int64_t)reps * W * gp.rows;
+  ARG(seqs <= 65535, "%lld window rows: at most 65535", (long long)seqs);
+  const int64_t blocks = (gp.dst_len + 255) / 256;
+  dim3 grid((unsigned)(blocks < 1024 ? blocks : 1024), (unsigned)seqs);
+  window_gather_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(gp);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int a2p_attention_logit_max(a2p_ctx* c, float* max_logit_host, void* stream) {
   ARG(c && max_logit_host, "null argument");
   hipStream_t s = (hipStream_t)stream;

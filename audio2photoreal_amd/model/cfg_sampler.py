@@ -58,3 +58,8 @@ class ClassifierFreeSampleModel(nn.Module):
     def a2p_sample_step(self, sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised):
         """p_mean_variance + ddim_sample / p_sample in one library call; SpacedDiffusion's loops use it when present."""
         return self.model.sample_step(sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised)
+
+    def a2p_sample_step_windowed(self, sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised, starts, weights, T_total):
+        """The windowed form of a2p_sample_step (sample/long_form.py windowed_sample_loop)."""
+        return self.model.sample_step_windowed(sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised, starts, weights,
+                                               T_total)

@@ -466,3 +466,30 @@ class FiLMTransformer(nn.Module):
                                                    int(bool(clip_denoised)), _lib.ptr(x_next), _lib.ptr(x0),
                                                    _lib.current_stream(x.device)), "a2p_sample_step")
         return x_next, x0
+
+    def sample_step_windowed(self, sampler: int, x, t_idx, timestep_map, tables, y, noise, eta: float, clip_denoised: bool, starts,
+                             weights, T_total: int):
+        """One step of windowed joint sampling (include/a2p_hip.h a2p_sample_step_windowed): x [R*W, C, 1, T_w] windows,
+        `starts` a ctypes int32 array of the W window starts, `weights` fp32 [W, T_w], `noise` global [R, C, 1, T_total] or None.
+        Returns (x_next, pred_xstart) of the windows and (x_next, pred_xstart) global [R, C, 1, T_total]."""
+        x = x.to(torch.float32).contiguous()
+        self.prepare(x, y)
+        W = len(starts)
+        B, Cf, T_w = x.shape[0], x.shape[1], x.shape[-1]
+        R = B // W
+        x_next, x0 = torch.empty_like(x), torch.empty_like(x)
+        xg = torch.empty(R, Cf, 1, int(T_total), device=x.device, dtype=torch.float32)
+        x0g = torch.empty_like(xg)
+        sc = y["scale"].to(device=x.device, dtype=torch.float32).contiguous()
+        nz = None if noise is None else noise.to(device=x.device, dtype=torch.float32).contiguous()
+        if (B % W or sc.numel() != B or weights.dtype != torch.float32 or weights.numel() != W * T_w or not weights.is_contiguous()
+                or (nz is not None and nz.numel() != xg.numel())):
+            raise _lib.A2PError(f"windowed step: x {tuple(x.shape)} over {W} windows needs scale [{B}], fp32 weights [{W}, {T_w}] and "
+                                f"noise [{R}, {Cf}, 1, {T_total}] (got {tuple(sc.shape)}, {tuple(weights.shape)}, "
+                                f"{None if nz is None else tuple(nz.shape)})")
+        with _lib.on_device_of(x):
+            _lib.check(self._lib().a2p_sample_step_windowed(
+                self._ctx, sampler, _lib.ptr(x), _lib.ptr(t_idx), _lib.ptr(timestep_map), _lib.ptr(tables), tables.shape[1], _lib.ptr(sc),
+                _lib.ptr(nz), float(eta), int(bool(clip_denoised)), starts, _lib.ptr(weights), W, int(T_total), _lib.ptr(x_next),
+                _lib.ptr(x0), _lib.ptr(xg), _lib.ptr(x0g), _lib.current_stream(x.device)), "a2p_sample_step_windowed")
+        return x_next, x0, xg, x0g

@@ -56,7 +56,7 @@ def prepare_recording(waveform, sr: int, stats: Dict[str, np.ndarray], num_repet
 
     `waveform`: [L], or 2-D averaged over `dim = 0 if shape[0] == 2 else 1` (numpy or torch, any numeric dtype, e.g. `read_wav`'s
     output).  Raises A2PError, before any GPU work, for recordings shorter than 4 s or longer than `max_frames` frames after
-    resampling (long-form generation is out of scope) and for num_repetitions < 1; ValueError for sr <= 0."""
+    resampling (longer recordings: sample.long_form.prepare_long_recording) and for num_repetitions < 1; ValueError for sr <= 0."""
     if sr <= 0 or int(sr) != sr:
         raise ValueError(f"sr must be a positive integer rate (got {sr})")
     sr = int(sr)

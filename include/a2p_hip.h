@@ -132,6 +132,26 @@ int a2p_sample_step(a2p_ctx* ctx, int32_t sampler, const float* x, const int64_t
                     const float* scale, const float* noise, float eta, int32_t clip_denoised,
                     float* x_next, float* pred_xstart, void* stream);
 
+/* ---- windowed joint sampling of recordings longer than one window (sample/long_form.py) -----
+ * W windows of T_w = the prepared frames start at win_starts_host[W] (HOST int32: ascending, the first at 0, the last ending at
+ * T_total, no gaps; W <= A2P_WINDOW_MAX).  The prepared batch is R * W sequences, b = r * W + w: x_win, x_next_win, x0_win are
+ * [R*W, nfeats, 1, T_w], t_idx [R*W], scale [R*W].  One step: the a2p_sample_step forward, then for every global frame the
+ * guided x0 predictions of the covering windows are blended with win_weights fp32 [W, T_w] in ascending w, clamped when
+ * clip_denoised, and the DDIM / DDPM update is computed once from the blend (x from the first covering window, noise_global
+ * [R, nfeats, 1, T_total] or NULL for DDIM with eta == 0).  The same bits are written to every window copy of the frame and,
+ * when non-NULL, to x_global / x0_global [R, nfeats, 1, T_total].  x_next_win may alias x_win. */
+#define A2P_WINDOW_MAX 256
+int a2p_sample_step_windowed(a2p_ctx* ctx, int32_t sampler, const float* x_win, const int64_t* t_idx,
+                             const int64_t* timestep_map, const float* tables, int32_t n_steps, const float* scale,
+                             const float* noise_global, float eta, int32_t clip_denoised, const int32_t* win_starts_host,
+                             const float* win_weights, int32_t W, int32_t T_total, float* x_next_win, float* x0_win,
+                             float* x_global, float* x0_global, void* stream);
+/* Windows of a per-frame signal: channels last, src [reps, T_total * k, ch] -> dst [reps * W, T_w * k, ch] (k samples of ch
+ * channels per frame, e.g. the dual audio: k = 1600, ch = 2); channels_first (k = 1), src [reps, ch, T_total] -> dst
+ * [reps * W, ch, T_w].  dst[r * W + w] is the slice of src[r] from frame win_starts_host[w] (same rules as above). */
+int a2p_window_gather(const float* src, int32_t reps, int32_t T_total, int32_t k, int32_t ch, int32_t channels_first,
+                      const int32_t* win_starts_host, int32_t W, int32_t T_w, float* dst, void* stream);
+
 /* ---- stand-alone sampler arithmetic (any model callable on the host side) ------
  * model_out [B, T, C] -> pred_xstart/mean [B, C, 1, T]: GaussianDiffusion.p_mean_variance
  * (gaussian_diffusion.py:305-316) + q_posterior_mean_variance (:235-257). */
