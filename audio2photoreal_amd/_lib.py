@@ -39,7 +39,7 @@ EXPORTS = (
     "a2p_guide_forward", "a2p_guide_generate", "a2p_guide_debug_read", "a2p_vq_decode",
     "a2p_frontend_create", "a2p_frontend_destroy", "a2p_frontend_set_weight", "a2p_frontend_finalize",
     "a2p_frontend_encode_audio", "a2p_frontend_encode_lip", "a2p_resample", "a2p_dual_audio",
-    "a2p_sample_step_windowed", "a2p_window_gather",
+    "a2p_sample_step_windowed", "a2p_window_gather", "a2p_sample_step_inpaint",
 )
 
 
@@ -148,6 +148,7 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_dual_audio": [vp, i64, vp, vp, C.c_double, C.c_double, C.c_double, i32, vp, vp],
         "a2p_sample_step_windowed": [vp, i32, vp, vp, vp, vp, i32, vp, vp, f32, i32, C.POINTER(i32), vp, i32, i32, vp, vp, vp, vp, vp],
         "a2p_window_gather": [vp, i32, i32, i32, i32, i32, C.POINTER(i32), i32, i32, vp, vp],
+        "a2p_sample_step_inpaint": [vp, i32, vp, vp, vp, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

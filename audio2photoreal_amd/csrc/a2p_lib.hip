@@ -31,6 +31,7 @@
 #include "kernels_chain.h"
 #include "kernels_chain4.h"
 #include "kernels_gemm.h"
+#include "kernels_inpaint.h"
 #include "kernels_misc.h"
 #include "kernels_small.h"
 #include "kernels_tail.h"

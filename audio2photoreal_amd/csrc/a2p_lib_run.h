@@ -1265,6 +1265,32 @@ extern "C" int a2p_sample_step(a2p_ctx* c, int32_t sampler, const float* x, cons
   return launch_step_tail(c, sp, s);
 }
 
+extern "C" int a2p_sample_step_inpaint(a2p_ctx* c, int32_t sampler, const float* x, const int64_t* t_idx,
+                                       const int64_t* timestep_map, const float* tables, int32_t n_steps, const float* scale,
+                                       const float* noise, float eta, int32_t clip_denoised, const float* known,
+                                       const uint8_t* known_mask, float* x_next, float* pred_xstart, void* stream) {
+  ARG(c && x && t_idx && timestep_map && tables && x_next, "null argument");
+  ARG(known && known_mask, "inpainting needs known values and a mask");
+  ARG(sampler == A2P_SAMPLER_DDIM || sampler == A2P_SAMPLER_DDPM, "bad sampler");
+  ARG(sampler == A2P_SAMPLER_DDIM || noise, "DDPM step needs noise");
+  ARG(scale, "classifier-free guidance scale required");
+  hipStream_t s = (hipStream_t)stream;
+  int64_t* t_orig = reinterpret_cast<int64_t*>(c->tmpa.p);
+  map_timesteps_kernel<<<1, 256, 0, s>>>(t_idx, timestep_map, t_orig, c->pB);
+  int rows = 0;
+  CHK(run_forward(c, x, t_orig, A2P_PASS_CFG, &rows, s));
+  InpaintStepP ip;
+  memset(&ip, 0, sizeof(ip));
+  ip.mo = c->mo.f(); ip.mo_seq_rows = rows; ip.B = c->pB; ip.C = c->C; ip.Tn = c->pT;
+  ip.scale = scale; ip.sampler = sampler; ip.x = x; ip.t_idx = t_idx; ip.tables = tables; ip.n_steps = n_steps; ip.noise = noise;
+  ip.eta = eta; ip.clip = clip_denoised; ip.known = known; ip.mask = known_mask; ip.x_next = x_next; ip.x0 = pred_xstart;
+  ip.nonfinite = reinterpret_cast<int*>(c->nonfinite.p);
+  dim3 grid((ip.Tn + 31) / 32, (ip.C + 31) / 32, ip.B);
+  inpaint_step_tail_kernel<<<grid, 256, 0, s>>>(ip);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // Window starts on the host: ascending, the first at 0, the last ending at T_total, no gaps (every frame covered).
 static int check_windows(const int32_t* starts, int32_t W, int32_t Tw, int32_t Ttot) {
   ARG(starts, "null window starts");

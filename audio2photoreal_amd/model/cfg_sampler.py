@@ -63,3 +63,7 @@ class ClassifierFreeSampleModel(nn.Module):
         """The windowed form of a2p_sample_step (sample/long_form.py windowed_sample_loop)."""
         return self.model.sample_step_windowed(sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised, starts, weights,
                                                T_total)
+
+    def a2p_sample_step_inpaint(self, sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised, known, known_mask):
+        """a2p_sample_step with held elements (sample/inpaint.py inpaint_sample_loop)."""
+        return self.model.sample_step_inpaint(sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised, known, known_mask)

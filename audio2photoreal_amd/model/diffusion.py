@@ -493,3 +493,27 @@ class FiLMTransformer(nn.Module):
                 _lib.ptr(nz), float(eta), int(bool(clip_denoised)), starts, _lib.ptr(weights), W, int(T_total), _lib.ptr(x_next),
                 _lib.ptr(x0), _lib.ptr(xg), _lib.ptr(x0g), _lib.current_stream(x.device)), "a2p_sample_step_windowed")
         return x_next, x0, xg, x0g
+
+    def sample_step_inpaint(self, sampler: int, x, t_idx, timestep_map, tables, y, noise, eta: float, clip_denoised: bool, known,
+                            known_mask):
+        """One step with held elements (include/a2p_hip.h a2p_sample_step_inpaint): a2p_sample_step whose x0 prediction takes
+        `known` where `known_mask` is set.  `known` fp32 and `known_mask` uint8 are contiguous [B, C, 1, T] on x's device.
+        Returns (x_next, pred_xstart)."""
+        x = x.to(torch.float32).contiguous()
+        if (known.dtype != torch.float32 or known_mask.dtype != torch.uint8 or known.shape != x.shape or known_mask.shape != x.shape
+                or not known.is_contiguous() or not known_mask.is_contiguous() or known.device != x.device
+                or known_mask.device != x.device):
+            raise _lib.A2PError(f"inpaint step: x {tuple(x.shape)} needs contiguous known fp32 and known_mask uint8 of that shape on "
+                                f"{x.device} (got {known.dtype} {tuple(known.shape)} on {known.device}, {known_mask.dtype} "
+                                f"{tuple(known_mask.shape)} on {known_mask.device})")
+        self.prepare(x, y)
+        x_next, x0 = torch.empty_like(x), torch.empty_like(x)
+        sc = y["scale"].to(device=x.device, dtype=torch.float32).contiguous()
+        nz = None if noise is None else noise.to(device=x.device, dtype=torch.float32).contiguous()
+        with _lib.on_device_of(x):
+            _lib.check(self._lib().a2p_sample_step_inpaint(self._ctx, sampler, _lib.ptr(x), _lib.ptr(t_idx), _lib.ptr(timestep_map),
+                                                           _lib.ptr(tables), tables.shape[1], _lib.ptr(sc), _lib.ptr(nz), float(eta),
+                                                           int(bool(clip_denoised)), _lib.ptr(known), _lib.ptr(known_mask),
+                                                           _lib.ptr(x_next), _lib.ptr(x0), _lib.current_stream(x.device)),
+                       "a2p_sample_step_inpaint")
+        return x_next, x0

@@ -235,3 +235,11 @@ def _overlapped(face, pose, run_face, run_body, device):
     if redo_body:
         body_s = run_body()
     return face_s, body_s
+
+
+def __getattr__(name):
+    """continue_recording and regenerate_segment (sample/inpaint.py) are importable from here, next to generate_from_recording."""
+    if name in ("continue_recording", "regenerate_segment"):
+        from . import inpaint
+        return getattr(inpaint, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

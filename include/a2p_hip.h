@@ -132,6 +132,17 @@ int a2p_sample_step(a2p_ctx* ctx, int32_t sampler, const float* x, const int64_t
                     const float* scale, const float* noise, float eta, int32_t clip_denoised,
                     float* x_next, float* pred_xstart, void* stream);
 
+/* ---- sampling with held elements: inpainting and clip continuation (sample/inpaint.py) -----
+ * a2p_sample_step with MDM's x0 replacement.  known fp32 and known_mask uint8 are [B, nfeats, 1, T] in x's layout (x's
+ * normalised space); both are required.  Per element: the guided output g = u + scale[b] * (a - u) (non-finite g ORs the
+ * a2p_check_finite flag, held or not), x0 = g clamped to [-1, 1] when clip_denoised, x0 = known where known_mask != 0 (not
+ * clamped; a non-finite held value ORs the flag too), pred_xstart = x0, then the DDIM / DDPM update of a2p_sample_step with the
+ * same noise layout.  An all-zero mask gives a2p_sample_step's bits.  x_next may alias x. */
+int a2p_sample_step_inpaint(a2p_ctx* ctx, int32_t sampler, const float* x, const int64_t* t_idx,
+                            const int64_t* timestep_map, const float* tables, int32_t n_steps,
+                            const float* scale, const float* noise, float eta, int32_t clip_denoised,
+                            const float* known, const uint8_t* known_mask, float* x_next, float* pred_xstart, void* stream);
+
 /* ---- windowed joint sampling of recordings longer than one window (sample/long_form.py) -----
  * W windows of T_w = the prepared frames start at win_starts_host[W] (HOST int32: ascending, the first at 0, the last ending at
  * T_total, no gaps; W <= A2P_WINDOW_MAX).  The prepared batch is R * W sequences, b = r * W + w: x_win, x_next_win, x0_win are
