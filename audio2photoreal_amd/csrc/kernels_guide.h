@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void guide_ar_kernel(const GuideArP p) {
         ++n;
       }
       const float u = p.uniforms[(int64_t)pos * gridDim.x + b];
-      int pick = 0;
+      int pick = n - 1;  // the fp32 running sum can end a few ulps below 1: a u above it draws the last nucleus entry, not the head
       float c2 = 0.f;
       for (int i = 0; i < n; ++i) {
         c2 += lg[i] / kept;

@@ -13,7 +13,8 @@ ONE persistent kernel launch (`a2p_guide_generate`).
 `condition` is the audio FEATURE tensor [B, S, 1024] that `encode_audio` (model/guide.py:111-119) returns -- the vq-wav2vec
 front end is outside this path -- or raw audio when an `audio_frontend` callable is given.
 The categorical draw takes `uniforms` [sequence_length * layers, B] (default: torch.rand on the device) instead of torch's
-global multinomial stream: token = first sorted index whose cumulative nucleus probability exceeds u.
+global multinomial stream: token = first sorted index whose cumulative nucleus probability exceeds u (the last nucleus entry when
+none does: an fp32 cumulative sum can end a few ulps below 1).
 """
 from __future__ import annotations
 

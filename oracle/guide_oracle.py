@@ -76,9 +76,10 @@ class OracleGuide:
         x = F.conv1d(x, self.sd[f"pre_audio.{n}.weight"], self.sd[f"pre_audio.{n}.bias"])
         return x.permute(0, 2, 1)
 
-    def condition(self, cond_embed: Tensor, cond_drop_prob: float = 0.0):
+    def condition(self, cond_embed: Tensor, cond_drop_prob: float = 0.0, features: Optional[Tensor] = None):
+        """(norm_cond memory [B, S', d], pooled hidden [B, d]); `features`: pre_audio(cond_embed) when already computed."""
         sd = self.sd
-        ct = self.pre_audio(cond_embed) @ sd["cond_projection.weight"].T + sd["cond_projection.bias"]
+        ct = (self.pre_audio(cond_embed) if features is None else features) @ sd["cond_projection.weight"].T + sd["cond_projection.bias"]
         if cond_drop_prob == 1.0:
             ct = sd["null_cond_embed"][:, : ct.shape[1]].expand(ct.shape[0], -1, -1)
         h = layer_norm(ct.mean(dim=-2), sd["non_attn_cond_projection.0.weight"], sd["non_attn_cond_projection.0.bias"])
@@ -104,16 +105,24 @@ class OracleGuide:
         sorted_probs = sorted_probs.masked_fill(~nucleus, 0.0)
         return sorted_probs / sorted_probs.sum(-1, keepdim=True), indices
 
+    @staticmethod
+    def draw(sorted_probs: Tensor, indices: Tensor, u: Tensor) -> Tensor:
+        """Inverse-CDF form of Categorical(sorted_probs).sample() for uniforms u [...]: the first sorted entry whose cumulative
+        probability exceeds u.  When none does (the cumulative sum can end a few ulps below 1 and u can be 1 - 2^-24), the
+        last nucleus entry -- never the head."""
+        above = torch.cumsum(sorted_probs, dim=-1) > u[..., None]
+        last = (sorted_probs > 0).sum(-1) - 1
+        pick = torch.where(above.any(-1), above.float().argmax(dim=-1), last)
+        return indices.gather(-1, pick[..., None])[..., 0]
+
     def generate(self, cond_embed: Tensor, sequence_length: int, layers: int, uniforms: Tensor, top_p: float = 0.94) -> Tensor:
-        """uniforms [sequence_length * layers, B] in [0, 1): token = first sorted index whose cumulative probability exceeds u
-        (the inverse-CDF form of Categorical(sorted_probs).sample())."""
+        """uniforms [sequence_length * layers, B] in [0, 1): token = `draw` of the nucleus at u."""
         B = cond_embed.shape[0]
         cond = self.condition(cond_embed)
         toks = torch.full((B, 1), self.tokens, dtype=torch.int64)
         for i in range(sequence_length * layers):
             probs, idx = self.nucleus_probs(self.forward(toks, cond_embed, cond=cond)[:, -1, :], top_p)
-            pick = (torch.cumsum(probs, dim=-1) > uniforms[i][:, None]).float().argmax(dim=-1)
-            toks = torch.cat([toks, idx.gather(-1, pick[:, None])], dim=-1)
+            toks = torch.cat([toks, self.draw(probs, idx, uniforms[i])[:, None]], dim=-1)
         return toks[:, 1:].contiguous()
 
 

@@ -60,3 +60,17 @@ def test_residual_vq_decode(gg):
     ts = TokenizerSpec()
     out = G.vq_decode(synthetic_tokenizer_state_dict(ts, SEED), torch.from_numpy(gg["vq/tokens"]), ts.residual_depth)
     assert out.shape == (2, 20, ts.n_vertices) and rel_l2(out, gg["vq/decoded"]) < TOL
+
+
+def test_draw_falls_back_to_the_last_nucleus_entry():
+    """The cumulative sum of a nucleus can end below the largest uniform torch.rand returns (1 - 2^-24); the draw then takes
+    the last nucleus entry (the tail of the inverse CDF), not the head."""
+    u_max = float(np.nextafter(np.float32(1), np.float32(0)))
+    probs = torch.tensor([[0.5, 0.25, 0.125, 0.125 - 2.0 ** -23, 0.0, 0.0],     # sums to 1 - 2^-23 exactly
+                          [1.0, 0.0, 0.0, 0.0, 0.0, 0.0]], dtype=torch.float32)
+    idx = torch.tensor([[4, 2, 0, 5, 1, 3], [3, 0, 1, 2, 4, 5]])
+    assert float(torch.cumsum(probs, -1)[0, -1]) < u_max
+    assert G.OracleGuide.draw(probs, idx, torch.tensor([u_max, u_max])).tolist() == [5, 3]
+    assert G.OracleGuide.draw(probs, idx, torch.tensor([0.0, 0.0])).tolist() == [4, 3]
+    assert G.OracleGuide.draw(probs, idx, torch.tensor([0.5, 0.999])).tolist() == [2, 3]
+    assert G.OracleGuide.draw(probs.double(), idx, torch.tensor([0.875, 0.5])).tolist() == [5, 3]
