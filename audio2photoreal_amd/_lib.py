@@ -39,7 +39,7 @@ EXPORTS = (
     "a2p_guide_forward", "a2p_guide_generate", "a2p_guide_debug_read", "a2p_vq_decode",
     "a2p_frontend_create", "a2p_frontend_destroy", "a2p_frontend_set_weight", "a2p_frontend_finalize",
     "a2p_frontend_encode_audio", "a2p_frontend_encode_lip", "a2p_resample", "a2p_dual_audio",
-    "a2p_sample_step_windowed", "a2p_window_gather", "a2p_sample_step_inpaint",
+    "a2p_sample_step_windowed", "a2p_window_gather", "a2p_sample_step_inpaint", "a2p_guide_generate_forced", "a2p_vq_encode",
 )
 
 
@@ -138,6 +138,8 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_guide_generate": [vp, i32, i32, f32, vp, vp, vp, vp],
         "a2p_guide_debug_read": [vp, C.c_char_p, vp, i64],
         "a2p_vq_decode": [vp, i32, i32, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp],
+        "a2p_guide_generate_forced": [vp, i32, i32, f32, vp, vp, vp, vp, vp],
+        "a2p_vq_encode": [vp, i32, i32, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp],
         "a2p_frontend_create": [C.POINTER(A2PFrontendConfig), C.POINTER(vp)],
         "a2p_frontend_destroy": [vp],
         "a2p_frontend_set_weight": [vp, C.c_char_p, vp, i64, vp],

@@ -284,6 +284,17 @@ extern "C" int a2p_guide_generate(a2p_guide_ctx* g, int32_t batch, int32_t n_ste
   return guide_run(g, p, batch, (hipStream_t)stream);
 }
 
+// a2p_guide_generate with forced positions (nullable forced: a2p_guide_generate's launch)
+extern "C" int a2p_guide_generate_forced(a2p_guide_ctx* g, int32_t batch, int32_t n_steps, float top_p, const float* uniforms,
+                                         const int64_t* forced, int64_t* tokens_out, float* sorted_probs_out, void* stream) {
+  ARG(g && uniforms && tokens_out, "null argument");
+  GuideArP p;
+  memset(&p, 0, sizeof(p));
+  p.mode = 1; p.n_pos = n_steps; p.top_p = top_p; p.uniforms = uniforms; p.tokens_out = tokens_out; p.probs_out = sorted_probs_out;
+  p.forced = forced;
+  return guide_run(g, p, batch, (hipStream_t)stream);
+}
+
 extern "C" int a2p_guide_debug_read(a2p_guide_ctx* g, const char* name, void* host, int64_t bytes) {
   ARG(g && name && host, "null argument");
   const std::string n(name);
@@ -310,6 +321,32 @@ extern "C" int a2p_vq_decode(const int64_t* q, int32_t batch, int32_t T, int32_t
   const size_t lds = (size_t)2 * (T + 7) * latent * 4;
   ARG(lds <= 64 * 1024, "VQ decode of %d frames x %d latent needs %zu bytes of LDS", T, latent, lds);
   vq_decode_kernel<<<batch, 256, lds, (hipStream_t)stream>>>(p);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// TemporalVertexCodec.encode (model/vqvae.py:499-506); all pointers are device pointers, the arrays of pointers live on the host
+extern "C" int a2p_vq_encode(const float* poses, int32_t batch, int32_t T, int32_t depth, int32_t categories, int32_t latent, int32_t vertices,
+                             const float* const* codebooks, const float* const* code_norms, const float* const* conv_w,
+                             const float* const* conv_b, int64_t* tokens_out, float* latents_out, void* stream) {
+  ARG(poses && codebooks && code_norms && conv_w && conv_b && (tokens_out || latents_out), "null argument");
+  ARG(depth >= 1 && depth <= 8 && batch >= 1 && T >= 1 && latent >= 4 && latent % 4 == 0 && vertices >= 1 && categories >= 1,
+      "bad VQ shape (the latent width must be a multiple of 4)");
+  VqEncodeP p;
+  memset(&p, 0, sizeof(p));
+  p.poses = poses; p.T = T; p.depth = depth; p.categories = categories; p.e = latent; p.nv = vertices;
+  p.tokens = tokens_out; p.latents = latents_out;
+  for (int i = 0; i < depth; ++i) {
+    p.codebook[i] = codebooks[i]; p.norms[i] = code_norms[i];
+    ARG(p.codebook[i] && p.norms[i], "null codebook %d", i);
+  }
+  for (int i = 0; i < 5; ++i) {
+    p.cw[i] = conv_w[i]; p.cb[i] = conv_b[i];
+    ARG(p.cw[i] && p.cb[i], "null encoder conv %d", i);
+  }
+  const size_t lds = (size_t)2 * (T + 7) * latent * 4;
+  ARG(lds <= 64 * 1024, "VQ encode of %d frames x %d latent needs %zu bytes of LDS", T, latent, lds);
+  vq_encode_kernel<<<batch, 256, lds, (hipStream_t)stream>>>(p);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -35,6 +35,7 @@
 #include "kernels_misc.h"
 #include "kernels_small.h"
 #include "kernels_tail.h"
+#include "kernels_vq.h"
 #include "kernels_window.h"
 
 static thread_local char g_err[1024] = "";

@@ -7,7 +7,8 @@
 // and the token loop is ONE persistent launch: `guide_ar_kernel`, one workgroup per sequence, walks the positions with a
 // self-attention K/V cache, runs the 6-layer d=64 stack out of registers/LDS (GEMV-sized work: VALU, no MFMA), and -- in
 // sampling mode -- does the softmax, the descending bitonic sort, the nucleus cut (model/guide.py:201-214) and the
-// categorical draw (inverse CDF over an injected uniform) in the same kernel.  All arithmetic fp32.
+// categorical draw (inverse CDF over an injected uniform) in the same kernel.  Positions whose token is given (`forced`: known
+// keyframes encoded by kernels_vq.h) run the decoder stack and skip the rest.  All arithmetic fp32.
 #pragma once
 #include "a2p_common.h"
 
@@ -39,6 +40,7 @@ struct GuideArP {
   const float* uniforms;        // [n_pos][B]
   int64_t* tokens_out;          // [B][n_pos]
   float* probs_out;             // optional [n_pos][B][V]: the renormalised sorted nucleus probabilities
+  const int64_t* forced;        // optional [B][n_pos] (sampling): -1 draws, a value in [0, V) is that position's token
 };
 
 __device__ __forceinline__ float wave_max_f(float v) {
@@ -253,6 +255,19 @@ __global__ __launch_bounds__(256) void guide_ar_kernel(const GuideArP p) {
       guide_gemv_splitk(w.w2, w.b2, hid, tmp, part, d, ff);
       __syncthreads();
       film_residual(fl + 4 * d);
+    }
+    if (p.forced) {  // a forced position: the stack above has written its K/V cache rows; no logits, no draw
+      const int64_t f = p.forced[(int64_t)b * p.n_pos + pos];
+      if (f != -1) {
+        const bool ok = f >= 0 && f < V;  // uniform over the workgroup: every thread takes the same branch
+        if (tid == 0) p.tokens_out[(int64_t)b * p.n_pos + pos] = ok ? f : -2;
+        if (!ok) return;                  // an id outside [0, V) never reaches the embedding lookup
+        if (p.probs_out)
+          for (int v = tid; v < V; v += 256) p.probs_out[((int64_t)pos * gridDim.x + b) * V + v] = 0.f;
+        token = (int)f;
+        __syncthreads();
+        continue;
+      }
     }
     guide_gemv<ACT_NONE>(p.fin_w, p.fin_b, x, lg, V, d);
     __syncthreads();

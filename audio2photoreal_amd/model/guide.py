@@ -8,7 +8,7 @@ Nothing is computed in PyTorch: the sub-modules are parameter containers; `liba2
 depend on the tokens (the 13-layer 1024-channel `pre_audio` conv stack the reference re-runs in each of the 80 steps, the
 conditioning projections, all FiLM vectors, the cross-attention K/V of every layer) into `a2p_guide_prepare`, and runs the
 whole autoregressive loop -- decoder stack with a self-attention K/V cache, softmax, sort, nucleus cut, categorical draw -- as
-ONE persistent kernel launch (`a2p_guide_generate`).
+ONE persistent kernel launch (`a2p_guide_generate`; `a2p_guide_generate_forced` when some positions' tokens are given).
 
 `condition` is the audio FEATURE tensor [B, S, 1024] that `encode_audio` (model/guide.py:111-119) returns -- the vq-wav2vec
 front end is outside this path -- or raw audio when an `audio_frontend` callable is given.
@@ -27,6 +27,14 @@ from torch.nn import functional as F
 
 from .. import _lib
 from .diffusion import DecoderLayerStack, RotaryEmbedding, _DecoderLayerParams
+
+
+def check_forced_result(tokens: torch.Tensor) -> None:
+    """Raise when a2p_guide_generate_forced stopped a sequence at a forced id outside [0, V) (it writes -2 there)."""
+    bad = (tokens == -2).nonzero()
+    if bad.numel():
+        b, i = (int(v) for v in bad[0])
+        raise _lib.A2PError(f"a2p_guide_generate_forced: sequence {b} stopped at position {i}: its forced token is outside the vocabulary")
 
 
 class GuideTransformer(nn.Module):
@@ -142,13 +150,30 @@ class GuideTransformer(nn.Module):
 
     def generate(self, condition: torch.Tensor, sequence_length: int, layers: int, n_sequences: int = 1, max_key_len: int = 8,
                  max_seq_len: int = 240, top_p: float = 0.94, uniforms: Optional[torch.Tensor] = None,
-                 return_probs: bool = False) -> torch.Tensor:
+                 return_probs: bool = False, forced_tokens: Optional[torch.Tensor] = None) -> torch.Tensor:
         """model/guide.py:175-222: `sequence_length * layers` tokens per sequence, nucleus sampling; returns int64
-        [n_sequences, sequence_length * layers] (the start token is not returned)."""
+        [n_sequences, sequence_length * layers] (the start token is not returned).
+
+        `forced_tokens`: int64 [n_sequences, sequence_length * layers], -1 = draw, a value in [0, tokens) = that position's token
+        (a2p_guide_generate_forced).  A forced position is fed to the next one like a drawn token, skips the draw and has a zero
+        `return_probs` row; a free position consumes its uniform whether or not others are forced.  Any other value raises
+        A2PError before any GPU work."""
         assert max_key_len == int(max_seq_len / 30), "currently only running for 1fps"
+        n = sequence_length * layers
+        forced = None
+        if forced_tokens is not None:
+            if not torch.is_tensor(forced_tokens) or forced_tokens.dtype not in (torch.int64, torch.int32):
+                raise _lib.A2PError(f"forced_tokens must be an int64 tensor (got {getattr(forced_tokens, 'dtype', type(forced_tokens).__name__)})")
+            if tuple(forced_tokens.shape) != (n_sequences, n):
+                raise _lib.A2PError(f"forced_tokens must be [{n_sequences}, {n}] (got {tuple(forced_tokens.shape)})")
+            host = forced_tokens.detach().to("cpu", torch.int64)
+            bad = (host != -1) & ((host < 0) | (host >= self.tokens))
+            if bool(bad.any()):
+                i = tuple(int(v) for v in bad.nonzero()[0])
+                raise _lib.A2PError(f"forced_tokens{list(i)} = {int(host[i])}: a forced token lies in [0, {self.tokens}), -1 draws")
+            forced = host
         B = self._prepare(condition, 0.0)
         assert n_sequences == B, "one condition row per sequence"
-        n = sequence_length * layers
         dev = condition.device
         if uniforms is None:
             uniforms = torch.rand(n, B, device=dev)
@@ -157,8 +182,14 @@ class GuideTransformer(nn.Module):
         out = torch.empty(B, n, device=dev, dtype=torch.int64)
         probs = torch.empty(n, B, self.tokens, device=dev, dtype=torch.float32) if return_probs else None
         with torch.no_grad(), _lib.on_device_of(u):
-            _lib.check(_lib.load().a2p_guide_generate(self._ctx, B, n, float(top_p), _lib.ptr(u), _lib.ptr(out), _lib.ptr(probs),
-                                                      _lib.current_stream(dev)), "a2p_guide_generate")
+            if forced is None:
+                _lib.check(_lib.load().a2p_guide_generate(self._ctx, B, n, float(top_p), _lib.ptr(u), _lib.ptr(out), _lib.ptr(probs),
+                                                          _lib.current_stream(dev)), "a2p_guide_generate")
+            else:
+                f = forced.to(dev).contiguous()
+                _lib.check(_lib.load().a2p_guide_generate_forced(self._ctx, B, n, float(top_p), _lib.ptr(u), _lib.ptr(f), _lib.ptr(out),
+                                                                 _lib.ptr(probs), _lib.current_stream(dev)), "a2p_guide_generate_forced")
+                check_forced_result(out)
         return (out, probs) if return_probs else out
 
     def pre_audio_features(self, n_rows: int) -> torch.Tensor:

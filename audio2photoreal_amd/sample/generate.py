@@ -16,6 +16,7 @@ import torch
 
 import itertools
 
+from .. import _lib
 from ..sample_parallel import derive_seed, per_sample_noise, sample_parallel, shared_base_seed
 
 _CALLS = itertools.count()   # sampling calls of this process: every rank makes the same calls in the same order
@@ -87,23 +88,62 @@ def load_results(npy_path: str) -> Dict[str, np.ndarray]:
     return np.load(npy_path, allow_pickle=True).item()
 
 
-def _replace_keyframes(model_kwargs, model, uniforms: Optional[torch.Tensor] = None, top_p: Optional[float] = None) -> torch.Tensor:
+def _replace_keyframes(model_kwargs, model, uniforms: Optional[torch.Tensor] = None, top_p: Optional[float] = None,
+                       known: Optional[torch.Tensor] = None, known_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Keyframes predicted by the guide transformer instead of ground truth (reference sample/generate.py:51-71):
     `model.transformer.generate` -> `[B, T, residual_depth]` tokens -> `model.tokenizer.decode`.  The condition is
     `y["cond_embed"]` (audio features) when present, else `y["audio"]` through the transformer's `audio_frontend`.
     `top_p`: the nucleus of the token sampling (None = `generate`'s default, as reference sample/generate.py:60-65 leaves it;
-    the demo passes 0.97, demo/demo.py:77-83)."""
+    the demo passes 0.97, demo/demo.py:77-83).
+
+    `known` (normalised poses [B, T, nv]) with `known_mask` (bool [B, T]): keyframes whose pose is given.  `model.tokenizer.encode`
+    turns `known` into tokens (its causal encoder reads every row, masked or not: pass the best poses there are, or zeros), all
+    `residual_depth` tokens of each known keyframe are forced in the guide's draw, the others are drawn after them, and the
+    known rows of the result are `known`'s rows verbatim (the free rows are the decode).  The reference trained both routes on
+    real poses: the body on `motion[::30]` (data_loaders/data.py:191), the guide teacher-forced on `tokenizer.predict` of those
+    (train/train_guide.py:64-92)."""
+    if known is None and known_mask is None:
+        return _guide_keyframes(model_kwargs, model, uniforms, top_p)[0]
+    y = model_kwargs["y"]
+    B, T, nv = y["keyframes"].shape
+    known, known_mask = check_known_keyframes(known, known_mask, B, T, nv)
+    tok = model.tokenizer
+    dev = model.transformer.final_layer.weight.device
+    with torch.no_grad():
+        kt = tok.encode(known.to(dev))
+        m = known_mask.to(dev)
+        forced = torch.where(m[:, :, None], kt, torch.full_like(kt, -1)).reshape(B, -1)
+        pred, _ = _guide_keyframes(model_kwargs, model, uniforms, top_p, forced)
+    return torch.where(known_mask.cpu()[:, :, None], known.cpu(), pred)
+
+
+def check_known_keyframes(known, known_mask, B: int, T: int, nv: int):
+    """(known fp32 [B, T, nv], known_mask bool [B, T]) or A2PError; host checks of `_replace_keyframes(known=...)`."""
+    if not torch.is_tensor(known) or not torch.is_tensor(known_mask):
+        raise _lib.A2PError("known and known_mask must both be tensors")
+    if tuple(known.shape) != (B, T, nv) or not known.is_floating_point():
+        raise _lib.A2PError(f"known must be floating point [{B}, {T}, {nv}] (got {known.dtype} {tuple(known.shape)})")
+    if known_mask.dtype != torch.bool or tuple(known_mask.shape) != (B, T):
+        raise _lib.A2PError(f"known_mask must be bool [{B}, {T}] (got {known_mask.dtype} {tuple(known_mask.shape)})")
+    if not bool(torch.isfinite(known).all()):
+        raise _lib.A2PError("known holds non-finite values")
+    return known.to(torch.float32), known_mask
+
+
+def _guide_keyframes(model_kwargs, model, uniforms=None, top_p=None, forced_tokens=None):
+    """(decoded keyframes [B, T, nv] on the host, tokens int64 [B, T, residual_depth] on the device) of one guide launch."""
     y = model_kwargs["y"]
     B, T = y["keyframes"].shape[0], y["keyframes"].shape[1]
     cond = y["cond_embed"] if "cond_embed" in y else y["audio"]
     nucleus = {} if top_p is None else {"top_p": float(top_p)}
+    forced = {} if forced_tokens is None else {"forced_tokens": forced_tokens}
     with torch.no_grad():
         tokens = model.transformer.generate(cond, T, layers=model.tokenizer.residual_depth, n_sequences=B, max_key_len=T,
-                                            max_seq_len=30 * T, uniforms=uniforms, **nucleus)
+                                            max_seq_len=30 * T, uniforms=uniforms, **nucleus, **forced)
     tokens = tokens.reshape((B, -1, model.tokenizer.residual_depth))
     pred = model.tokenizer.decode(tokens).detach().cpu()
     assert y["keyframes"].shape == pred.shape, f"{y['keyframes'].shape} vs {pred.shape}"
-    return pred
+    return pred, tokens
 
 
 def _run_single_diffusion(args, model_kwargs, diffusion, model, inv_transform: Callable, gt: Optional[torch.Tensor],

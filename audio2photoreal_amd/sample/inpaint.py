@@ -95,7 +95,7 @@ def inpaint_sample_loop(diffusion, model, y, known: torch.Tensor, known_mask: to
 
 # ------------------------------------------------------------------------------------------------------------ recording level
 
-def _check_models(face, pose):
+def _check_models(face, pose, need_encoder: bool = False):
     face_m, pose_m = face[0], pose[0]
     fm, pm = _denoiser(face_m), _denoiser(pose_m)
     for name, m in (("face", fm), ("pose", pm)):
@@ -103,7 +103,16 @@ def _check_models(face, pose):
             raise _lib.A2PError(f"the {name} model has no audio front end: construct it with audio_frontend=\"native\"")
     if getattr(pm, "transformer", None) is None or getattr(pm, "tokenizer", None) is None:
         raise _lib.A2PError("the pose model has no guide transformer: attach it with setup_guide_predictor(transformer, tokenizer)")
+    if need_encoder:
+        require_encoder(pm)
     return fm, pm
+
+
+def require_encoder(pm) -> None:
+    """Keyframes from known poses need the encode side of the pose model's tokenizer."""
+    if not getattr(pm.tokenizer, "has_encoder", False):
+        raise _lib.A2PError("keyframes from known poses need the tokenizer's encoder: build TemporalVertexCodec(..., with_encoder=True) "
+                            "and load its encoder.enc.* weights")
 
 
 def _result_arrays(result, name: str):
@@ -156,8 +165,9 @@ def _conditions(face_m, pose_m, fm, pm, audio, share_features: bool):
 
 
 def _inpaint_window(face, pose, audio, R: int, Tw: int, known_face, known_pose, mask, ids, seed: int,
-                    top_p: float, face_scale: float, pose_scale: float, overlap: bool, share_features: bool):
+                    top_p: float, face_scale: float, pose_scale: float, overlap: bool, share_features: bool, known_kf=None):
     """Denoise one window of Tw frames with held elements: face and / or body (a part whose known tensor is None is not run).
+    `known_kf`: None, or (normalised poses [R, Tw / 30, 104], bool mask [R, Tw / 30]) of keyframes the guide is forced to.
     Returns (face [R, C, 1, Tw] or None, body [R, C, 1, Tw] or None, keyframes [R, Tw / 30, 104] normalised, or None)."""
     face_m, face_d = face
     pose_m, pose_d = pose
@@ -180,7 +190,8 @@ def _inpaint_window(face, pose, audio, R: int, Tw: int, known_face, known_pose, 
 
         def run_body():
             guide_y = {**guide_cond, "keyframes": torch.zeros(R, nk, pm.nfeats, device=device)}
-            y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p).to(device)
+            kk = {} if known_kf is None else {"known": known_kf[0], "known_mask": known_kf[1]}
+            y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p, **kk).to(device)
             return inpaint_sample_loop(pose_d, pose_m, y_body, known_pose, mask, noise_pose)
 
         face_s = body_s = None
@@ -200,7 +211,8 @@ def _motion(sample: torch.Tensor, mean, std) -> np.ndarray:
 
 def continue_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: int, previous: Dict[str, object], context_frames: int = 120,
                        num_repetitions: Optional[int] = None, top_p: float = 0.97, face_scale: float = 10.0, pose_scale: float = 2.0,
-                       seed: int = 10, overlap: bool = True, share_features: bool = True) -> Dict[str, object]:
+                       seed: int = 10, overlap: bool = True, share_features: bool = True,
+                       guide_context: bool = False) -> Dict[str, object]:
     """Continue a clip with new audio: face and body motion for `waveform` that starts from where `previous` ended.
 
     `previous`: a result of generate_from_recording or of an earlier continue_recording (its "face", "pose" and "audio" are read).
@@ -211,7 +223,9 @@ def continue_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: i
     inpaint_sample_loop: all face and body channels of its first P frames are held at `previous`'s last P frames, normalised with
     `stats` in float64 and cast to fp32.  Its audio is the last P * 1600 samples of previous["audio"] followed by the new chunk's
     dual audio, z-normalised as prepare_recording does and tiled over the repetitions; the guide transformer predicts the window's
-    keyframes from that audio alone (it is not told about the held frames).  Every random draw is a function of `seed` and the
+    keyframes from that audio alone (it is not told about the held frames).  `guide_context=True` tells it: the window's first
+    P / 30 keyframes are the held frames 0, 30, ..., P - 30 verbatim, and their VQ tokens (the pose tokenizer's `encode`; it must
+    be built with an encoder) are forced in the guide's draw, so the keyframes after them follow on from them.  Every random draw is a function of `seed` and the
     repetition index, so the result does not depend on `overlap`; pass a new seed per chunk for fresh noise.
 
     Returns generate_from_recording's keys for the NEW frames only -- {"face": [R, T_new, 256], "pose": [R, T_new, 104],
@@ -221,7 +235,7 @@ def continue_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: i
     Raises A2PError before any GPU work when P is not a positive multiple of 30 or exceeds the previous clip, when P + T_new exceeds
     the models' seq_len, when num_repetitions differs from previous's, when `previous` is not finite, and for what
     prepare_recording refuses."""
-    fm, pm = _check_models(face, pose)
+    fm, pm = _check_models(face, pose, guide_context)
     prev_face, prev_pose, prev_audio = _result_arrays(previous, "previous")
     R, T_prev = prev_face.shape[:2]
     if num_repetitions is not None and int(num_repetitions) != R:
@@ -251,10 +265,16 @@ def continue_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: i
     mask = torch.zeros(R, Tw, dtype=torch.bool)
     mask[:, :P] = True
     mask = mask.to(device)
+    known_pose = held(prev_pose, stats["pose_mean"], stats["pose_std"])
+    known_kf = None
+    if guide_context:
+        nk, nc = len(range(Tw)[::KEYFRAME_STEP]), P // KEYFRAME_STEP
+        kf_mask = torch.zeros(R, nk, dtype=torch.bool)
+        kf_mask[:, :nc] = True
+        known_kf = (known_pose[:, :, 0, ::KEYFRAME_STEP].transpose(1, 2).contiguous(), kf_mask)
     face_s, body_s, kf = _inpaint_window(face, pose, audio, R, Tw, held(prev_face, stats["code_mean"], stats["code_std"]),
-                                         held(prev_pose, stats["pose_mean"], stats["pose_std"]), mask,
-                                         (_CONT_UNIFORMS, _CONT_POSE, _CONT_FACE), seed, top_p, face_scale, pose_scale, overlap,
-                                         share_features)
+                                         known_pose, mask, (_CONT_UNIFORMS, _CONT_POSE, _CONT_FACE), seed, top_p, face_scale,
+                                         pose_scale, overlap, share_features, known_kf)
     kf = kf.cpu().numpy()[:, P // KEYFRAME_STEP:]
     return {"face": _motion(face_s, stats["code_mean"], stats["code_std"])[:, P:],
             "pose": _motion(body_s, stats["pose_mean"], stats["pose_std"])[:, P:],
@@ -277,7 +297,8 @@ def segment_window(T: int, start: int, end: int, seq_len: int):
 
 def regenerate_segment(face, pose, stats: Dict[str, np.ndarray], result: Dict[str, object], start_frame: int, end_frame: int,
                        parts: Sequence[str] = ("face", "pose"), top_p: float = 0.97, face_scale: float = 10.0, pose_scale: float = 2.0,
-                       seed: int = 10, overlap: bool = True, share_features: bool = True) -> Dict[str, object]:
+                       seed: int = 10, overlap: bool = True, share_features: bool = True,
+                       guide_context: bool = False) -> Dict[str, object]:
     """Re-roll frames [start_frame, end_frame) of a result and keep everything else.
 
     `result`: a dict with "face" [R, T, 256], "pose" [R, T, 104] and "audio" float64 [2, T * 1600] (generate_from_recording,
@@ -285,7 +306,10 @@ def regenerate_segment(face, pose, stats: Dict[str, np.ndarray], result: Dict[st
     frames, else seq_len frames on the 30-frame grid around the segment; its audio is the matching slice of result["audio"],
     z-normalised as prepare_recording does.  For every part in `parts` ("face", "pose" or both) the window is denoised (ddim) by
     inpaint_sample_loop with all its frames outside the segment held at the result's values (normalised with `stats`); the body's
-    keyframes are predicted again from the window's audio.  Random draws are functions of `seed` and the repetition index.
+    keyframes are predicted again from the window's audio.  `guide_context=True` (with "pose" in `parts`): every keyframe of the
+    window outside [start, end) is the result's pose at that frame, verbatim, and its VQ tokens are forced in the guide's draw (the
+    pose tokenizer must be built with an encoder).  The draw inside the segment follows the forced keyframes before it, and the
+    body model is conditioned on all of them, the ones after the segment included.  Random draws are functions of `seed` and the repetition index.
 
     Returns a copy of `result` in which only the listed parts' frames [start, end) are new: frames outside the segment and parts not
     listed are the input's arrays verbatim.  When the body is regenerated and result["keyframes"] is [R, T / 30, 104], its rows
@@ -299,6 +323,8 @@ def regenerate_segment(face, pose, stats: Dict[str, np.ndarray], result: Dict[st
     parts = tuple(parts) if not isinstance(parts, str) else (parts,)
     if not parts or any(p not in ("face", "pose") for p in parts):
         raise _lib.A2PError(f"parts must name 'face', 'pose' or both (got {parts!r})")
+    if guide_context and "pose" in parts:
+        require_encoder(pm)
     s, e = start_frame, end_frame
     if int(s) != s or int(e) != e or s % KEYFRAME_STEP or e % KEYFRAME_STEP or not 0 <= s < e <= T:
         raise _lib.A2PError(f"the segment [{start_frame}, {end_frame}) must have bounds that are multiples of {KEYFRAME_STEP} with "
@@ -313,9 +339,15 @@ def regenerate_segment(face, pose, stats: Dict[str, np.ndarray], result: Dict[st
     mask = mask.to(device)
     known_face = _normalised(res_face[:, ws:we], stats["code_mean"], stats["code_std"], device) if "face" in parts else None
     known_pose = _normalised(res_pose[:, ws:we], stats["pose_mean"], stats["pose_std"], device) if "pose" in parts else None
+    known_kf = None
+    if guide_context and known_pose is not None:
+        kf_mask = torch.ones(R, len(range(Tw)[::KEYFRAME_STEP]), dtype=torch.bool)
+        kf_mask[:, s // KEYFRAME_STEP - ws // KEYFRAME_STEP:e // KEYFRAME_STEP - ws // KEYFRAME_STEP] = False
+        # every row, the segment's old poses included: the tokenizer's causal encoder reads them for the keyframes after it
+        known_kf = (known_pose[:, :, 0, ::KEYFRAME_STEP].transpose(1, 2).contiguous(), kf_mask)
     face_s, body_s, kf = _inpaint_window(face, pose, audio, R, Tw, known_face, known_pose, mask,
                                          (_REGEN_UNIFORMS, _REGEN_POSE, _REGEN_FACE), seed, top_p, face_scale, pose_scale, overlap,
-                                         share_features)
+                                         share_features, known_kf)
     out = dict(result)
     if face_s is not None:
         new = np.array(result["face"], copy=True)

@@ -22,7 +22,7 @@ import torch
 from .. import _lib
 from ..audio import resampled_length
 from ..sample_parallel import derive_seed, per_sample_noise
-from .generate import _replace_keyframes
+from .generate import _guide_keyframes, _replace_keyframes
 from .recording import (BLOCK, MAX_FRAMES, SAMPLE_RATE, SAMPLES_PER_FRAME, _channels_last, _denoiser, _overlapped, can_share_features,
                         prepare_recording)
 
@@ -208,13 +208,20 @@ def _max_batch(*modules) -> int:
 
 def generate_from_long_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: int, num_repetitions: int = 1,
                                  top_p: float = 0.97, face_scale: float = 10.0, pose_scale: float = 2.0, seed: int = 10,
-                                 min_overlap: int = 120, overlap: bool = True, share_features: bool = True) -> Dict[str, object]:
+                                 min_overlap: int = 120, overlap: bool = True, share_features: bool = True,
+                                 chain_keyframes: bool = False) -> Dict[str, object]:
     """`generate_from_recording` for a recording of any length, over the windows of `plan_windows(T_total, seq_len, min_overlap)`.
 
     Per window (batch R*W): the audio front end / lip features, and guide transformer -> VQ keyframes.  The keyframes of two
     overlapping windows are predicted independently and may disagree on their shared frames; the body model's blend of the
     windows' x0 predictions absorbs that (the body follows a weighted mean of the two windows' keyframe-conditioned predictions).
     The face and body loops are `windowed_sample_loop` ddim, on two HIP streams when `overlap`.
+
+    `chain_keyframes=True` makes the overlapping keyframes agree instead: the guide runs window by window, and window w > 0 forces
+    its keyframes inside window w - 1 to window w - 1's VQ tokens and takes window w - 1's keyframe rows there verbatim (window
+    starts are on the 30-frame grid, so the two windows' keyframes fall on the same frames).  Its draws after the overlap follow on
+    from those keyframes.  Each free position draws the uniform it draws without chaining, so window 0 is unchanged.  This runs W
+    guide launches of R sequences instead of one launch of R * W.
 
     Random draws: the initial noise is `per_sample_noise((R, C, 1, T_total), [derive_seed(seed, 3 or 2, r)])`, as
     `generate_from_recording` draws it for T frames; the keyframe uniforms of window 0 come from `derive_seed(seed, 1, r)`, as
@@ -271,8 +278,11 @@ def generate_from_long_recording(face, pose, stats: Dict[str, np.ndarray], wavef
             return windowed_sample_loop(face_d, face_m, plan, R, y_face, noise_face)
 
         def run_body():
-            guide_y = {**guide_cond, "keyframes": torch.zeros(B, nk, pm.nfeats, device=device)}
-            y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p).to(device)
+            if chain_keyframes and W > 1:
+                y_body["keyframes"] = _chained_keyframes(pose_m, plan, R, guide_cond, uniforms, top_p, nk, pm.nfeats).to(device)
+            else:
+                guide_y = {**guide_cond, "keyframes": torch.zeros(B, nk, pm.nfeats, device=device)}
+                y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p).to(device)
             return windowed_sample_loop(pose_d, pose_m, plan, R, y_body, noise_pose)
 
         if overlap:
@@ -288,3 +298,29 @@ def generate_from_long_recording(face, pose, stats: Dict[str, np.ndarray], wavef
             "pose": pose_np * stats["pose_std"] + stats["pose_mean"],
             "keyframes": kf * stats["pose_std"] + stats["pose_mean"],
             "audio": rec.dual_audio, "T": T, "sr": SAMPLE_RATE, "window_starts": list(plan.starts)}
+
+
+def _chained_keyframes(pose_m, plan: WindowPlan, R: int, guide_cond, uniforms: torch.Tensor, top_p: float, nk: int,
+                       nv: int) -> torch.Tensor:
+    """generate_from_long_recording(chain_keyframes=True): one guide launch of R sequences per window, in window order.  Window
+    w > 0 forces its first keyframes (those inside window w - 1) to window w - 1's tokens and takes window w - 1's decoded rows
+    there.  Returns keyframes [R * W, nk, nv] on the host (row r * W + w)."""
+    W = plan.W
+    depth = pose_m.tokenizer.residual_depth
+    kf = torch.empty(R, W, nk, nv)
+    prev_tokens = None
+    for w in range(W):
+        cond = {k: v[w::W] for k, v in guide_cond.items()}          # rows r * W + w
+        y = {**cond, "keyframes": torch.zeros(R, nk, nv)}
+        forced, n_ov, off = None, 0, 0
+        if w > 0:
+            off = (plan.starts[w] - plan.starts[w - 1]) // KEYFRAME_STEP
+            n_ov = nk - off                                            # keyframes of window w that window w - 1 also has
+            forced = torch.full((R, nk, depth), -1, dtype=torch.int64, device=prev_tokens.device)
+            forced[:, :n_ov] = prev_tokens[:, off:]
+            forced = forced.reshape(R, -1)
+        pred, prev_tokens = _guide_keyframes({"y": y}, pose_m, uniforms[:, w::W], top_p, forced)
+        if w > 0:
+            pred[:, :n_ov] = kf[:, w - 1, off:]
+        kf[:, w] = pred
+    return kf.reshape(R * W, nk, nv)

@@ -125,7 +125,7 @@ def can_share_features(face_model, pose_model) -> bool:
 
 def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: int, num_repetitions: int = 1, top_p: float = 0.97,
                             face_scale: float = 10.0, pose_scale: float = 2.0, seed: int = 10, overlap: bool = True,
-                            share_features: bool = True) -> Dict[str, object]:
+                            share_features: bool = True, known_keyframes=None) -> Dict[str, object]:
     """`generate_results` (demo/demo.py:156-216) for `num_repetitions` samples of one recording.
 
     `face` / `pose`: (ClassifierFreeSampleModel, SpacedDiffusion) pairs as `sample.generate._setup_model` builds them, the pose
@@ -139,6 +139,12 @@ def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, 
     of its own takes the body model's features).  `overlap`: face on one HIP stream, guide -> VQ decode -> body on another;
     False runs face, then body, as the demo does.
 
+    `known_keyframes`: {frame: pose [104]} of un-normalised poses the body must take, e.g. to start or end in a given pose.  Frames
+    are multiples of 30 inside the clip; the same poses apply to every repetition.  Those keyframes are the given poses (normalised
+    with `stats` in float64, cast to fp32), and their VQ tokens (the pose tokenizer's `encode`; it must be built with an encoder) are
+    forced in the guide's draw, so the keyframes drawn after them follow on from them.  Bad frames, shapes or non-finite poses
+    raise A2PError before any GPU work.
+
     Returns {"face": [R, T, 256], "pose": [R, T, 104], "keyframes": [R, T / 30, 104] (un-normalised with the code_* / pose_*
     statistics: * std + mean), "audio": the un-normalised dual audio float64 [2, Lc], "T", "sr": 48000}."""
     from ..model.audio_frontend import NativeAudioFrontend
@@ -150,6 +156,12 @@ def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, 
             raise _lib.A2PError(f"the {name} model has no audio front end: construct it with audio_frontend=\"native\"")
     if getattr(pm, "transformer", None) is None or getattr(pm, "tokenizer", None) is None:
         raise _lib.A2PError("the pose model has no guide transformer: attach it with setup_guide_predictor(transformer, tokenizer)")
+    known = None
+    if known_keyframes is not None:
+        from .inpaint import require_encoder
+        from .long_form import recording_frames
+        require_encoder(pm)
+        known = _known_keyframes(known_keyframes, recording_frames(waveform, sr), stats, pm.nfeats)
     device = fm.null_cond_embed.device
     R = int(num_repetitions)
     prep = prepare_recording(waveform, sr, stats, R, seed, device, max_frames=min(fm.seq_len, pm.seq_len))
@@ -185,7 +197,8 @@ def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, 
 
         def run_body():
             guide_y = {**guide_cond, "keyframes": torch.zeros(R, nk, pm.nfeats, device=device)}
-            y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p).to(device)
+            kk = {} if known is None else {"known": known[0].expand(R, -1, -1), "known_mask": known[1].expand(R, -1)}
+            y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p, **kk).to(device)
             return pose_d.ddim_sample_loop(pose_m, (R, pm.nfeats, 1, T), noise=noise_pose, clip_denoised=False, model_kwargs={"y": y_body})
 
         if overlap:
@@ -201,6 +214,28 @@ def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, 
             "pose": pose_np * stats["pose_std"] + stats["pose_mean"],
             "keyframes": kf * stats["pose_std"] + stats["pose_mean"],
             "audio": prep.dual_audio, "T": T, "sr": SAMPLE_RATE}
+
+
+def _known_keyframes(known_keyframes, T: int, stats, nv: int):
+    """{frame: pose} -> (normalised fp32 [1, T / 30, nv], bool mask [1, T / 30]) on the host, or A2PError."""
+    if not isinstance(known_keyframes, dict) or not known_keyframes:
+        raise _lib.A2PError(f"known_keyframes must be a non-empty {{frame: pose[{nv}]}} dict")
+    nk = len(range(T)[::30])
+    known = np.zeros((nk, nv), np.float64)
+    mask = np.zeros(nk, bool)
+    mean = np.asarray(stats["pose_mean"], np.float64).reshape(-1)
+    std = np.asarray(stats["pose_std"], np.float64).reshape(-1)
+    for f, pose in known_keyframes.items():
+        if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or f % 30 or not 0 <= f < T:
+            raise _lib.A2PError(f"known_keyframes: frame {f!r} must be a multiple of 30 in [0, {T})")
+        v = np.asarray(pose.detach().cpu() if torch.is_tensor(pose) else pose, dtype=np.float64)
+        if v.shape != (nv,):
+            raise _lib.A2PError(f"known_keyframes[{f}] must be a pose of {nv} values (got shape {v.shape})")
+        if not np.isfinite(v).all():
+            raise _lib.A2PError(f"known_keyframes[{f}] holds non-finite values")
+        known[f // 30] = (v - mean) / std
+        mask[f // 30] = True
+    return torch.from_numpy(known.astype(np.float32))[None], torch.from_numpy(mask)[None]
 
 
 def _overlapped(face, pose, run_face, run_body, device):

@@ -242,3 +242,16 @@ def tokenizer_param_shapes(spec: TokenizerSpec) -> "OrderedDict[str, Tuple[int, 
     s["decoder.dec.8.weight"] = (spec.n_vertices, e, 1)
     s["decoder.dec.8.bias"] = (spec.n_vertices,)
     return s
+
+
+def tokenizer_encoder_param_shapes(spec: TokenizerSpec) -> "OrderedDict[str, Tuple[int, ...]]":
+    """The encode-side parameters of TemporalVertexCodec (model/vqvae.py:395-415): the causal dilated Conv1d encoder.  With
+    tokenizer_param_shapes these are every key `encode` reads (the codebooks are shared with `decode`)."""
+    e = spec.latent_dim
+    s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    s["encoder.enc.0.weight"] = (e, spec.n_vertices, 1)
+    s["encoder.enc.0.bias"] = (e,)
+    for i in (2, 4, 6, 8):
+        s[f"encoder.enc.{i}.weight"] = (e, e, 2)
+        s[f"encoder.enc.{i}.bias"] = (e,)
+    return s

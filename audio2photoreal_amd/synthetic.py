@@ -17,7 +17,8 @@ from typing import Dict
 import numpy as np
 import torch
 
-from .spec import DenoiserSpec, GuideSpec, TokenizerSpec, guide_param_shapes, param_shapes, tokenizer_param_shapes
+from .spec import (DenoiserSpec, GuideSpec, TokenizerSpec, guide_param_shapes, param_shapes, tokenizer_encoder_param_shapes,
+                   tokenizer_param_shapes)
 
 
 def _rng(seed: int, name: str) -> np.random.Generator:
@@ -118,6 +119,12 @@ def synthetic_guide_state_dict(spec: GuideSpec, seed: int = 10) -> Dict[str, tor
 
 def synthetic_tokenizer_state_dict(spec: TokenizerSpec, seed: int = 10) -> Dict[str, torch.Tensor]:
     return {name: _init_like_reference(seed, name, shape, "vq.") for name, shape in tokenizer_param_shapes(spec).items()}
+
+
+def synthetic_tokenizer_encoder_state_dict(spec: TokenizerSpec, seed: int = 10) -> Dict[str, torch.Tensor]:
+    """The encoder's parameters (`encoder.enc.*`), to load next to synthetic_tokenizer_state_dict's (own random streams, so that
+    dictionary is unchanged)."""
+    return {name: _init_like_reference(seed, name, shape, "vq.") for name, shape in tokenizer_encoder_param_shapes(spec).items()}
 
 
 def synthetic_frontend_state_dict(seed: int = 10, lip: bool = True, geometry=None) -> Dict[str, torch.Tensor]:

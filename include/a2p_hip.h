@@ -322,6 +322,13 @@ int a2p_guide_forward(a2p_guide_ctx* ctx, const int64_t* tokens, int32_t batch, 
  * nucleus probabilities the reference hands to Categorical (:212-214). */
 int a2p_guide_generate(a2p_guide_ctx* ctx, int32_t batch, int32_t n_steps, float top_p, const float* uniforms,
                        int64_t* tokens_out, float* sorted_probs_out, void* stream);
+/* a2p_guide_generate with positions whose token is given: forced int64 [batch, n_steps], -1 = draw, a value in [0, tokens) =
+ * that position's token.  A forced position runs the decoder stack (its self-attention K/V cache rows are written as for a
+ * drawn token), skips the softmax, sort and draw, writes its token to tokens_out, feeds it to the next position and zero-fills
+ * its sorted_probs_out row.  A free position still reads uniforms[i * batch + b].  Any other value is never looked up: the
+ * sequence writes -2 at that position and stops there.  forced == NULL is a2p_guide_generate. */
+int a2p_guide_generate_forced(a2p_guide_ctx* ctx, int32_t batch, int32_t n_steps, float top_p, const float* uniforms,
+                              const int64_t* forced, int64_t* tokens_out, float* sorted_probs_out, void* stream);
 /* test / diagnostics: copy a prepared buffer ("pre_audio", "ct", "mem", "memr", "hidden", "film", "kc", "vc") to the host */
 int a2p_guide_debug_read(a2p_guide_ctx* ctx, const char* name, void* host, int64_t bytes);
 /* TemporalVertexCodec.decode: q int64 [batch, T, depth] -> out fp32 [batch, T, vertices].  codebooks: `depth` device
@@ -330,6 +337,16 @@ int a2p_guide_debug_read(a2p_guide_ctx* ctx, const char* name, void* host, int64
 int a2p_vq_decode(const int64_t* q, int32_t batch, int32_t T, int32_t depth, int32_t categories, int32_t latent,
                   int32_t vertices, const float* const* codebooks, const float* const* conv_w, const float* const* conv_b,
                   float* out, void* stream);
+/* TemporalVertexCodec.encode (model/vqvae.py:499-506): poses fp32 [batch, T, vertices] (keyframe-rate rows, normalised) ->
+ * tokens_out int64 [batch, T, depth] and / or latents_out fp32 [batch, T, latent] (the encoder's output; either may be NULL, not
+ * both).  Encoder: 7 zero rows of left padding, encoder.enc.0 (Conv1d vertices -> latent, k=1), LeakyReLU(0.2), enc.{2,4,6,8}
+ * (Conv1d latent -> latent, k=2, dilation 1,2,3,1) with LeakyReLU between them and none after the last.  Residual quantisation:
+ * per level idx = argmax(-(|x|^2 - 2 x.embed + |embed|^2)) in fp32, lowest index on an exact tie, then x -= embed[idx].
+ * code_norms: `depth` device pointers [categories] holding |embed|^2.  The pointer arrays are host memory.  A2P_ERR_ARG when
+ * 2 (T + 7) latent floats exceed 64 KB of LDS (T <= 121 at latent 64) or latent is not a multiple of 4. */
+int a2p_vq_encode(const float* poses, int32_t batch, int32_t T, int32_t depth, int32_t categories, int32_t latent,
+                  int32_t vertices, const float* const* codebooks, const float* const* code_norms, const float* const* conv_w,
+                  const float* const* conv_b, int64_t* tokens_out, float* latents_out, void* stream);
 
 /* ---- audio front end ------------------------------------------------------------------
  * What FiLMTransformer.forward computes from y["audio"] before anything else, in every step and pass (model/diffusion.py:
