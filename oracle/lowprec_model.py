@@ -66,8 +66,13 @@ def _round(x: Tensor, fmt: str) -> Tensor:
 
 
 class Rounding:
-    def __init__(self, default: str = "fp16", modes: Optional[Dict[str, str]] = None):
-        self.default, self.modes = default, dict(modes or {})
+    """`attn` picks which attention kernel's rounding `_attn` restates: "attn_kernel" (kernels_attn.h, the default) or "attn3"
+    (kernels_attn3.h, the one-wave-per-SIMD kernel launch_attn takes at the benchmarked batch sizes)."""
+
+    def __init__(self, default: str = "fp16", modes: Optional[Dict[str, str]] = None, attn: str = "attn_kernel"):
+        if attn not in ("attn_kernel", "attn3"):
+            raise ValueError(attn)
+        self.default, self.modes, self.attn = default, dict(modes or {}), attn
 
     def __call__(self, site: str, x: Tensor) -> Tensor:
         return _round(x, self.modes.get(site, self.default))
@@ -79,18 +84,35 @@ def _mm(R: Rounding, sa: str, a: Tensor, sw: str, w: Tensor, b: Optional[Tensor]
 
 
 def _attn(R: Rounding, pre: str, q: Tensor, k: Tensor, v: Tensor, nheads: int, tail: int = 0) -> Tensor:
-    """softmax(q k^T / sqrt(dh)) v on already-projected (and already rounded) q, k, v; P is rounded before the PV product and
-    the row sum is taken over the UNROUNDED fp32 numerators, as kernels_attn.h does."""
+    """softmax(q k^T / sqrt(dh)) v on already-projected (and already rounded) q, k, v, with the rounding of the kernel
+    `R.attn` names (attn_kernel unless the hook says otherwise).
+
+    attn_kernel (kernels_attn.h): scores in fp32, P rounded before the PV product, the row sum taken over the UNROUNDED fp32
+    numerators.
+
+    attn3 (kernels_attn3.h): the stored 16-bit Q is multiplied by scale_log2e = log2(e)/sqrt(dh) in fp32 and rounded to 16 bits
+    AGAIN (site `<pre>.q`, the format of the stored Q) when its fragments are loaded; scores are in log2 units, P = exp2(s - m) is
+    rounded before the PV product, and the row sum is taken over the ROUNDED P (the ones-fragment MFMA l += ones x P^T sums the
+    16-bit operand).  The kernel's lazy reference m_ref (moved only when a score exceeds it by more than 8) changes bits, not the
+    expected error: softmax is invariant to the reference and every P stays <= 256 in either form, so the model subtracts the
+    exact row maximum."""
     B, Lq, d = q.shape
     Lk, dh = k.shape[1], d // nheads
     qh = q.view(B, Lq, nheads, dh).transpose(1, 2)
     kh = k.view(B, Lk, nheads, dh).transpose(1, 2)
     vh = v.view(B, Lk, nheads, dh).transpose(1, 2)
-    s = (qh @ kh.transpose(-1, -2)) / math.sqrt(dh)
+    if getattr(R, "attn", "attn_kernel") == "attn3":
+        scale_log2e = float(torch.tensor(1.4426950408889634 / math.sqrt(dh), dtype=torch.float32))   # an fp32 kernel argument
+        s2 = R(pre + ".q", qh * scale_log2e) @ kh.transpose(-1, -2)                                   # log2 units
+        s = s2 * math.log(2.0)                                                                         # natural units (probe)
+        pr = R(pre + ".p", torch.exp2(s2 - s2.amax(-1, keepdim=True)))
+        o = (pr @ vh) / pr.sum(-1, keepdim=True)
+    else:
+        s = (qh @ kh.transpose(-1, -2)) / math.sqrt(dh)
+        p = torch.exp(s - s.amax(-1, keepdim=True))
+        o = (R(pre + ".p", p) @ vh) / p.sum(-1, keepdim=True)
     if hasattr(R, "logit_peak"):   # tests/tools/trained_like_budget.py: the largest |logit| any attention of the forward sees
         R.logit_peak = max(R.logit_peak, float(s.abs().max()))
-    p = torch.exp(s - s.amax(-1, keepdim=True))
-    o = (R(pre + ".p", p) @ vh) / p.sum(-1, keepdim=True)
     return o.transpose(1, 2).reshape(B, Lq, d)
 
 
@@ -113,7 +135,7 @@ class LowPrecDenoiser(O.OracleDenoiser):
         q = R("cond.a", _mm(R, "cond.a", xr, "cond.w", inw[:d], inb[:d]))
         k = R("cond.a", _mm(R, "cond.a", xr, "cond.w", inw[d:2 * d], inb[d:2 * d]))
         v = R("cond.a", _mm(R, "cond.a", xh, "cond.w", inw[2 * d:], inb[2 * d:]))
-        Rc = Rounding(self.R.modes.get("cond.a", self.R.default))
+        Rc = Rounding(self.R.modes.get("cond.a", self.R.default), attn=getattr(self.R, "attn", "attn_kernel"))
         ao = R("cond.a", _attn(Rc, "x", q, k, v, self.H))
         x = x + _mm(R, "cond.a", ao, "cond.w", g("self_attn.out_proj.weight"), g("self_attn.out_proj.bias"))
         xh = O.layer_norm(x, g("norm2.weight"), g("norm2.bias"))

@@ -3,9 +3,13 @@ with oracle/lowprec_model.py (the model of the GPU's rounding sites that predict
 the fp32 oracle: the guided forward and the ddim10 loop of the bench configuration with synthetic weights pushed towards trained
 statistics (audio2photoreal_amd.synthetic.trained_like_state_dict) -- every Linear weight x {2, 4, 8}, peaky attention logits,
 a residual stream of 1e3 .. 1e4 units.  Reports, per scenario: the largest |logit| and the largest 16-bit-stored operand the
-fp32 oracle sees (65504 is IEEE half's ceiling), whether the 16-bit model stays finite, and the errors.
+fp32 oracle sees (65504 is IEEE half's ceiling), whether the 16-bit model stays finite, and the errors -- for attn_kernel's
+rounding and for attn3_kernel's (the attention kernel of the benchmarked batch sizes: Q rounded again after its log2(e)/sqrt(dh)
+pre-scale, row sums over the rounded P; oracle/lowprec_model.py `_attn`).  The combined and near-bound scenarios place row maxima
+around 16, at 0.9-1.0 x the 16-bit envelope (_lib.LOGIT_ENVELOPE_FP16) and beyond it.
 
-usage: python tests/tools/trained_like_budget.py [--model face] [--T 600] [--steps 10] [--out profiles/r04_trained_like_budget.json]
+usage: python tests/tools/trained_like_budget.py [--model face] [--T 600] [--steps 10] [--only name] [--out profiles/<name>.json]
+       (--steps 0: guided forwards only; CPU threads: $OMP_NUM_THREADS, else all cores)
 """
 import argparse
 import json
@@ -36,6 +40,14 @@ SCENARIOS = {
     "residual stream x1e3": {"resid_gain": 1e3},
     "residual stream x1e4": {"resid_gain": 1e4},
     "weights x4 + q,k x2 + residual x1e3": {"weight_gain": 4.0, "qk_gain": 2.0, "resid_gain": 1e3},
+    # combined and near-bound scenarios (the envelope is decided by one number, the row maximum; these probe it from two directions:
+    # ordinary weight growth with slightly peaked attention, and peaked attention alone)
+    "weights x2 + q,k x1.1": {"weight_gain": 2.0, "qk_gain": 1.1},
+    "weights x2 + q,k x1.15": {"weight_gain": 2.0, "qk_gain": 1.15},
+    "weights x2 + q,k x1.2": {"weight_gain": 2.0, "qk_gain": 1.2},
+    "q,k rows x2.2": {"qk_gain": 2.2},
+    "q,k rows x2.5": {"qk_gain": 2.5},
+    "q,k rows x2.7": {"qk_gain": 2.7},
 }
 
 
@@ -57,10 +69,10 @@ def main():
     ap.add_argument("--model", default="face")
     ap.add_argument("--T", type=int, default=600)
     ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r04_trained_like_budget.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "trained_like_envelope_face_T600.json"))
     ap.add_argument("--only", default="")
     a = ap.parse_args()
-    torch.set_num_threads(os.cpu_count() or 1)
+    torch.set_num_threads(int(os.environ.get("OMP_NUM_THREADS", 0)) or os.cpu_count() or 1)
     fmt = a.model
     spec = face_spec() if fmt == "face" else pose_spec()
     B, T = 1, a.T
@@ -70,7 +82,7 @@ def main():
     samp = O.OracleSampler("ddim10")
     t700 = torch.tensor([700])
     rel = lambda g, w: float((g - w).norm() / w.norm())
-    res = {"config": {"model": fmt, "T": T, "B": B, "scale": float(scale[0]), "sampler": f"ddim10 x {a.steps} steps",
+    res = {"config": {"model": fmt, "T": T, "B": B, "scale": float(scale[0]), "sampler": f"ddim10 x {a.steps} steps" if a.steps else "guided forward at t=700 only",
                       "tool": "oracle/lowprec_model.py vs oracle/a2p_oracle.py (CPU)"}, "rows": {}}
     for name, kw in SCENARIOS.items():
         if a.only and a.only not in name:
@@ -82,8 +94,9 @@ def main():
         with torch.no_grad():
             probe_out = O.OracleDenoiser(sd, fmt, spec.num_layers, spec.num_heads).forward_cfg(inp["x_T"], t700, inp["cond_embed"], scale, kf, mk)
         g = float(probe_out.std())
-        head = "final_layer" if fmt == "face" else [k for k in sd if k.startswith("final_layer") or k.startswith("pose_tail") or "conv" in k.split(".")[0]][0].split(".")[0]
-        for k in ("final_layer.weight", "final_layer.bias"):
+        # the LAST linear map of the model (pose: final_conv behind the conv tail, as tests/test_hip_round4.py rescales it)
+        head = [k for k in sd if k.startswith("final_conv.")] if spec.is_pose else ["final_layer.weight", "final_layer.bias"]
+        for k in head:
             if k in sd:
                 sd[k] = sd[k] / g
 
@@ -91,7 +104,7 @@ def main():
             with torch.no_grad():
                 fwd = den.forward_cfg(inp["x_T"], t700, inp["cond_embed"], scale, kf, mk)
                 fn = lambda x, ts: den.forward_cfg(x, ts, inp["cond_embed"], scale, kf, mk)
-                x0, _ = samp.ddim_sample_loop(fn, inp["x_T"], max_steps=a.steps)
+                x0 = samp.ddim_sample_loop(fn, inp["x_T"], max_steps=a.steps)[0] if a.steps else fwd
             return fwd, x0
 
         want_fwd, want_x0 = run(O.OracleDenoiser(sd, fmt, spec.num_layers, spec.num_heads))
@@ -103,11 +116,16 @@ def main():
                "peak_logit_operands": {k: probe.peak[k] for k in ("self.q", "self.k", "cross.q") if k in probe.peak},
                "peak_logit": getattr(probe, "logit_peak", None)}
         for base in ("fp16", "bf16"):
-            fwd, x0 = run(LP.LowPrecDenoiser(sd, fmt, spec.num_layers, spec.num_heads, LP.Rounding(base, {s: "fp16x2" if base == "fp16" else "fp32" for s in ("fin.a", "fin.w", "in.a", "in.w", "tail.a", "tail.w")})))
-            fin = bool(torch.isfinite(fwd).all() and torch.isfinite(x0).all())
-            row[base] = {"finite": fin, "fwd_rel_l2": rel(fwd, want_fwd) if fin else None, "loop_rel_l2": rel(x0, want_x0) if fin else None}
+            for attn, col in (("attn_kernel", base), ("attn3", base + "_attn3")):
+                modes = {s: "fp16x2" if base == "fp16" else "fp32" for s in ("fin.a", "fin.w", "in.a", "in.w", "tail.a", "tail.w")}
+                fwd, x0 = run(LP.LowPrecDenoiser(sd, fmt, spec.num_layers, spec.num_heads, LP.Rounding(base, modes, attn=attn)))
+                fin = bool(torch.isfinite(fwd).all() and torch.isfinite(x0).all())
+                row[col] = {"finite": fin, "fwd_rel_l2": rel(fwd, want_fwd) if fin else None,
+                            "loop_rel_l2": rel(x0, want_x0) if fin and a.steps else None}
         res["rows"][name] = row
-        print(f"{name:42s} |logit| <= {row['peak_logit']:.1f}  peak operand {row['peak_16bit_operand']:.3g} ({row['peak_site']})  fp16 {row['fp16']}  bf16 {row['bf16']}  ({time.time() - t0:.0f} s)", flush=True)
+        f = lambda c: f"{c}: fwd {row[c]['fwd_rel_l2'] or float('nan'):.3g} loop {row[c]['loop_rel_l2'] or float('nan'):.3g}"
+        print(f"{name:40s} |logit| <= {row['peak_logit']:.1f}  peak operand {row['peak_16bit_operand']:.3g} ({row['peak_site']})  "
+              f"{f('fp16')}  {f('fp16_attn3')}  {f('bf16')}  {f('bf16_attn3')}  ({time.time() - t0:.0f} s)", flush=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
 
