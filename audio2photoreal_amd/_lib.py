@@ -28,6 +28,8 @@ TABLE_NAMES = (
     "sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "alphas_cumprod", "alphas_cumprod_prev",
     "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod", "alphas_cumprod_next",
 )
+# a2p_ms_coef_id: rows of the DPM-Solver++(2M) coefficient table (GaussianDiffusion.multistep_table)
+MS_COEF_NAMES = ("CX", "B1", "B2", "P2")
 PLMS_PREDICT, PLMS_AB1, PLMS_AB2, PLMS_AB3, PLMS_AB4, PLMS_EULER = range(6)
 
 EXPORTS = (
@@ -40,6 +42,7 @@ EXPORTS = (
     "a2p_frontend_create", "a2p_frontend_destroy", "a2p_frontend_set_weight", "a2p_frontend_finalize",
     "a2p_frontend_encode_audio", "a2p_frontend_encode_lip", "a2p_resample", "a2p_dual_audio",
     "a2p_sample_step_windowed", "a2p_window_gather", "a2p_sample_step_inpaint", "a2p_guide_generate_forced", "a2p_vq_encode",
+    "a2p_sample_step_multistep", "a2p_sample_step_windowed_multistep", "a2p_multistep_update",
 )
 
 
@@ -153,6 +156,9 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_sample_step_windowed": [vp, i32, vp, vp, vp, vp, i32, vp, vp, f32, i32, C.POINTER(i32), vp, i32, i32, vp, vp, vp, vp, vp],
         "a2p_window_gather": [vp, i32, i32, i32, i32, i32, C.POINTER(i32), i32, i32, vp, vp],
         "a2p_sample_step_inpaint": [vp, i32, vp, vp, vp, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp],
+        "a2p_sample_step_multistep": [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp],
+        "a2p_sample_step_windowed_multistep": [vp, vp, vp, vp, i32, vp, vp, vp, i32, C.POINTER(i32), vp, i32, i32, vp, vp, vp, vp, vp],
+        "a2p_multistep_update": [vp, vp, vp, vp, vp, i32, i32, i64, vp, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

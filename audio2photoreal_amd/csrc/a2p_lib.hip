@@ -33,6 +33,7 @@
 #include "kernels_gemm.h"
 #include "kernels_inpaint.h"
 #include "kernels_misc.h"
+#include "kernels_multistep.h"
 #include "kernels_small.h"
 #include "kernels_tail.h"
 #include "kernels_vq.h"

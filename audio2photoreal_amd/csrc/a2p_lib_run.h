@@ -1334,6 +1334,62 @@ extern "C" int a2p_sample_step_windowed(a2p_ctx* c, int32_t sampler, const float
   return 0;
 }
 
+// ---- DPM-Solver++(2M) step tails (kernels_multistep.h) ----
+extern "C" int a2p_sample_step_multistep(a2p_ctx* c, const float* x, const int64_t* t_idx, const int64_t* timestep_map, int32_t n_steps,
+                                         const float* scale, const float* coefs, const float* x0_prev, int32_t clip_denoised,
+                                         const float* known, const uint8_t* known_mask, float* x_next, float* pred_xstart, void* stream) {
+  ARG(c && x && t_idx && timestep_map && coefs && x_next && pred_xstart, "null argument");
+  ARG(scale, "classifier-free guidance scale required");
+  ARG(!known == !known_mask, "held elements need both known values and a mask");
+  ARG(n_steps >= 1, "bad n_steps %d", n_steps);
+  ARG(pred_xstart != x0_prev, "pred_xstart must not alias x0_prev (the history of a repeated step)");
+  hipStream_t s = (hipStream_t)stream;
+  int64_t* t_orig = reinterpret_cast<int64_t*>(c->tmpa.p);
+  map_timesteps_kernel<<<1, 256, 0, s>>>(t_idx, timestep_map, t_orig, c->pB);
+  int rows = 0;
+  CHK(run_forward(c, x, t_orig, A2P_PASS_CFG, &rows, s));
+  MsStepP mp;
+  memset(&mp, 0, sizeof(mp));
+  mp.mo = c->mo.f(); mp.mo_seq_rows = rows; mp.B = c->pB; mp.C = c->C; mp.Tn = c->pT;
+  mp.scale = scale; mp.x = x; mp.t_idx = t_idx; mp.coefs = coefs; mp.n_steps = n_steps; mp.x0_prev = x0_prev; mp.clip = clip_denoised;
+  mp.known = known; mp.mask = known_mask; mp.x_next = x_next; mp.x0 = pred_xstart;
+  mp.nonfinite = reinterpret_cast<int*>(c->nonfinite.p);
+  dim3 grid((mp.Tn + 31) / 32, (mp.C + 31) / 32, mp.B);
+  multistep_step_tail_kernel<<<grid, 256, 0, s>>>(mp);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int a2p_sample_step_windowed_multistep(a2p_ctx* c, const float* x_win, const int64_t* t_idx, const int64_t* timestep_map,
+                                                  int32_t n_steps, const float* scale, const float* coefs, const float* x0_prev_win,
+                                                  int32_t clip_denoised, const int32_t* win_starts_host, const float* win_weights,
+                                                  int32_t W, int32_t T_total, float* x_next_win, float* x0_win, float* x_global,
+                                                  float* x0_global, void* stream) {
+  ARG(c && x_win && t_idx && timestep_map && coefs && x_next_win && x0_win, "null argument");
+  ARG(scale, "classifier-free guidance scale required");
+  ARG(win_weights, "null window weights");
+  ARG(n_steps >= 1, "bad n_steps %d", n_steps);
+  ARG(!x0_prev_win || (x0_win != x0_prev_win && x0_global != x0_prev_win), "the pred_xstart outputs must not alias x0_prev_win (the history of a repeated step)");
+  ARG(c->pB > 0 && W >= 1 && c->pB % W == 0, "prepared batch %d is not repetitions x %d windows", c->pB, W);
+  CHK(check_windows(win_starts_host, W, c->pT, T_total));
+  hipStream_t s = (hipStream_t)stream;
+  int64_t* t_orig = reinterpret_cast<int64_t*>(c->tmpa.p);
+  map_timesteps_kernel<<<1, 256, 0, s>>>(t_idx, timestep_map, t_orig, c->pB);
+  int rows = 0;
+  CHK(run_forward(c, x_win, t_orig, A2P_PASS_CFG, &rows, s));
+  MsWinStepP wp;
+  memset(&wp, 0, sizeof(wp));
+  wp.mo = c->mo.f(); wp.mo_seq_rows = rows; wp.R = c->pB / W; wp.W = W; wp.C = c->C; wp.Tw = c->pT; wp.Ttot = T_total;
+  wp.scale = scale; wp.weights = win_weights; wp.x = x_win; wp.t_idx = t_idx; wp.coefs = coefs; wp.n_steps = n_steps;
+  wp.x0_prev = x0_prev_win; wp.clip = clip_denoised; wp.x_next = x_next_win; wp.x0 = x0_win; wp.x_glob = x_global; wp.x0_glob = x0_global;
+  wp.nonfinite = reinterpret_cast<int*>(c->nonfinite.p);
+  memcpy(wp.starts, win_starts_host, sizeof(int32_t) * W);
+  dim3 grid((T_total + 31) / 32, (c->C + 31) / 32, wp.R);
+  windowed_multistep_step_tail_kernel<<<grid, 256, 0, s>>>(wp);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int a2p_window_gather(const float* src, int32_t reps, int32_t T_total, int32_t k, int32_t ch, int32_t channels_first,
                                  const int32_t* win_starts_host, int32_t W, int32_t T_w, float* dst, void* stream) {
   ARG(src && dst, "null argument");
@@ -1427,6 +1483,18 @@ extern "C" int a2p_ddim_update(const float* pred_xstart, const float* x, const i
   const int64_t total = batch * per_sample;
   ddim_update_kernel<<<(int)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(pred_xstart, x, t_idx, tables, n_steps, noise, eta,
                                                                                  per_sample, total, sample);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int a2p_multistep_update(const float* x, const float* pred_xstart, const float* x0_prev, const int64_t* t_idx, const float* coefs,
+                                    int32_t n_steps, int32_t batch, int64_t per_sample, float* sample, void* stream) {
+  ARG(x && pred_xstart && t_idx && coefs && sample, "null argument");
+  ARG(n_steps >= 1, "bad n_steps %d", n_steps);
+  ARG(pred_xstart != x0_prev, "pred_xstart must not alias x0_prev");
+  const int64_t total = batch * per_sample;
+  multistep_update_kernel<<<(int)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, pred_xstart, x0_prev, t_idx, coefs, n_steps,
+                                                                                      per_sample, total, sample);
   HIPCHK(hipGetLastError());
   return 0;
 }

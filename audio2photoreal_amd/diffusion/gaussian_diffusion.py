@@ -147,6 +147,45 @@ class GaussianDiffusion:
             self._dev_cache[key] = th.from_numpy(mat.astype(np.float32)).to(device).contiguous()
         return self._dev_cache[key]
 
+    def multistep_table(self) -> np.ndarray:
+        """float64 [A2P_NMS, N] coefficients of DPM-Solver++(2M) (Lu et al. 2022, data prediction), rows in a2p_ms_coef_id order
+        (CX, B1, B2, P2).  Step i goes from abar_i to its target abar_prev_i: alpha = sqrt(abar), sigma = sqrt(1 - abar),
+        lambda = log alpha - log sigma, primes for the target, h_i = lambda'_i - lambda_i.
+          first order  x' = CX x + B1 x0,               CX = sigma'/sigma, B1 = -alpha' expm1(-h)   (= DDIM with eta = 0)
+          second order x' = CX x + B2 x0 + P2 x0_prev,  B2 = B1 (1 + 1/(2r)), P2 = -B1/(2r), r_i = h_{i+1} / h_i
+        h_{i+1} is the previous step's h (abar_prev_{i+1} = abar_i).  Rows without a previous step (i = N-1) and the step into
+        t = 0 (i = 1: the last jump in log-SNR is large, and extrapolating over it costs more than it gains) are first order:
+        B2 = B1, P2 = 0.  Row 0 has sigma' = 0 and returns x0: CX = 0, B1 = B2 = 1, P2 = 0."""
+        key = ("ms64",)
+        if key not in self._dev_cache:
+            n = self.num_timesteps
+            acp, acpp = self.alphas_cumprod, self.alphas_cumprod_prev
+            cx, b1, h = np.zeros(n), np.ones(n), np.full(n, np.nan)
+            for i in range(1, n):
+                a, s = math.sqrt(acp[i]), math.sqrt(1.0 - acp[i])
+                ap, sp = math.sqrt(acpp[i]), math.sqrt(1.0 - acpp[i])
+                h[i] = (math.log(ap) - math.log(sp)) - (math.log(a) - math.log(s))
+                cx[i] = sp / s
+                b1[i] = -ap * math.expm1(-h[i])
+            b2, p2 = b1.copy(), np.zeros(n)
+            for i in range(2, n - 1):
+                r = h[i + 1] / h[i]
+                b2[i] = b1[i] * (1.0 + 1.0 / (2.0 * r))
+                p2[i] = -b1[i] / (2.0 * r)
+            self._dev_cache[key] = np.stack([cx, b1, b2, p2])
+        return self._dev_cache[key]
+
+    def _multistep_coefs(self, device) -> th.Tensor:
+        """fp32 [A2P_NMS, N] on `device`: multistep_table() cast to float32 (as _tables casts its rows)."""
+        key = ("ms", str(device))
+        if key not in self._dev_cache:
+            self._dev_cache[key] = th.from_numpy(self.multistep_table().astype(np.float32)).to(device).contiguous()
+        return self._dev_cache[key]
+
+    def _timestep_map(self, device) -> th.Tensor:
+        return self._timestep_map_tensor(device) if hasattr(self, "_timestep_map_tensor") else \
+            self._dev_cache.setdefault(("tmap", str(device)), th.arange(self.num_timesteps, device=device, dtype=th.int64))
+
     def _step_index_tensor(self, device, batch) -> th.Tensor:
         key = ("idx", str(device), batch)
         if key not in self._dev_cache:
@@ -410,6 +449,89 @@ class GaussianDiffusion:
                     step_noise=step_noise):
                 final = sample
             return final["pred_xstart"]
+        return self._run_call(run, model, device)
+
+    # ------------------------------------------------------------------ DPM-Solver++(2M) (multistep_table; csrc/kernels_multistep.h)
+    @staticmethod
+    def check_multistep_args(order=2, eta=0.0, step_noise=None):
+        """The solver is deterministic and of order 1 or 2: anything else is refused before any GPU work."""
+        if isinstance(order, bool) or order not in (1, 2):
+            raise _lib.A2PError(f"dpm++2m: order must be 1 or 2 (got {order!r})")
+        if eta != 0.0 or step_noise is not None:
+            raise _lib.A2PError("dpm++2m solves the probability-flow ODE: it takes no eta and no step_noise")
+
+    def dpm_solver_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, x0_prev=None,
+                          order=2):
+        """One DPM-Solver++(2M) step from step index t to its target (multistep_table).  `x0_prev`: the previous step's
+        pred_xstart, None on the first step of a call (the step is then first order); order=1 ignores it.  The fused path
+        (a2p_sample_step_multistep) runs when `_fused` holds; any other callable goes through p_mean_variance and
+        a2p_multistep_update.  clip_denoised clamps x0 before the update; the clamped x0 is the returned pred_xstart."""
+        self.check_multistep_args(order)
+        if cond_fn is not None:
+            raise NotImplementedError("cond_fn guidance is out of scope")
+        hist = x0_prev if order == 2 else None
+        t64 = t.to(th.int64).contiguous()
+        if self._fused(model, denoised_fn, cond_fn):
+            x_next, x0 = model.a2p_sample_step_multistep(x, t64, self._timestep_map(x.device), self._multistep_coefs(x.device),
+                                                         (model_kwargs or {})["y"], hist, clip_denoised)
+            return {"sample": x_next, "pred_xstart": x0}
+        out = self.p_mean_variance(model, x, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, model_kwargs=model_kwargs)
+        x = self._prep(x)
+        x0 = out["pred_xstart"]
+        hist = None if hist is None else self._prep(hist)
+        if hist is not None and hist.shape != x.shape:
+            raise _lib.A2PError(f"x0_prev {tuple(hist.shape)} does not match x {tuple(x.shape)}")
+        sample = self._elementwise("a2p_multistep_update", x, _lib.ptr(x), _lib.ptr(x0), _lib.ptr(hist), _lib.ptr(t64),
+                                   _lib.ptr(self._multistep_coefs(x.device)), self.num_timesteps)
+        return {"sample": sample, "pred_xstart": x0}
+
+    def _multistep_loop(self, step, model, shape, noise, model_kwargs, device, progress, skip_timesteps, init_image,
+                        randomize_class, order=2):
+        """`_loop` for the multistep solver.  `step(model, img, t, x0_prev, model_kwargs=...)` is a pure function of its
+        arguments; the history lives in THIS generator and advances only after `_loop` hands a step out, so `_loop`'s repeat of an
+        escalated first step reads the same (absent) history, and `_run_call`'s repeat of the call starts from none."""
+        hist = [None]
+
+        def one(model, img, t, model_kwargs=None, noise=None):
+            return step(model, img, t, hist[0] if order == 2 else None, model_kwargs=model_kwargs)
+
+        for out in self._loop(one, model, shape, noise, model_kwargs, device, progress, skip_timesteps, init_image, randomize_class,
+                              None):
+            hist[0] = out["pred_xstart"]
+            yield out
+
+    def dpm_solver_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                           model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
+                                           randomize_class=False, cond_fn_with_grad=False, step_noise=None, order=2):
+        self.check_multistep_args(order, 0.0, step_noise)
+        if cond_fn_with_grad:
+            raise NotImplementedError("*_with_grad samplers are out of scope")
+
+        def step(model, img, t, x0_prev, model_kwargs=None):
+            return self.dpm_solver_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                                          model_kwargs=model_kwargs, x0_prev=x0_prev, order=order)
+        yield from self._multistep_loop(step, model, shape, noise, model_kwargs, device, progress, skip_timesteps, init_image,
+                                        randomize_class, order)
+
+    def dpm_solver_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                               model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
+                               randomize_class=False, cond_fn_with_grad=False, dump_steps=None, const_noise=False, step_noise=None,
+                               order=2):
+        """DPM-Solver++(2M) over this diffusion's (respaced) steps, one model call per step: `ddim_sample_loop`'s keywords
+        without eta, plus `order` (1: DDIM with eta = 0 in the solver's form).  Returns the final "sample", which is the last
+        step's pred_xstart bits (row 0 of multistep_table)."""
+        self.check_multistep_args(order, 0.0, step_noise)
+        if dump_steps is not None or const_noise is True:
+            raise NotImplementedError()
+
+        def run():
+            final = None
+            for sample in self.dpm_solver_sample_loop_progressive(
+                    model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                    model_kwargs=model_kwargs, device=device, progress=progress, skip_timesteps=skip_timesteps,
+                    init_image=init_image, randomize_class=randomize_class, cond_fn_with_grad=cond_fn_with_grad, order=order):
+                final = sample
+            return final["sample"]
         return self._run_call(run, model, device)
 
     # ------------------------------------------------------------------ DDIM reverse ODE, PLMS (SURVEY.md §8 f4)

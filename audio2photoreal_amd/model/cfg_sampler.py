@@ -67,3 +67,12 @@ class ClassifierFreeSampleModel(nn.Module):
     def a2p_sample_step_inpaint(self, sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised, known, known_mask):
         """a2p_sample_step with held elements (sample/inpaint.py inpaint_sample_loop)."""
         return self.model.sample_step_inpaint(sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised, known, known_mask)
+
+    def a2p_sample_step_multistep(self, x, t_idx, timestep_map, coefs, y, x0_prev, clip_denoised, known=None, known_mask=None):
+        """One DPM-Solver++(2M) step, plain or with held elements (GaussianDiffusion.dpm_solver_sample, inpaint_sample_loop)."""
+        return self.model.sample_step_multistep(x, t_idx, timestep_map, coefs, y, x0_prev, clip_denoised, known, known_mask)
+
+    def a2p_sample_step_windowed_multistep(self, x, t_idx, timestep_map, coefs, y, x0_prev, clip_denoised, starts, weights, T_total):
+        """The windowed form of a2p_sample_step_multistep (sample/long_form.py windowed_sample_loop)."""
+        return self.model.sample_step_windowed_multistep(x, t_idx, timestep_map, coefs, y, x0_prev, clip_denoised, starts, weights,
+                                                         T_total)

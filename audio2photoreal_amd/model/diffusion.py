@@ -517,3 +517,59 @@ class FiLMTransformer(nn.Module):
                                                            _lib.ptr(x_next), _lib.ptr(x0), _lib.current_stream(x.device)),
                        "a2p_sample_step_inpaint")
         return x_next, x0
+
+    def sample_step_multistep(self, x, t_idx, timestep_map, coefs, y, x0_prev, clip_denoised: bool, known=None, known_mask=None):
+        """One DPM-Solver++(2M) step (include/a2p_hip.h a2p_sample_step_multistep): the guided forward, then
+        x_next = CX x + B x0 + P x0_prev from `coefs` fp32 [A2P_NMS, n_steps] (GaussianDiffusion._multistep_coefs).  `x0_prev`: the
+        previous step's pred_xstart [B, C, 1, T], or None (first order).  `known` fp32 / `known_mask` uint8 [B, C, 1, T]: held
+        elements, as sample_step_inpaint takes them, or both None.  Returns (x_next, pred_xstart)."""
+        x = x.to(torch.float32).contiguous()
+        if (known is None) != (known_mask is None):
+            raise _lib.A2PError("multistep step: known and known_mask go together")
+        if known is not None and (known.dtype != torch.float32 or known_mask.dtype != torch.uint8 or known.shape != x.shape
+                                  or known_mask.shape != x.shape or not known.is_contiguous() or not known_mask.is_contiguous()
+                                  or known.device != x.device or known_mask.device != x.device):
+            raise _lib.A2PError(f"multistep step: x {tuple(x.shape)} needs contiguous known fp32 and known_mask uint8 of that shape on "
+                                f"{x.device} (got {known.dtype} {tuple(known.shape)} on {known.device}, {known_mask.dtype} "
+                                f"{tuple(known_mask.shape)} on {known_mask.device})")
+        hist = None if x0_prev is None else x0_prev.to(device=x.device, dtype=torch.float32).contiguous()
+        if hist is not None and hist.shape != x.shape:
+            raise _lib.A2PError(f"multistep step: x0_prev {tuple(hist.shape)} does not match x {tuple(x.shape)}")
+        cf = coefs.to(device=x.device, dtype=torch.float32).contiguous()
+        self.prepare(x, y)
+        x_next, x0 = torch.empty_like(x), torch.empty_like(x)
+        sc = y["scale"].to(device=x.device, dtype=torch.float32).contiguous()
+        with _lib.on_device_of(x):
+            _lib.check(self._lib().a2p_sample_step_multistep(self._ctx, _lib.ptr(x), _lib.ptr(t_idx), _lib.ptr(timestep_map), cf.shape[1],
+                                                             _lib.ptr(sc), _lib.ptr(cf), _lib.ptr(hist), int(bool(clip_denoised)),
+                                                             _lib.ptr(known), _lib.ptr(known_mask), _lib.ptr(x_next), _lib.ptr(x0),
+                                                             _lib.current_stream(x.device)), "a2p_sample_step_multistep")
+        return x_next, x0
+
+    def sample_step_windowed_multistep(self, x, t_idx, timestep_map, coefs, y, x0_prev, clip_denoised: bool, starts, weights,
+                                       T_total: int):
+        """The windowed form of sample_step_multistep (include/a2p_hip.h a2p_sample_step_windowed_multistep): sample_step_windowed's
+        windows and outputs, `x0_prev` the previous step's window pred_xstart [R*W, C, 1, T_w] or None.
+        Returns (x_next, pred_xstart) of the windows and (x_next, pred_xstart) global [R, C, 1, T_total]."""
+        x = x.to(torch.float32).contiguous()
+        W = len(starts)
+        B, Cf, T_w = x.shape[0], x.shape[1], x.shape[-1]
+        R = B // W
+        hist = None if x0_prev is None else x0_prev.to(device=x.device, dtype=torch.float32).contiguous()
+        sc = y["scale"].to(device=x.device, dtype=torch.float32).contiguous()
+        if (B % W or sc.numel() != B or weights.dtype != torch.float32 or weights.numel() != W * T_w or not weights.is_contiguous()
+                or (hist is not None and hist.shape != x.shape)):
+            raise _lib.A2PError(f"windowed multistep step: x {tuple(x.shape)} over {W} windows needs scale [{B}], fp32 weights [{W}, {T_w}] "
+                                f"and x0_prev of x's shape (got {tuple(sc.shape)}, {tuple(weights.shape)}, "
+                                f"{None if hist is None else tuple(hist.shape)})")
+        cf = coefs.to(device=x.device, dtype=torch.float32).contiguous()
+        self.prepare(x, y)
+        x_next, x0 = torch.empty_like(x), torch.empty_like(x)
+        xg = torch.empty(R, Cf, 1, int(T_total), device=x.device, dtype=torch.float32)
+        x0g = torch.empty_like(xg)
+        with _lib.on_device_of(x):
+            _lib.check(self._lib().a2p_sample_step_windowed_multistep(
+                self._ctx, _lib.ptr(x), _lib.ptr(t_idx), _lib.ptr(timestep_map), cf.shape[1], _lib.ptr(sc), _lib.ptr(cf), _lib.ptr(hist),
+                int(bool(clip_denoised)), starts, _lib.ptr(weights), W, int(T_total), _lib.ptr(x_next), _lib.ptr(x0), _lib.ptr(xg),
+                _lib.ptr(x0g), _lib.current_stream(x.device)), "a2p_sample_step_windowed_multistep")
+        return x_next, x0, xg, x0g

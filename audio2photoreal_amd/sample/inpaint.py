@@ -16,10 +16,12 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..diffusion.gaussian_diffusion import GaussianDiffusion
 from ..sample_parallel import derive_seed, per_sample_noise
 from .generate import _replace_keyframes
 from .long_form import KEYFRAME_STEP, recording_frames
-from .recording import SAMPLE_RATE, SAMPLES_PER_FRAME, _audio_stats, _denoiser, _overlapped, can_share_features, prepare_recording
+from .recording import (MULTISTEP, SAMPLE_RATE, SAMPLES_PER_FRAME, _audio_stats, _check_sampler, _denoiser, _overlapped, can_share_features,
+                        prepare_recording)
 
 _SAMPLERS = {"ddim": _lib.SAMPLER_DDIM, "ddpm": _lib.SAMPLER_DDPM}
 
@@ -51,12 +53,21 @@ def inpaint_sample_loop(diffusion, model, y, known: torch.Tensor, known_mask: to
     `step_noise` as the plain loops take it.  Without `step_noise`, DDPM steps and DDIM steps with eta != 0 draw randn per step.
     The loop is GaussianDiffusion._loop: skip_timesteps, the finite checks and the fp32 escalation repeat work as in the plain loops.
 
-    Returns the final pred_xstart for "ddim" (its held elements are `known`'s bits) and the final sample for "ddpm".  PLMS, a model
-    without a2p_sample_step_inpaint, and wrong shapes, dtypes or devices raise A2PError before any GPU work."""
-    if sampler not in _SAMPLERS:
-        raise _lib.A2PError(f"inpainting runs 'ddim' or 'ddpm' (got {sampler!r}; PLMS is not supported)")
-    if not hasattr(model, "a2p_sample_step_inpaint"):
-        raise _lib.A2PError("inpainting needs this package's ClassifierFreeSampleModel (a2p_sample_step_inpaint)")
+    `sampler="dpm++2m"`: DPM-Solver++(2M) over the same steps (GaussianDiffusion.dpm_solver_sample_loop; a2p_sample_step_multistep
+    with known / known_mask): held elements replace x0 after the clamp, and the history of the second-order update is the previous
+    step's pred_xstart, held elements included.  It is deterministic: eta != 0 or `step_noise` is refused.
+
+    Returns the final pred_xstart for "ddim" (its held elements are `known`'s bits), the final sample for "ddpm" and "dpm++2m" (for
+    the latter the last step's pred_xstart bits).  PLMS, a model without a2p_sample_step_inpaint (a2p_sample_step_multistep for
+    "dpm++2m"), and wrong shapes, dtypes or devices raise A2PError before any GPU work."""
+    multistep = sampler == MULTISTEP
+    if sampler not in _SAMPLERS and not multistep:
+        raise _lib.A2PError(f"inpainting runs 'ddim', 'ddpm' or '{MULTISTEP}' (got {sampler!r}; PLMS is not supported)")
+    if multistep:
+        GaussianDiffusion.check_multistep_args(2, eta, step_noise)
+    need = "a2p_sample_step_multistep" if multistep else "a2p_sample_step_inpaint"
+    if not hasattr(model, need):
+        raise _lib.A2PError(f"inpainting needs this package's ClassifierFreeSampleModel ({need})")
     if not torch.is_tensor(known) or known.dim() != 4 or known.shape[2] != 1:
         raise _lib.A2PError(f"known must be a [B, C, 1, T] tensor (got {tuple(getattr(known, 'shape', ()))})")
     if known.dtype != torch.float32:
@@ -70,12 +81,26 @@ def inpaint_sample_loop(diffusion, model, y, known: torch.Tensor, known_mask: to
     for name, t in (("known_mask", known_mask), ("noise", noise)):
         if t is not None and t.device != device:
             raise _lib.A2PError(f"{name} is on {t.device}, known on {device}")
-    sid = _SAMPLERS[sampler]
     known_c = known.contiguous()
     mask_u8 = expand_mask(known_mask, B, Cf, T)
+    tmap = diffusion._timestep_map(device)
+    if multistep:
+        coefs = diffusion._multistep_coefs(device)
+
+        def ms_step(model, img, t, x0_prev, model_kwargs=None):
+            x_next, x0 = model.a2p_sample_step_multistep(img, t.to(torch.int64).contiguous(), tmap, coefs, model_kwargs["y"], x0_prev,
+                                                         clip_denoised, known_c, mask_u8)
+            return {"sample": x_next, "pred_xstart": x0}
+
+        def run_ms():
+            final = None
+            for out in diffusion._multistep_loop(ms_step, model, (B, Cf, 1, T), noise, {"y": y}, device, progress, skip_timesteps,
+                                                 None, False):
+                final = out
+            return final["sample"]
+        return diffusion._run_call(run_ms, model, device)
+    sid = _SAMPLERS[sampler]
     tables = diffusion._tables(device)
-    tmap = diffusion._timestep_map_tensor(device) if hasattr(diffusion, "_timestep_map_tensor") else \
-        diffusion._dev_cache.setdefault(("tmap", str(device)), torch.arange(diffusion.num_timesteps, device=device, dtype=torch.int64))
 
     def step(model, img, t, model_kwargs=None, noise=None, **_):
         if noise is None and (sid == _lib.SAMPLER_DDPM or eta != 0.0):
@@ -165,7 +190,8 @@ def _conditions(face_m, pose_m, fm, pm, audio, share_features: bool):
 
 
 def _inpaint_window(face, pose, audio, R: int, Tw: int, known_face, known_pose, mask, ids, seed: int,
-                    top_p: float, face_scale: float, pose_scale: float, overlap: bool, share_features: bool, known_kf=None):
+                    top_p: float, face_scale: float, pose_scale: float, overlap: bool, share_features: bool, known_kf=None,
+                    sampler: str = "ddim"):
     """Denoise one window of Tw frames with held elements: face and / or body (a part whose known tensor is None is not run).
     `known_kf`: None, or (normalised poses [R, Tw / 30, 104], bool mask [R, Tw / 30]) of keyframes the guide is forced to.
     Returns (face [R, C, 1, Tw] or None, body [R, C, 1, Tw] or None, keyframes [R, Tw / 30, 104] normalised, or None)."""
@@ -186,13 +212,13 @@ def _inpaint_window(face, pose, audio, R: int, Tw: int, known_face, known_pose, 
                   "scale": torch.full((R,), float(pose_scale), device=device)}
 
         def run_face():
-            return inpaint_sample_loop(face_d, face_m, y_face, known_face, mask, noise_face)
+            return inpaint_sample_loop(face_d, face_m, y_face, known_face, mask, noise_face, sampler=sampler)
 
         def run_body():
             guide_y = {**guide_cond, "keyframes": torch.zeros(R, nk, pm.nfeats, device=device)}
             kk = {} if known_kf is None else {"known": known_kf[0], "known_mask": known_kf[1]}
             y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p, **kk).to(device)
-            return inpaint_sample_loop(pose_d, pose_m, y_body, known_pose, mask, noise_pose)
+            return inpaint_sample_loop(pose_d, pose_m, y_body, known_pose, mask, noise_pose, sampler=sampler)
 
         face_s = body_s = None
         if known_face is not None and known_pose is not None and overlap:
@@ -212,7 +238,7 @@ def _motion(sample: torch.Tensor, mean, std) -> np.ndarray:
 def continue_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: int, previous: Dict[str, object], context_frames: int = 120,
                        num_repetitions: Optional[int] = None, top_p: float = 0.97, face_scale: float = 10.0, pose_scale: float = 2.0,
                        seed: int = 10, overlap: bool = True, share_features: bool = True,
-                       guide_context: bool = False) -> Dict[str, object]:
+                       guide_context: bool = False, sampler: str = "ddim") -> Dict[str, object]:
     """Continue a clip with new audio: face and body motion for `waveform` that starts from where `previous` ended.
 
     `previous`: a result of generate_from_recording or of an earlier continue_recording (its "face", "pose" and "audio" are read).
@@ -226,15 +252,17 @@ def continue_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: i
     keyframes from that audio alone (it is not told about the held frames).  `guide_context=True` tells it: the window's first
     P / 30 keyframes are the held frames 0, 30, ..., P - 30 verbatim, and their VQ tokens (the pose tokenizer's `encode`; it must
     be built with an encoder) are forced in the guide's draw, so the keyframes after them follow on from them.  Every random draw is a function of `seed` and the
-    repetition index, so the result does not depend on `overlap`; pass a new seed per chunk for fresh noise.
+    repetition index, so the result does not depend on `overlap`; pass a new seed per chunk for fresh noise.  `sampler`: "ddim" or
+    "dpm++2m" (inpaint_sample_loop), over the steps the diffusions were built with.
 
     Returns generate_from_recording's keys for the NEW frames only -- {"face": [R, T_new, 256], "pose": [R, T_new, 104],
     "keyframes": [R, T_new / 30, 104], "audio": float64 [2, T_new * 1600], "T": T_new, "sr": 48000} -- plus "context": P.
     Concatenating `previous` with it along frames gives the continued clip, and it is itself a valid `previous`.
 
     Raises A2PError before any GPU work when P is not a positive multiple of 30 or exceeds the previous clip, when P + T_new exceeds
-    the models' seq_len, when num_repetitions differs from previous's, when `previous` is not finite, and for what
-    prepare_recording refuses."""
+    the models' seq_len, when num_repetitions differs from previous's, when `previous` is not finite, for an unknown sampler and
+    for what prepare_recording refuses."""
+    _check_sampler(sampler)
     fm, pm = _check_models(face, pose, guide_context)
     prev_face, prev_pose, prev_audio = _result_arrays(previous, "previous")
     R, T_prev = prev_face.shape[:2]
@@ -274,7 +302,7 @@ def continue_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: i
         known_kf = (known_pose[:, :, 0, ::KEYFRAME_STEP].transpose(1, 2).contiguous(), kf_mask)
     face_s, body_s, kf = _inpaint_window(face, pose, audio, R, Tw, held(prev_face, stats["code_mean"], stats["code_std"]),
                                          known_pose, mask, (_CONT_UNIFORMS, _CONT_POSE, _CONT_FACE), seed, top_p, face_scale,
-                                         pose_scale, overlap, share_features, known_kf)
+                                         pose_scale, overlap, share_features, known_kf, sampler)
     kf = kf.cpu().numpy()[:, P // KEYFRAME_STEP:]
     return {"face": _motion(face_s, stats["code_mean"], stats["code_std"])[:, P:],
             "pose": _motion(body_s, stats["pose_mean"], stats["pose_std"])[:, P:],
@@ -298,7 +326,7 @@ def segment_window(T: int, start: int, end: int, seq_len: int):
 def regenerate_segment(face, pose, stats: Dict[str, np.ndarray], result: Dict[str, object], start_frame: int, end_frame: int,
                        parts: Sequence[str] = ("face", "pose"), top_p: float = 0.97, face_scale: float = 10.0, pose_scale: float = 2.0,
                        seed: int = 10, overlap: bool = True, share_features: bool = True,
-                       guide_context: bool = False) -> Dict[str, object]:
+                       guide_context: bool = False, sampler: str = "ddim") -> Dict[str, object]:
     """Re-roll frames [start_frame, end_frame) of a result and keep everything else.
 
     `result`: a dict with "face" [R, T, 256], "pose" [R, T, 104] and "audio" float64 [2, T * 1600] (generate_from_recording,
@@ -310,13 +338,15 @@ def regenerate_segment(face, pose, stats: Dict[str, np.ndarray], result: Dict[st
     window outside [start, end) is the result's pose at that frame, verbatim, and its VQ tokens are forced in the guide's draw (the
     pose tokenizer must be built with an encoder).  The draw inside the segment follows the forced keyframes before it, and the
     body model is conditioned on all of them, the ones after the segment included.  Random draws are functions of `seed` and the repetition index.
+    `sampler`: "ddim" or "dpm++2m" (inpaint_sample_loop), over the steps the diffusions were built with.
 
     Returns a copy of `result` in which only the listed parts' frames [start, end) are new: frames outside the segment and parts not
     listed are the input's arrays verbatim.  When the body is regenerated and result["keyframes"] is [R, T / 30, 104], its rows
     [start / 30, end / 30) are the new keyframes; other keyframe layouts are returned unchanged.
 
     Raises A2PError before any GPU work for bounds that are not multiples of 30 inside the clip with start < end, a segment longer
-    than the window, unknown or no parts, and a result that is not finite."""
+    than the window, unknown or no parts, an unknown sampler, and a result that is not finite."""
+    _check_sampler(sampler)
     fm, pm = _check_models(face, pose)
     res_face, res_pose, res_audio = _result_arrays(result, "result")
     R, T = res_face.shape[:2]
@@ -347,7 +377,7 @@ def regenerate_segment(face, pose, stats: Dict[str, np.ndarray], result: Dict[st
         known_kf = (known_pose[:, :, 0, ::KEYFRAME_STEP].transpose(1, 2).contiguous(), kf_mask)
     face_s, body_s, kf = _inpaint_window(face, pose, audio, R, Tw, known_face, known_pose, mask,
                                          (_REGEN_UNIFORMS, _REGEN_POSE, _REGEN_FACE), seed, top_p, face_scale, pose_scale, overlap,
-                                         share_features, known_kf)
+                                         share_features, known_kf, sampler)
     out = dict(result)
     if face_s is not None:
         new = np.array(result["face"], copy=True)

@@ -20,11 +20,12 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..diffusion.gaussian_diffusion import GaussianDiffusion
 from ..audio import resampled_length
 from ..sample_parallel import derive_seed, per_sample_noise
 from .generate import _guide_keyframes, _replace_keyframes
-from .recording import (BLOCK, MAX_FRAMES, SAMPLE_RATE, SAMPLES_PER_FRAME, _channels_last, _denoiser, _overlapped, can_share_features,
-                        prepare_recording)
+from .recording import (BLOCK, MAX_FRAMES, MULTISTEP, SAMPLE_RATE, SAMPLES_PER_FRAME, _channels_last, _check_sampler, _denoiser, _overlapped,
+                        can_share_features, prepare_recording)
 
 KEYFRAME_STEP = 30                    # the body model's keyframe step: window starts snap to it
 
@@ -129,24 +130,47 @@ def windowed_sample_loop(diffusion, model, plan: WindowPlan, R: int, y_windows, 
     `randn(R, C, 1, T_total)` per step.  The loop is GaussianDiffusion._loop: skip_timesteps, the first-step and end-of-call
     finite checks and the fp32 escalation repeat work as in the plain loops.
 
+    `sampler="dpm++2m"`: DPM-Solver++(2M) over the same steps (a2p_sample_step_windowed_multistep): the update is computed once per
+    global frame from the blend, with the history (the previous step's pred_xstart) read from the first covering window like x.
+    It is deterministic: eta != 0 or `step_noise` is refused.
+
     Returns the global [R, C, 1, T_total] result: the final pred_xstart for "ddim" (as ddim_sample_loop), the final sample for
-    "ddpm" (as p_sample_loop).  PLMS is refused."""
-    if sampler not in _SAMPLERS:
-        raise _lib.A2PError(f"windowed sampling runs 'ddim' or 'ddpm' (got {sampler!r}; PLMS is not supported)")
-    if not hasattr(model, "a2p_sample_step_windowed"):
-        raise _lib.A2PError("windowed sampling needs this package's ClassifierFreeSampleModel (a2p_sample_step_windowed)")
+    "ddpm" (as p_sample_loop) and for "dpm++2m" (the last step's pred_xstart bits).  PLMS is refused."""
+    multistep = sampler == MULTISTEP
+    if sampler not in _SAMPLERS and not multistep:
+        raise _lib.A2PError(f"windowed sampling runs 'ddim', 'ddpm' or '{MULTISTEP}' (got {sampler!r}; PLMS is not supported)")
+    if multistep:
+        GaussianDiffusion.check_multistep_args(2, eta, step_noise)
+    need = "a2p_sample_step_windowed_multistep" if multistep else "a2p_sample_step_windowed"
+    if not hasattr(model, need):
+        raise _lib.A2PError(f"windowed sampling needs this package's ClassifierFreeSampleModel ({need})")
     _lib.require_gpu_tensor(noise_global, "noise_global")
     if noise_global.dim() != 4 or noise_global.shape[0] != R or noise_global.shape[2] != 1 or noise_global.shape[3] != plan.T_total:
         raise _lib.A2PError(f"noise_global must be [{R}, C, 1, {plan.T_total}] (got {tuple(noise_global.shape)})")
     device = noise_global.device
     Cf = noise_global.shape[1]
-    sid = _SAMPLERS[sampler]
     starts = _starts_host(plan)
     weights = torch.from_numpy(plan.weights).to(device).contiguous()
-    tables = diffusion._tables(device)
-    tmap = diffusion._timestep_map_tensor(device) if hasattr(diffusion, "_timestep_map_tensor") else \
-        diffusion._dev_cache.setdefault(("tmap", str(device)), torch.arange(diffusion.num_timesteps, device=device, dtype=torch.int64))
+    tmap = diffusion._timestep_map(device)
     x_win = window_gather(noise_global.to(torch.float32), plan, channels_first=True)
+    if multistep:
+        coefs = diffusion._multistep_coefs(device)
+
+        def ms_step(model, img, t, x0_prev, model_kwargs=None):
+            x_next, x0, xg, x0g = model.a2p_sample_step_windowed_multistep(img, t.to(torch.int64).contiguous(), tmap, coefs,
+                                                                           model_kwargs["y"], x0_prev, clip_denoised, starts, weights,
+                                                                           plan.T_total)
+            return {"sample": x_next, "pred_xstart": x0, "sample_global": xg, "pred_xstart_global": x0g}
+
+        def run_ms():
+            final = None
+            for out in diffusion._multistep_loop(ms_step, model, (R * plan.W, Cf, 1, plan.T_w), x_win, {"y": y_windows}, device,
+                                                 progress, skip_timesteps, None, False):
+                final = out
+            return final["sample_global"]
+        return diffusion._run_call(run_ms, model, device)
+    sid = _SAMPLERS[sampler]
+    tables = diffusion._tables(device)
 
     def step(model, img, t, model_kwargs=None, noise=None, **_):
         if noise is None and (sid == _lib.SAMPLER_DDPM or eta != 0.0):
@@ -209,13 +233,14 @@ def _max_batch(*modules) -> int:
 def generate_from_long_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: int, num_repetitions: int = 1,
                                  top_p: float = 0.97, face_scale: float = 10.0, pose_scale: float = 2.0, seed: int = 10,
                                  min_overlap: int = 120, overlap: bool = True, share_features: bool = True,
-                                 chain_keyframes: bool = False) -> Dict[str, object]:
+                                 chain_keyframes: bool = False, sampler: str = "ddim") -> Dict[str, object]:
     """`generate_from_recording` for a recording of any length, over the windows of `plan_windows(T_total, seq_len, min_overlap)`.
 
     Per window (batch R*W): the audio front end / lip features, and guide transformer -> VQ keyframes.  The keyframes of two
     overlapping windows are predicted independently and may disagree on their shared frames; the body model's blend of the
     windows' x0 predictions absorbs that (the body follows a weighted mean of the two windows' keyframe-conditioned predictions).
-    The face and body loops are `windowed_sample_loop` ddim, on two HIP streams when `overlap`.
+    The face and body loops are `windowed_sample_loop` with `sampler` ("ddim" or "dpm++2m", over the steps the diffusions were
+    built with), on two HIP streams when `overlap`.
 
     `chain_keyframes=True` makes the overlapping keyframes agree instead: the guide runs window by window, and window w > 0 forces
     its keyframes inside window w - 1 to window w - 1's VQ tokens and takes window w - 1's keyframe rows there verbatim (window
@@ -234,6 +259,7 @@ def generate_from_long_recording(face, pose, stats: Dict[str, np.ndarray], wavef
     face_m, face_d = face
     pose_m, pose_d = pose
     fm, pm = _denoiser(face_m), _denoiser(pose_m)
+    _check_sampler(sampler)
     for name, m in (("face", fm), ("pose", pm)):
         if getattr(m, "audio_frontend", None) is None:
             raise _lib.A2PError(f"the {name} model has no audio front end: construct it with audio_frontend=\"native\"")
@@ -275,7 +301,7 @@ def generate_from_long_recording(face, pose, stats: Dict[str, np.ndarray], wavef
                   "scale": torch.full((B,), float(pose_scale), device=device)}
 
         def run_face():
-            return windowed_sample_loop(face_d, face_m, plan, R, y_face, noise_face)
+            return windowed_sample_loop(face_d, face_m, plan, R, y_face, noise_face, sampler=sampler)
 
         def run_body():
             if chain_keyframes and W > 1:
@@ -283,7 +309,7 @@ def generate_from_long_recording(face, pose, stats: Dict[str, np.ndarray], wavef
             else:
                 guide_y = {**guide_cond, "keyframes": torch.zeros(B, nk, pm.nfeats, device=device)}
                 y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p).to(device)
-            return windowed_sample_loop(pose_d, pose_m, plan, R, y_body, noise_pose)
+            return windowed_sample_loop(pose_d, pose_m, plan, R, y_body, noise_pose, sampler=sampler)
 
         if overlap:
             face_s, body_s = _overlapped(face, pose, run_face, run_body, device)

@@ -22,6 +22,13 @@ SAMPLE_RATE = 48_000                  # the models' audio rate
 BLOCK = 4 * SAMPLE_RATE               # the demo keeps whole 4 s blocks (demo/demo.py:169-171)
 SAMPLES_PER_FRAME = SAMPLE_RATE // 30
 MAX_FRAMES = 600                      # the denoisers' seq_len: null embeddings of 1998 audio tokens / 20 keyframes (20 s)
+MULTISTEP = "dpm++2m"                 # DPM-Solver++(2M): GaussianDiffusion.dpm_solver_sample_loop
+SAMPLERS = ("ddim", MULTISTEP)        # the `sampler` of the recording-level APIs
+
+
+def _check_sampler(sampler) -> None:
+    if sampler not in SAMPLERS:
+        raise _lib.A2PError(f"sampler must be one of {SAMPLERS} (got {sampler!r})")
 
 
 class PreparedRecording(NamedTuple):
@@ -125,7 +132,7 @@ def can_share_features(face_model, pose_model) -> bool:
 
 def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: int, num_repetitions: int = 1, top_p: float = 0.97,
                             face_scale: float = 10.0, pose_scale: float = 2.0, seed: int = 10, overlap: bool = True,
-                            share_features: bool = True, known_keyframes=None) -> Dict[str, object]:
+                            share_features: bool = True, known_keyframes=None, sampler: str = "ddim") -> Dict[str, object]:
     """`generate_results` (demo/demo.py:156-216) for `num_repetitions` samples of one recording.
 
     `face` / `pose`: (ClassifierFreeSampleModel, SpacedDiffusion) pairs as `sample.generate._setup_model` builds them, the pose
@@ -145,12 +152,17 @@ def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, 
     forced in the guide's draw, so the keyframes drawn after them follow on from them.  Bad frames, shapes or non-finite poses
     raise A2PError before any GPU work.
 
+    `sampler`: "ddim" (ddim_sample_loop) or "dpm++2m" (dpm_solver_sample_loop, DPM-Solver++(2M): second order, one model call per
+    step), for face and body alike.  The number of steps is the one each SpacedDiffusion was built with (e.g.
+    timestep_respacing="ddim20"); anything else raises A2PError before any GPU work.
+
     Returns {"face": [R, T, 256], "pose": [R, T, 104], "keyframes": [R, T / 30, 104] (un-normalised with the code_* / pose_*
     statistics: * std + mean), "audio": the un-normalised dual audio float64 [2, Lc], "T", "sr": 48000}."""
     from ..model.audio_frontend import NativeAudioFrontend
     face_m, face_d = face
     pose_m, pose_d = pose
     fm, pm = _denoiser(face_m), _denoiser(pose_m)
+    _check_sampler(sampler)
     for name, m in (("face", fm), ("pose", pm)):
         if getattr(m, "audio_frontend", None) is None:
             raise _lib.A2PError(f"the {name} model has no audio front end: construct it with audio_frontend=\"native\"")
@@ -192,14 +204,17 @@ def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, 
         y_body = {**body_cond, "mask": torch.ones(R, 1, 1, T, dtype=torch.bool, device=device),
                   "scale": torch.full((R,), float(pose_scale), device=device)}
 
+        def loop(d):
+            return d.ddim_sample_loop if sampler == "ddim" else d.dpm_solver_sample_loop
+
         def run_face():
-            return face_d.ddim_sample_loop(face_m, (R, fm.nfeats, 1, T), noise=noise_face, clip_denoised=False, model_kwargs={"y": y_face})
+            return loop(face_d)(face_m, (R, fm.nfeats, 1, T), noise=noise_face, clip_denoised=False, model_kwargs={"y": y_face})
 
         def run_body():
             guide_y = {**guide_cond, "keyframes": torch.zeros(R, nk, pm.nfeats, device=device)}
             kk = {} if known is None else {"known": known[0].expand(R, -1, -1), "known_mask": known[1].expand(R, -1)}
             y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p, **kk).to(device)
-            return pose_d.ddim_sample_loop(pose_m, (R, pm.nfeats, 1, T), noise=noise_pose, clip_denoised=False, model_kwargs={"y": y_body})
+            return loop(pose_d)(pose_m, (R, pm.nfeats, 1, T), noise=noise_pose, clip_denoised=False, model_kwargs={"y": y_body})
 
         if overlap:
             face_s, body_s = _overlapped(face, pose, run_face, run_body, device)

@@ -157,6 +157,31 @@ int a2p_sample_step_windowed(a2p_ctx* ctx, int32_t sampler, const float* x_win, 
                              const float* noise_global, float eta, int32_t clip_denoised, const int32_t* win_starts_host,
                              const float* win_weights, int32_t W, int32_t T_total, float* x_next_win, float* x0_win,
                              float* x_global, float* x0_global, void* stream);
+
+/* ---- DPM-Solver++(2M): multistep sampling in fewer steps (GaussianDiffusion.dpm_solver_sample_loop) -----
+ * coefs fp32 [A2P_NMS, n_steps] rows in the order of a2p_ms_coef_id, built by the host in float64 and cast
+ * (GaussianDiffusion.multistep_table).  Per element, after the guided output g = u + scale[b] * (a - u) (non-finite g ORs the
+ * a2p_check_finite flag), x0 = g clamped to [-1, 1] when clip_denoised, and x0 = known where known_mask != 0 (a2p_sample_step_inpaint's
+ * rule): pred_xstart = x0 and, with t = t_idx[b],
+ *   t == 0            x_next = x0
+ *   x0_prev == NULL   x_next = fmaf(CX[t], x, B1[t] * x0)
+ *   otherwise         x_next = fmaf(CX[t], x, fmaf(B2[t], x0, P2[t] * x0_prev))
+ * x0_prev [B, nfeats, 1, T] is the previous step's pred_xstart (NULL on the first step of a call).  known and known_mask are both
+ * NULL (plain step) or both set ([B, nfeats, 1, T] fp32 / uint8).  x_next may alias x; pred_xstart must not alias x0_prev
+ * (A2P_ERR_ARG). */
+enum a2p_ms_coef_id { A2P_MS_CX = 0, A2P_MS_B1, A2P_MS_B2, A2P_MS_P2, A2P_NMS };
+int a2p_sample_step_multistep(a2p_ctx* ctx, const float* x, const int64_t* t_idx, const int64_t* timestep_map, int32_t n_steps,
+                              const float* scale, const float* coefs, const float* x0_prev, int32_t clip_denoised,
+                              const float* known, const uint8_t* known_mask, float* x_next, float* pred_xstart, void* stream);
+/* The windowed form (a2p_sample_step_windowed's windows, blend and outputs): the update above is computed once per global frame
+ * from the blended x0, with x and x0_prev_win [R*W, nfeats, 1, T_w] (or NULL) read from the first covering window; the same
+ * bits go to every window copy and to x_global / x0_global when non-NULL.  x_next_win may alias x_win; x0_win and x0_global
+ * must not alias x0_prev_win (A2P_ERR_ARG). */
+int a2p_sample_step_windowed_multistep(a2p_ctx* ctx, const float* x_win, const int64_t* t_idx, const int64_t* timestep_map,
+                                       int32_t n_steps, const float* scale, const float* coefs, const float* x0_prev_win,
+                                       int32_t clip_denoised, const int32_t* win_starts_host, const float* win_weights, int32_t W,
+                                       int32_t T_total, float* x_next_win, float* x0_win, float* x_global, float* x0_global,
+                                       void* stream);
 /* Windows of a per-frame signal: channels last, src [reps, T_total * k, ch] -> dst [reps * W, T_w * k, ch] (k samples of ch
  * channels per frame, e.g. the dual audio: k = 1600, ch = 2); channels_first (k = 1), src [reps, ch, T_total] -> dst
  * [reps * W, ch, T_w].  dst[r * W + w] is the slice of src[r] from frame win_starts_host[w] (same rules as above). */
@@ -173,6 +198,10 @@ int a2p_p_mean_variance(const float* model_out, const float* x, const int64_t* t
 int a2p_ddim_update(const float* pred_xstart, const float* x, const int64_t* t_idx, const float* tables,
                     int32_t n_steps, const float* noise, float eta, int32_t batch, int64_t per_sample,
                     float* sample, void* stream);
+/* DPM-Solver++(2M) update of a2p_sample_step_multistep from pred_xstart (x, pred_xstart, x0_prev, sample all
+ * [batch, per_sample]; x0_prev NULL: first order).  sample may alias x; pred_xstart must not alias x0_prev (A2P_ERR_ARG). */
+int a2p_multistep_update(const float* x, const float* pred_xstart, const float* x0_prev, const int64_t* t_idx,
+                         const float* coefs, int32_t n_steps, int32_t batch, int64_t per_sample, float* sample, void* stream);
 /* p_sample update (gaussian_diffusion.py:470-476): mean + [t!=0] exp(.5 logvar) noise. */
 int a2p_p_sample_update(const float* mean, const int64_t* t_idx, const float* tables, int32_t n_steps,
                         const float* noise, int32_t batch, int64_t per_sample, float* sample, void* stream);
