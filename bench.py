@@ -7,14 +7,16 @@ restored noise), classifier-free guidance (2 denoiser passes per step), batch 8 
 Synthetic weights + inputs (no checkpoints/datasets offline).  One "step" = one p_sample:
 2 x FiLMTransformer forward over 8 samples + guidance + posterior update.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision fp16|bf16|fp32] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision fp16|bf16|fp32] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Defaults: N=1, K=200 timed steps behind W=20 warm-up steps, in one timed region (--repeats R: R regions of K steps, the median
-is reported); `ms_per_step` = region time / K.  The whole default run, legs, parity and CPU baseline included, takes ~35 s on
-the GPU box.  --dump-outputs DIR writes the outputs of the last timed step as .npy files (dump_outputs).
+is reported); `ms_per_step` = region time / K.  --dump-outputs DIR writes the outputs of the last timed step as .npy files
+(dump_outputs).
 
-The ONE JSON line rank 0 prints carries, next to the contract fields:
+A plain run does only what the headline needs: set up, warm up, time the steps, dump the outputs if asked, print the line.
+Everything else the benchmark measures runs with --full only (each part can still be left out with its --no-* switch); a --full
+run takes ~30 s more on an MI355X.  With --full the ONE JSON line rank 0 prints carries, next to the contract fields:
   roofline      dominant kernel class, algorithmic FLOPs / measured launch time (HIP events on the launch stream) vs the bf16 peak
   cpu_baseline  the oracle (CPU port of the reference algorithm) timed on this box's host cores, bounded sample
   parity        all three modes (fp16 = benchmarked, bf16, fp32 = parity mode) against that same oracle run at the bench shape
@@ -22,6 +24,8 @@ The ONE JSON line rank 0 prints carries, next to the contract fields:
   legs          the same workload with bf16 operands ("bf16") and in the exact-fp32 parity mode ("fp32"), and the other north-star
                 shapes on this GPU: face B=32 ("b32"), the body model B=16 with keyframes ("body") and the reference's CPU-runnable
                 config 0 shape ("cfg0")
+  box           device properties, an HBM copy probe, rocm-smi, KFD topology and VBIOS of this box
+  under_load    board power / clock / temperature while extra steps run
 
 Multi-GPU = sample parallel: rank r denoises the global samples shard_bounds(N*B, N, r) with its own
 replica, no per-step communication (weak scaling); one all_gather (sample_parallel.gather_samples; RCCL over xGMI) of the
@@ -929,15 +933,19 @@ def main():
     ap.add_argument("--total-samples", type=int, default=0,
                     help="STRONG scaling (BASELINE configs[3]): a fixed number of samples split over --gpus ranks (contiguous blocks; a rank may "
                          "hold none) instead of --batch samples per GPU; the pose model then steps its ddim100 chain")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else: per-kernel timing and roofline, the box record, power / clock "
+                         "under load, the CPU baseline, parity against the oracle and the other precisions and shapes (legs); "
+                         "the --no-* switches below leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (and with it the parity record)")
     ap.add_argument("--cpu-all-cores", action="store_true",
-                    help="also time the oracle with EVERY host CPU as a torch thread (one sample x one step; ~8 minutes on a 256-CPU box, where it "
-                         "thrashes: the default line quotes profiles/r06_cpu_all_cores.json instead)")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity legs (the oracle still times the cpu_baseline)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the face B=32 and body B=16 sub-records")
-    ap.add_argument("--chain-steps", type=int, default=1000, help="length of the bf16-vs-fp32 drift chain (0 = skip)")
-    ap.add_argument("--write-parity", default=None, help="also write the parity record to this JSON file (profiles/r02_parity.json)")
+                    help="with --full: also time the oracle with EVERY host CPU as a torch thread (one sample x one step; ~8 minutes on a 256-CPU "
+                         "box, where it thrashes: the line quotes profiles/r06_cpu_all_cores.json instead)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel timing, roofline and under-load probe")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity legs (the oracle still times the cpu_baseline)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the bf16, fp32, face B=32, body B=16 and config-0 sub-records")
+    ap.add_argument("--chain-steps", type=int, default=1000, help="with --full: length of the bf16-vs-fp32 drift chain (0 = skip)")
+    ap.add_argument("--write-parity", default=None, help="with --full: also write the parity record to this JSON file (profiles/r02_parity.json)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step returned (p_sample / ddim_sample: sample, pred_xstart; "
                          "N > 1: the gathered samples) as DIR/<name>.npy, float32, at most 64 MB in all (larger outputs: a fixed seeded "
@@ -947,6 +955,8 @@ def main():
         ap.error("--steps and --repeats must be at least 1")
     if a.dump_outputs and a.pipeline:
         ap.error("--dump-outputs covers the step benchmark, not --pipeline")
+    if (a.cpu_all_cores or a.write_parity) and not a.full:
+        ap.error("--cpu-all-cores and --write-parity belong to the --full run")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` started directly (the form the driver uses at N=1): launch the N ranks ourselves, one process per
@@ -1056,9 +1066,11 @@ def main():
         dumped = dump_outputs(a.dump_outputs, {"sample": allx} if world > 1 else
                               {"sample": case.last_out["sample"], "pred_xstart": case.last_out["pred_xstart"]})
 
+    # ---- --full only: everything below measures more than the headline ----
+    kernel_timing = rank == 0 and a.full and not a.no_kernel_timing
     kernels, roofline = {}, None
-    under_load = load_probe(case, dev) if rank == 0 and not a.no_kernel_timing else None   # after the timed regions (not under a profiler): power / clock / temperature while the steps run
-    if rank == 0 and not a.no_kernel_timing:
+    under_load = load_probe(case, dev) if kernel_timing else None   # after the timed regions (not under a profiler): power / clock / temperature while the steps run
+    if kernel_timing:
         kernels, roofline = kernel_breakdown(case, min(a.steps, 5))
         if "chain" in kernels:
             roofline["chain_workgroup_waves"] = chain_workgroup_waves(case)
@@ -1080,7 +1092,7 @@ def main():
 
     cpu = parity = None
     legs = {}
-    if rank == 0 and world == 1:   # reported at N=1 only (other ranks would idle in the final barrier)
+    if rank == 0 and world == 1 and a.full:   # reported at N=1 only (other ranks would idle in the final barrier)
         if not a.no_cpu_baseline and a.model == "face":
             cpu, parity = cpu_and_parity(case, dev, want_parity=not a.no_parity, chain_steps=a.chain_steps, all_cores_live=a.cpu_all_cores)
             if parity and a.write_parity:
@@ -1133,7 +1145,7 @@ def main():
             "collectives": ({"backend": dist.get_backend(), "ranks": dist.get_world_size(), "gather": os.environ.get("A2P_GATHER", "ring"),
                              "gather_rows": int(allx.shape[0]), "gather_bytes_per_rank": int(mine.numel() * mine.element_size())}
                             if world > 1 else None),
-            "box": box_record(dev), "under_load": under_load,
+            "box": box_record(dev) if a.full else None, "under_load": under_load,
             "roofline": roofline, "kernels": kernels, "cpu_baseline": cpu, "parity": parity, "legs": legs or None,
             "dump_outputs": dumped and {"dir": a.dump_outputs, "arrays": dumped},
         }

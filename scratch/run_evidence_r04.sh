@@ -32,5 +32,5 @@ rm -rf $O/pmcs_$TAG $O/pmcf_$TAG $O/pmcw_$TAG $O/prof_$TAG $O/prof_${TAG}_b32 $O
 cd $R
 head -6 $O/${TAG}_kernel_stats.csv | cut -c1-140; tail -3 $O/pmc_traffic_$TAG.txt; cat $O/${TAG}_pmc_sq_counters.txt | cut -c1-260
 # un-profiled bench lines
-timeout -k 5 900 python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 600 $O/${TAG}_bench_default.json
+timeout -k 5 900 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 600 $O/${TAG}_bench_default.json
 timeout -k 5 600 python bench.py --pipeline --batch 8 > $O/${TAG}_pipeline.json 2> $O/${TAG}_pipeline.err; tail -c 800 $O/${TAG}_pipeline.json

@@ -43,4 +43,4 @@ for b in 8 32; do
   echo "B=$b power samples: $(wc -l < $O/${TAG}_power_b$b.txt)"; tail -4 $O/${TAG}_power_b$b.txt | cut -c1-400
 done
 # un-profiled bench line
-timeout -k 5 900 python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 900 $O/${TAG}_bench_default.json
+timeout -k 5 900 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 900 $O/${TAG}_bench_default.json

@@ -5,7 +5,7 @@ O=$R/gpurun_out; mkdir -p $O
 cd $R
 line() {  # $1 = tag, rest = env + bench args
   local tag=$1; shift
-  env "$@" timeout -k 5 300 python bench.py --no-cpu-baseline --no-parity --no-legs --warmup 10 $BARGS > $O/slow_probe.json 2> $O/slow_probe.err
+  env "$@" timeout -k 5 300 python bench.py --full --no-cpu-baseline --no-parity --no-legs --warmup 10 $BARGS > $O/slow_probe.json 2> $O/slow_probe.err
   python - "$tag" <<PY
 import json, sys
 try:

@@ -6,7 +6,9 @@ import json
 import os
 import subprocess
 import sys
+import time
 
+import numpy as np
 import pytest
 import torch
 
@@ -264,6 +266,34 @@ def test_bench_gpus_2_launches_its_own_ranks():
     assert line["n_gpus"] == 2 and line["collectives"]["ranks"] == 2 and line["config"]["global_batch"] == 4
     assert line["gather_ms"] is not None and line["value"] > 0 and line["steps"] == 4
     record("bench_gpus2_self_launch", value=float(line["value"]), gather_ms=float(line["gather_ms"]))
+
+
+# ----------------------------------------------------------------------------- a plain bench run times the headline alone; --full adds the rest
+def test_plain_bench_run_is_the_headline_alone_and_full_adds_the_records(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` sets up, warms up, times the steps, dumps and prints the line: no kernel timing,
+    box record, under-load probe, CPU baseline, parity or legs.  `--full` adds them after the same timed steps, so both runs dump the
+    same outputs bit for bit (here without the CPU baseline and the legs, which take minutes)."""
+    args = ["--gpus", "1", "--steps", "5", "--warmup", "2"]
+    lines, wall = {}, {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-legs"])):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + args + extra + ["--dump-outputs", str(tmp_path / mode)]
+        t0 = time.perf_counter()
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        wall[mode] = time.perf_counter() - t0
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines[mode] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    for line in lines.values():
+        assert line["unit"] == "steps/s" and line["higher_is_better"] is True and line["dtype"] == "fp16" and line["steps"] == 5
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and set(line["dump_outputs"]["arrays"]) == {"sample", "pred_xstart"}
+    plain, full = lines["plain"], lines["full"]
+    assert plain["kernels"] == {} and all(plain[k] is None for k in ("roofline", "box", "under_load", "cpu_baseline", "parity", "legs"))
+    assert full["roofline"]["kernel"] in full["kernels"] and isinstance(full["box"], dict) and full["under_load"]
+    assert full["cpu_baseline"] is None and full["legs"] is None
+    for name in ("sample", "pred_xstart"):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert np.array_equal(a, b), name
+    over = {m: wall[m] - (5 + 2) * lines[m]["ms_per_step"] / 1e3 for m in wall}   # (steps + warm-up) x ms_per_step
+    record("bench_plain_vs_full", plain_s_outside_steps=float(over["plain"]), full_s_outside_steps=float(over["full"]))
 
 
 # ----------------------------------------------------------------------------- ADVICE round 5 (medium): a 16-bit OVERFLOW escalates too

@@ -689,3 +689,11 @@ def test_bench_dump_outputs_stays_within_64_mb_with_a_fixed_sample(tmp_path):
         a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
         assert np.array_equal(a, b) and a.size == runs[0][k]["sampled_elements"] > 0
         assert np.isin(a[:1000], v.numpy()).all()                  # sampled values, not recomputed ones
+
+
+def test_bench_options_of_the_full_run_need_full():
+    """`--write-parity` and `--cpu-all-cores` only mean something in a `--full` run: without it bench.py refuses them before it starts."""
+    import subprocess
+    for opt in (["--write-parity", "parity.json"], ["--cpu-all-cores"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + opt, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--full" in r.stderr, r.stderr[-2000:]
