@@ -43,6 +43,7 @@ EXPORTS = (
     "a2p_frontend_encode_audio", "a2p_frontend_encode_lip", "a2p_resample", "a2p_dual_audio",
     "a2p_sample_step_windowed", "a2p_window_gather", "a2p_sample_step_inpaint", "a2p_guide_generate_forced", "a2p_vq_encode",
     "a2p_sample_step_multistep", "a2p_sample_step_windowed_multistep", "a2p_multistep_update",
+    "a2p_eval_moments", "a2p_eval_pair_dist", "a2p_eval_gemm_f64", "a2p_eval_eigh",
 )
 
 
@@ -83,6 +84,9 @@ class A2PPrecisionWarning(UserWarning):
 # the maximum alone does not decide, and no single bound above 13.5 closes it (tests/test_envelope_hip.py VIOLATIONS)
 LOGIT_ENVELOPE_FP16 = 20.0
 ERR_NONFINITE = -5     # include/a2p_hip.h A2P_ERR_NONFINITE (a2p_check_finite)
+ERR_NOCONVERGE = -6    # A2P_ERR_NOCONVERGE (a2p_eval_eigh)
+EVAL_MAX_CHANNELS = 256                # A2P_EVAL_MAX_CHANNELS
+EVAL_NSPLIT, EVAL_XV_PARTIALS = 16, 256   # A2P_EVAL_NSPLIT, A2P_EVAL_XV_PARTIALS (A2P_EVAL_MOMENTS_WS_DOUBLES)
 RESAMPLE_MAX_TABLE_BYTES = 16 << 20   # include/a2p_hip.h A2P_RESAMPLE_MAX_TABLE_BYTES
 RESAMPLE_MAX_CHANNELS = 64            # A2P_RESAMPLE_MAX_CHANNELS
 DUAL_AUDIO_SCRATCH = 257              # A2P_DUAL_AUDIO_SCRATCH (floats)
@@ -159,6 +163,10 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_sample_step_multistep": [vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp],
         "a2p_sample_step_windowed_multistep": [vp, vp, vp, vp, i32, vp, vp, vp, i32, C.POINTER(i32), vp, i32, i32, vp, vp, vp, vp, vp],
         "a2p_multistep_update": [vp, vp, vp, vp, vp, i32, i32, i64, vp, vp],
+        "a2p_eval_moments": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+        "a2p_eval_pair_dist": [vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp],
+        "a2p_eval_gemm_f64": [i32, vp, i64, i64, vp, vp, i64, i64, vp, vp],
+        "a2p_eval_eigh": [vp, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_double), vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

@@ -30,6 +30,7 @@
 #include "kernels_audio.h"
 #include "kernels_chain.h"
 #include "kernels_chain4.h"
+#include "kernels_eval.h"
 #include "kernels_gemm.h"
 #include "kernels_inpaint.h"
 #include "kernels_misc.h"
@@ -1002,3 +1003,4 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_lib_run.h"
 #include "a2p_guide.h"
 #include "a2p_frontend.h"
+#include "a2p_eval.h"

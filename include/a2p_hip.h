@@ -36,6 +36,7 @@ extern "C" {
 #define A2P_ERR_HIP (-3)      /* HIP runtime error */
 #define A2P_ERR_NOWEIGHT (-4) /* unknown / missing / mis-sized parameter (reference: load_model asserts, utils/model_util.py:30-38) */
 #define A2P_ERR_NONFINITE (-5) /* a2p_check_finite: a denoiser output held inf / nan (16-bit operand overflow, or non-finite inputs / weights) */
+#define A2P_ERR_NOCONVERGE (-6) /* a2p_eval_eigh: the Jacobi sweeps hit their cap */
 
 #define A2P_FACE 0
 #define A2P_POSE 1
@@ -431,6 +432,40 @@ int a2p_frontend_encode_audio(a2p_frontend_ctx* ctx, const float* audio, int32_t
 /* encode_lip: out [batch, n_tokens, cond_dim + lip_out] = cat(cond_in [batch, n_tokens, cond_dim], interpolate(lip(audio[..., 0]))). */
 int a2p_frontend_encode_lip(a2p_frontend_ctx* ctx, const float* audio, int32_t batch, int64_t samples, const float* cond_in,
                             int32_t n_tokens, int32_t cond_dim, float* out, void* stream);
+
+/* ---- motion evaluation (reference utils/eval.py; audio2photoreal_amd/evaluate.py) -------------------------------------
+ * Everything is fp64.  x is a motion batch [S, C, T] channels-first (the samplers' [S, C, 1, T] is the same memory), fp32
+ * (x_f64 = 0) or fp64 (x_f64 = 1); 1 <= C <= A2P_EVAL_MAX_CHANNELS.  No floating-point atomics: results are the same bits on
+ * every run.  nonfinite: one device int the kernels OR into (1: a non-finite input element, 2: a pair index out of range);
+ * the caller zeroes it and reads it back.
+ *
+ * a2p_eval_moments (T >= 2): over the N = S T frames x[s, :, t], mu [C] and cov [C, C] normalised by N - 1 (np.cov), over the
+ * S (T - 1) in-sequence velocities x[s, :, t + 1] - x[s, :, t], mu_v and cov_v.  Second moments are centred (two passes) and
+ * the per-range partials are merged in a fixed order.  sums[0] = sum over (s, c) of the variance along T (ddof 0),
+ * sums[1] = sum over the B C T elements of one repetition of the variance across the reps repetitions x[r B + b] (S = reps B;
+ * reps = 0 skips it and writes 0).  workspace: A2P_EVAL_MOMENTS_WS_DOUBLES(C) doubles. */
+#define A2P_EVAL_MAX_CHANNELS 256
+#define A2P_EVAL_NSPLIT 16
+#define A2P_EVAL_XV_PARTIALS 256
+#define A2P_EVAL_MOMENTS_WS_DOUBLES(C) ((int64_t)A2P_EVAL_NSPLIT * (C) * (C) + (C) + A2P_EVAL_XV_PARTIALS)
+int a2p_eval_moments(const void* x, int32_t x_f64, int32_t S, int32_t C, int32_t T, int32_t reps, double* mu, double* cov,
+                     double* mu_v, double* cov_v, double* sums, double* workspace, int32_t* nonfinite, void* stream);
+/* dist[i] = || frame idx1[i] - frame idx2[i] ||_2 (times pairs), frame f = x[f / T, :, f % T]: the rows of the reference's
+ * transpose(0, 1, 3, 2).reshape(-1, C), read without a transposed copy.  idx1 / idx2: device int64. */
+int a2p_eval_pair_dist(const void* x, int32_t x_f64, int32_t S, int32_t C, int32_t T, const int64_t* idx1, const int64_t* idx2,
+                       int64_t times, double* dist, int32_t* nonfinite, void* stream);
+/* c[i][j] = sum_k a[i a_rs + k a_cs] d[k] b[k b_rs + j b_cs] for n x n fp64 (d NULL: no scaling; the strides express transposes),
+ * n <= A2P_EVAL_MAX_CHANNELS; c must not alias an input. */
+int a2p_eval_gemm_f64(int32_t n, const double* a, int64_t a_rs, int64_t a_cs, const double* d, const double* b, int64_t b_rs,
+                      int64_t b_cs, double* c, void* stream);
+/* Symmetric eigensolver: cyclic Jacobi with round-robin ordering, one workgroup, n <= A2P_EVAL_MAX_CHANNELS.  a [n, n] (read as
+ * 0.5 (a + a^T)) -> eigenvalues w [n] (unsorted) and, when q is not NULL, eigenvectors q [n, n] (column j belongs to w[j]:
+ * a = q diag(w) q^T).  Stops when ||offdiag||_F <= 1e-15 ||a||_F; sweeps_host / off_host (host, may be NULL) receive the sweeps
+ * used and that final norm.  Synchronises `stream`.  A2P_ERR_NOCONVERGE when the sweep cap (40) is hit, A2P_ERR_NONFINITE for a
+ * non-finite input.  workspace: A2P_EVAL_EIGH_WS_DOUBLES(n) doubles of device memory. */
+#define A2P_EVAL_EIGH_WS_DOUBLES(n) ((int64_t)((n) + ((n) & 1)) * ((n) + ((n) & 1)) + 2)
+int a2p_eval_eigh(const double* a, int32_t n, double* w, double* q, double* workspace, int32_t* sweeps_host, double* off_host,
+                  void* stream);
 
 #ifdef __cplusplus
 }
