@@ -44,6 +44,7 @@ EXPORTS = (
     "a2p_sample_step_windowed", "a2p_window_gather", "a2p_sample_step_inpaint", "a2p_guide_generate_forced", "a2p_vq_encode",
     "a2p_sample_step_multistep", "a2p_sample_step_windowed_multistep", "a2p_multistep_update",
     "a2p_eval_moments", "a2p_eval_pair_dist", "a2p_eval_gemm_f64", "a2p_eval_eigh",
+    "a2p_resample_channels", "a2p_conversation_audio",
 )
 
 
@@ -90,6 +91,8 @@ EVAL_NSPLIT, EVAL_XV_PARTIALS = 16, 256   # A2P_EVAL_NSPLIT, A2P_EVAL_XV_PARTIAL
 RESAMPLE_MAX_TABLE_BYTES = 16 << 20   # include/a2p_hip.h A2P_RESAMPLE_MAX_TABLE_BYTES
 RESAMPLE_MAX_CHANNELS = 64            # A2P_RESAMPLE_MAX_CHANNELS
 DUAL_AUDIO_SCRATCH = 257              # A2P_DUAL_AUDIO_SCRATCH (floats)
+CONVERSATION_SCRATCH = 514            # A2P_CONVERSATION_SCRATCH (floats)
+NORMALIZE_NONE, NORMALIZE_PEAK = 0, 1 # A2P_NORMALIZE_*
 WINDOW_MAX = 256                      # A2P_WINDOW_MAX
 
 
@@ -167,6 +170,8 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_eval_pair_dist": [vp, i32, i32, i32, i32, vp, vp, i64, vp, vp, vp],
         "a2p_eval_gemm_f64": [i32, vp, i64, i64, vp, vp, i64, i64, vp, vp],
         "a2p_eval_eigh": [vp, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_double), vp],
+        "a2p_resample_channels": [vp, i64, i32, i32, i32, vp, i32, i32, i32, vp, vp],
+        "a2p_conversation_audio": [vp, i64, i64, i32, vp, i32, C.POINTER(C.c_double), i32, vp, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

@@ -1618,6 +1618,72 @@ extern "C" int a2p_dual_audio(const float* mono, int64_t len, float* peak_scratc
   return 0;
 }
 
+extern "C" int a2p_resample_channels(const float* in, int64_t len, int32_t channels, int32_t orig_freq, int32_t new_freq,
+                                     const float* table, int32_t n_phase, int32_t n_taps, int32_t width, float* out, void* stream) {
+  ARG(in && out, "resample_channels: null argument");
+  ARG(len >= 1 && len <= ((int64_t)1 << 40), "resample_channels: bad input length %lld", (long long)len);
+  ARG(channels >= 1 && channels <= A2P_RESAMPLE_MAX_CHANNELS, "resample_channels: channels=%d outside [1, %d]", channels,
+      A2P_RESAMPLE_MAX_CHANNELS);
+  ARG(orig_freq > 0 && new_freq > 0, "resample_channels: rates must be positive (orig=%d new=%d)", orig_freq, new_freq);
+  hipStream_t s = (hipStream_t)stream;
+  if (orig_freq == new_freq) {
+    const int64_t total = (int64_t)channels * len;
+    resample_channels_kernel<<<grid_for(total), 256, 0, s>>>(in, len, channels, 1, 1, nullptr, 0, 0, len, total, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  const int64_t g = gcd64(orig_freq, new_freq);
+  const int o = (int)(orig_freq / g), n = (int)(new_freq / g);
+  ARG(table, "resample_channels: null table");
+  ARG(n_phase == n && width >= 0 && n_taps == 2 * (int64_t)width + o,
+      "resample_channels: table [%d, %d] with width %d does not fit rates %d -> %d (want [%d, 2 * width + %d])", n_phase, n_taps, width,
+      orig_freq, new_freq, n, o);
+  ARG((int64_t)n_phase * n_taps * (int64_t)sizeof(float) <= A2P_RESAMPLE_MAX_TABLE_BYTES, "resample_channels: table of %lld bytes exceeds %d",
+      (long long)n_phase * n_taps * (long long)sizeof(float), A2P_RESAMPLE_MAX_TABLE_BYTES);
+  const int64_t out_len = (n * len + o - 1) / o;
+  const int64_t total = (int64_t)channels * out_len;
+  resample_channels_kernel<<<grid_for(total), 256, 0, s>>>(in, len, channels, o, n, table, n_taps, width, out_len, total, out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int a2p_conversation_audio(const float* channels, int64_t ld, int64_t len, int32_t normalize, float* peak_scratch,
+                                      int32_t people, const double* stats_host, int32_t reps, float* out, void* stream) {
+  ARG(channels && stats_host && out, "conversation_audio: null argument");
+  ARG(len >= 1 && len <= ld && ld <= ((int64_t)1 << 40) && reps >= 1, "conversation_audio: len=%lld ld=%lld reps=%d", (long long)len,
+      (long long)ld, reps);
+  ARG(people >= 1 && people <= 3, "conversation_audio: people=%d is not a bitmask of persons 0 and 1", people);
+  ARG(normalize == A2P_NORMALIZE_NONE || normalize == A2P_NORMALIZE_PEAK, "conversation_audio: normalize=%d", normalize);
+  for (int p = 0; p < 2; ++p) {
+    if (!(people >> p & 1)) continue;
+    const double* st = stats_host + 3 * p;
+    ARG(st[2] > 0.0 && isfinite(st[2]) && isfinite(st[0]) && isfinite(st[1]), "conversation_audio: bad statistics of person %d (std %g, mean %g %g)",
+        p, st[2], st[0], st[1]);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float peak[2] = {0.f, 0.f};
+  if (normalize == A2P_NORMALIZE_PEAK) {
+    ARG(peak_scratch, "conversation_audio: null peak scratch");
+    static_assert(2 * kPeakPartials + 2 == A2P_CONVERSATION_SCRATCH, "conversation peak scratch size");
+    peak2_partial_kernel<<<kPeakPartials, 256, 0, s>>>(channels, ld, len, peak_scratch);
+    HIPCHK(hipGetLastError());
+    peak2_final_kernel<<<1, kPeakPartials, 0, s>>>(peak_scratch);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&peak[0], peak_scratch + 2 * kPeakPartials, sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&peak[1], peak_scratch + 2 * kPeakPartials + 1, sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    // each voice is divided by its own maximum: a silent (or non-finite) channel is refused before the assembly
+    for (int k = 0; k < 2; ++k)
+      ARG(peak[k] > 0.f && isfinite(peak[k]), "conversation_audio: the peak of channel %d is %g (silent or non-finite input; "
+          "normalize=\"none\" takes the samples as given)", k, (double)peak[k]);
+  }
+  const double* st = stats_host;
+  conversation_audio_kernel<<<grid_for(len), 256, 0, s>>>(channels, ld, len, peak[0], peak[1], people, st[0], st[1], st[2], st[3], st[4], st[5],
+                                                          reps, reinterpret_cast<float2*>(out));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // unit entry points
 // ------------------------------------------------------------------------------------------------

@@ -22,10 +22,9 @@ import torch
 from .. import _lib
 from ..diffusion.gaussian_diffusion import GaussianDiffusion
 from ..audio import resampled_length
-from ..sample_parallel import derive_seed, per_sample_noise
-from .generate import _guide_keyframes, _replace_keyframes
-from .recording import (BLOCK, MAX_FRAMES, MULTISTEP, SAMPLE_RATE, SAMPLES_PER_FRAME, _channels_last, _check_sampler, _denoiser, _overlapped,
-                        can_share_features, prepare_recording)
+from .generate import _guide_keyframes
+from .recording import (BLOCK, MAX_FRAMES, MULTISTEP, SAMPLE_RATE, SAMPLES_PER_FRAME, _channels_last, _check_models, _check_sampler,
+                        _denoiser, _face_body_runs, _overlapped, _recording_draws, _unnormalised, prepare_recording)
 
 KEYFRAME_STEP = 30                    # the body model's keyframe step: window starts snap to it
 
@@ -255,74 +254,32 @@ def generate_from_long_recording(face, pose, stats: Dict[str, np.ndarray], wavef
 
     Returns {"face": [R, T_total, 256], "pose": [R, T_total, 104], "keyframes": [R, W, T_w / 30, 104] (un-normalised),
     "audio": float64 [2, Lc], "T": T_total, "sr": 48000, "window_starts": [W] ints}."""
-    from ..model.audio_frontend import NativeAudioFrontend
     face_m, face_d = face
     pose_m, pose_d = pose
     fm, pm = _denoiser(face_m), _denoiser(pose_m)
     _check_sampler(sampler)
-    for name, m in (("face", fm), ("pose", pm)):
-        if getattr(m, "audio_frontend", None) is None:
-            raise _lib.A2PError(f"the {name} model has no audio front end: construct it with audio_frontend=\"native\"")
-    if getattr(pm, "transformer", None) is None or getattr(pm, "tokenizer", None) is None:
-        raise _lib.A2PError("the pose model has no guide transformer: attach it with setup_guide_predictor(transformer, tokenizer)")
+    _check_models(fm, pm)
     device = fm.null_cond_embed.device
     R = int(num_repetitions)
     max_batch = _max_batch(fm, pm, pm.transformer, fm.audio_frontend, pm.audio_frontend)
     rec = prepare_long_recording(waveform, sr, stats, R, seed, device, max_batch=max_batch, T_w=min(fm.seq_len, pm.seq_len),
                                  min_overlap=min_overlap)
     plan, T, audio = rec.plan, rec.T, rec.windows
-    W, B = plan.W, R * plan.W
+    W = plan.W
     nk = len(range(plan.T_w)[::KEYFRAME_STEP])
-
-    n_u = nk * pm.tokenizer.residual_depth
-    uniforms = torch.stack([torch.rand(n_u, generator=torch.Generator().manual_seed(derive_seed(seed, 1, r) if w == 0 else
-                                                                                      derive_seed(seed, 1, r, w)))
-                            for r in range(R) for w in range(W)], dim=1)     # [n, R*W]: column r * W + w
-    noise_pose = per_sample_noise((R, pm.nfeats, 1, T), [derive_seed(seed, 2, r) for r in range(R)]).to(device)
-    noise_face = per_sample_noise((R, fm.nfeats, 1, T), [derive_seed(seed, 3, r) for r in range(R)]).to(device)
+    uniforms, noise_pose, noise_face = _recording_draws(seed, R, nk * pm.tokenizer.residual_depth, (pm.nfeats, fm.nfeats), T, W)
 
     with torch.no_grad():
-        if share_features and can_share_features(face_m, pose_m):
-            feats = pm.audio_frontend.encode_audio(audio)
-            guide_cond = {"cond_embed": feats}
-            body_cond = {"cond_embed": pm.audio_frontend.encode_lip(audio, feats) if pm.audio_frontend.has_lip else feats}
-            face_cond = {"cond_embed": fm.audio_frontend.encode_lip(audio, feats) if fm.audio_frontend.has_lip else feats}
-        else:
-            body_cond, face_cond = {"audio": audio}, {"audio": audio}
-            if getattr(pm.transformer, "audio_frontend", None) is not None:
-                guide_cond = {"audio": audio}
-            elif isinstance(pm.audio_frontend, NativeAudioFrontend):
-                guide_cond = {"cond_embed": pm.audio_frontend.encode_audio(audio)}
-            else:
-                raise _lib.A2PError("the guide transformer has no audio front end and the pose model's is not the native one: "
-                                    "construct GuideTransformer(audio_frontend=callable)")
-        y_face = {**face_cond, "scale": torch.full((B,), float(face_scale), device=device)}
-        y_body = {**body_cond, "mask": torch.ones(B, 1, 1, plan.T_w, dtype=torch.bool, device=device),
-                  "scale": torch.full((B,), float(pose_scale), device=device)}
-
-        def run_face():
-            return windowed_sample_loop(face_d, face_m, plan, R, y_face, noise_face, sampler=sampler)
-
-        def run_body():
-            if chain_keyframes and W > 1:
-                y_body["keyframes"] = _chained_keyframes(pose_m, plan, R, guide_cond, uniforms, top_p, nk, pm.nfeats).to(device)
-            else:
-                guide_y = {**guide_cond, "keyframes": torch.zeros(B, nk, pm.nfeats, device=device)}
-                y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p).to(device)
-            return windowed_sample_loop(pose_d, pose_m, plan, R, y_body, noise_pose, sampler=sampler)
-
+        run_face, run_body, y_body = _face_body_runs(face, pose, audio, plan.T_w, nk, uniforms, noise_face.to(device),
+                                                     noise_pose.to(device), top_p, face_scale, pose_scale, sampler, share_features,
+                                                     plan=plan, chain_keyframes=chain_keyframes)
         if overlap:
             face_s, body_s = _overlapped(face, pose, run_face, run_body, device)
         else:
             face_s = run_face()
             body_s = run_body()
-
-    face_np = face_s.squeeze(2).cpu().numpy().transpose(0, 2, 1)
-    pose_np = body_s.squeeze(2).cpu().numpy().transpose(0, 2, 1)
     kf = y_body["keyframes"].cpu().numpy().reshape(R, W, nk, pm.nfeats)
-    return {"face": face_np * stats["code_std"] + stats["code_mean"],
-            "pose": pose_np * stats["pose_std"] + stats["pose_mean"],
-            "keyframes": kf * stats["pose_std"] + stats["pose_mean"],
+    return {**_unnormalised(face_s, body_s, kf, stats),
             "audio": rec.dual_audio, "T": T, "sr": SAMPLE_RATE, "window_starts": list(plan.starts)}
 
 

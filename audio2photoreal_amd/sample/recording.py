@@ -158,16 +158,11 @@ def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, 
 
     Returns {"face": [R, T, 256], "pose": [R, T, 104], "keyframes": [R, T / 30, 104] (un-normalised with the code_* / pose_*
     statistics: * std + mean), "audio": the un-normalised dual audio float64 [2, Lc], "T", "sr": 48000}."""
-    from ..model.audio_frontend import NativeAudioFrontend
     face_m, face_d = face
     pose_m, pose_d = pose
     fm, pm = _denoiser(face_m), _denoiser(pose_m)
     _check_sampler(sampler)
-    for name, m in (("face", fm), ("pose", pm)):
-        if getattr(m, "audio_frontend", None) is None:
-            raise _lib.A2PError(f"the {name} model has no audio front end: construct it with audio_frontend=\"native\"")
-    if getattr(pm, "transformer", None) is None or getattr(pm, "tokenizer", None) is None:
-        raise _lib.A2PError("the pose model has no guide transformer: attach it with setup_guide_predictor(transformer, tokenizer)")
+    _check_models(fm, pm)
     known = None
     if known_keyframes is not None:
         from .inpaint import require_encoder
@@ -179,56 +174,111 @@ def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, 
     prep = prepare_recording(waveform, sr, stats, R, seed, device, max_frames=min(fm.seq_len, pm.seq_len))
     audio, T = prep.audio, prep.T
     nk = len(range(T)[::30])
-
-    uniforms = torch.stack([torch.rand(nk * pm.tokenizer.residual_depth, generator=torch.Generator().manual_seed(derive_seed(seed, 1, r)))
-                            for r in range(R)], dim=1)                    # [n, R]: column r belongs to repetition r
-    noise_pose = per_sample_noise((R, pm.nfeats, 1, T), [derive_seed(seed, 2, r) for r in range(R)]).to(device)
-    noise_face = per_sample_noise((R, fm.nfeats, 1, T), [derive_seed(seed, 3, r) for r in range(R)]).to(device)
+    uniforms, noise_pose, noise_face = _recording_draws(seed, R, nk * pm.tokenizer.residual_depth, (pm.nfeats, fm.nfeats), T)
 
     with torch.no_grad():
-        if share_features and can_share_features(face_m, pose_m):
-            feats = pm.audio_frontend.encode_audio(audio)
-            guide_cond = {"cond_embed": feats}
-            body_cond = {"cond_embed": pm.audio_frontend.encode_lip(audio, feats) if pm.audio_frontend.has_lip else feats}
-            face_cond = {"cond_embed": fm.audio_frontend.encode_lip(audio, feats) if fm.audio_frontend.has_lip else feats}
-        else:
-            body_cond, face_cond = {"audio": audio}, {"audio": audio}
-            if getattr(pm.transformer, "audio_frontend", None) is not None:
-                guide_cond = {"audio": audio}
-            elif isinstance(pm.audio_frontend, NativeAudioFrontend):
-                guide_cond = {"cond_embed": pm.audio_frontend.encode_audio(audio)}
-            else:
-                raise _lib.A2PError("the guide transformer has no audio front end and the pose model's is not the native one: "
-                                    "construct GuideTransformer(audio_frontend=callable)")
-        y_face = {**face_cond, "scale": torch.full((R,), float(face_scale), device=device)}
-        y_body = {**body_cond, "mask": torch.ones(R, 1, 1, T, dtype=torch.bool, device=device),
-                  "scale": torch.full((R,), float(pose_scale), device=device)}
-
-        def loop(d):
-            return d.ddim_sample_loop if sampler == "ddim" else d.dpm_solver_sample_loop
-
-        def run_face():
-            return loop(face_d)(face_m, (R, fm.nfeats, 1, T), noise=noise_face, clip_denoised=False, model_kwargs={"y": y_face})
-
-        def run_body():
-            guide_y = {**guide_cond, "keyframes": torch.zeros(R, nk, pm.nfeats, device=device)}
-            kk = {} if known is None else {"known": known[0].expand(R, -1, -1), "known_mask": known[1].expand(R, -1)}
-            y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p, **kk).to(device)
-            return loop(pose_d)(pose_m, (R, pm.nfeats, 1, T), noise=noise_pose, clip_denoised=False, model_kwargs={"y": y_body})
-
+        run_face, run_body, y_body = _face_body_runs(face, pose, audio, T, nk, uniforms, noise_face.to(device), noise_pose.to(device),
+                                                     top_p, face_scale, pose_scale, sampler, share_features, known=known)
         if overlap:
             face_s, body_s = _overlapped(face, pose, run_face, run_body, device)
         else:
             face_s = run_face()
             body_s = run_body()
+    return {**_unnormalised(face_s, body_s, y_body["keyframes"].cpu().numpy(), stats),
+            "audio": prep.dual_audio, "T": T, "sr": SAMPLE_RATE}
 
+
+def _check_models(fm, pm) -> None:
+    """A2PError unless both denoisers have an audio front end and the pose model its guide transformer and tokenizer."""
+    for name, m in (("face", fm), ("pose", pm)):
+        if getattr(m, "audio_frontend", None) is None:
+            raise _lib.A2PError(f"the {name} model has no audio front end: construct it with audio_frontend=\"native\"")
+    if getattr(pm, "transformer", None) is None or getattr(pm, "tokenizer", None) is None:
+        raise _lib.A2PError("the pose model has no guide transformer: attach it with setup_guide_predictor(transformer, tokenizer)")
+
+
+def _recording_draws(seed: int, R: int, n_u: int, nfeats, T: int, W: int = 1):
+    """The random draws of `seed` on the host: keyframe uniforms [n_u, R * W] (column r * W + w; window 0 from derive_seed(seed,
+    1, r), window w > 0 from derive_seed(seed, 1, r, w)), body noise and face noise [R, nfeats, 1, T] (derive_seed(seed, 2 / 3,
+    r)).  W = 1: generate_from_recording's draws; W > 1: generate_from_long_recording's."""
+    uniforms = torch.stack([torch.rand(n_u, generator=torch.Generator().manual_seed(derive_seed(seed, 1, r) if w == 0 else
+                                                                                    derive_seed(seed, 1, r, w)))
+                            for r in range(R) for w in range(W)], dim=1)
+    noise_pose = per_sample_noise((R, nfeats[0], 1, T), [derive_seed(seed, 2, r) for r in range(R)])
+    noise_face = per_sample_noise((R, nfeats[1], 1, T), [derive_seed(seed, 3, r) for r in range(R)])
+    return uniforms, noise_pose, noise_face
+
+
+def _conditions(face_m, pose_m, audio: torch.Tensor, share_features: bool):
+    """(guide, body, face) conditioning of y["audio"] rows: the features once when `share_features` and the front ends agree,
+    else each model's own front end (a guide without one takes the pose model's features)."""
+    from ..model.audio_frontend import NativeAudioFrontend
+    fm, pm = _denoiser(face_m), _denoiser(pose_m)
+    if share_features and can_share_features(face_m, pose_m):
+        feats = pm.audio_frontend.encode_audio(audio)
+        guide_cond = {"cond_embed": feats}
+        body_cond = {"cond_embed": pm.audio_frontend.encode_lip(audio, feats) if pm.audio_frontend.has_lip else feats}
+        face_cond = {"cond_embed": fm.audio_frontend.encode_lip(audio, feats) if fm.audio_frontend.has_lip else feats}
+    else:
+        body_cond, face_cond = {"audio": audio}, {"audio": audio}
+        if getattr(pm.transformer, "audio_frontend", None) is not None:
+            guide_cond = {"audio": audio}
+        elif isinstance(pm.audio_frontend, NativeAudioFrontend):
+            guide_cond = {"cond_embed": pm.audio_frontend.encode_audio(audio)}
+        else:
+            raise _lib.A2PError("the guide transformer has no audio front end and the pose model's is not the native one: "
+                                "construct GuideTransformer(audio_frontend=callable)")
+    return guide_cond, body_cond, face_cond
+
+
+def _face_body_runs(face, pose, audio: torch.Tensor, T: int, nk: int, uniforms, noise_face, noise_pose, top_p, face_scale, pose_scale,
+                    sampler: str, share_features: bool, plan=None, known=None, chain_keyframes: bool = False):
+    """The conditioning of the B = audio.shape[0] sequences (computed here, on the current stream) and two closures: run_face()
+    -> the face sample, run_body() -> guide keyframes into y_body["keyframes"], then the body sample.  plan None: the plain loops
+    over T frames (known: the forced keyframes of generate_from_recording); else windowed_sample_loop over the plan's windows
+    (rows r * W + w, T the window length, noise per global frame)."""
+    face_m, face_d = face
+    pose_m, pose_d = pose
+    fm, pm = _denoiser(face_m), _denoiser(pose_m)
+    device = fm.null_cond_embed.device
+    B = audio.shape[0]
+    guide_cond, body_cond, face_cond = _conditions(face_m, pose_m, audio, share_features)
+    y_face = {**face_cond, "scale": torch.full((B,), float(face_scale), device=device)}
+    y_body = {**body_cond, "mask": torch.ones(B, 1, 1, T, dtype=torch.bool, device=device),
+              "scale": torch.full((B,), float(pose_scale), device=device)}
+
+    if plan is None:
+        def loop(d, m, noise, y):
+            run = d.ddim_sample_loop if sampler == "ddim" else d.dpm_solver_sample_loop
+            return run(m, (B, noise.shape[1], 1, T), noise=noise, clip_denoised=False, model_kwargs={"y": y})
+    else:
+        from .long_form import _chained_keyframes, windowed_sample_loop
+
+        def loop(d, m, noise, y):
+            return windowed_sample_loop(d, m, plan, B // plan.W, y, noise, sampler=sampler)
+
+    def run_face():
+        return loop(face_d, face_m, noise_face, y_face)
+
+    def run_body():
+        if plan is not None and chain_keyframes and plan.W > 1:
+            y_body["keyframes"] = _chained_keyframes(pose_m, plan, B // plan.W, guide_cond, uniforms, top_p, nk, pm.nfeats).to(device)
+        else:
+            guide_y = {**guide_cond, "keyframes": torch.zeros(B, nk, pm.nfeats, device=device)}
+            kk = {} if known is None else {"known": known[0].expand(B, -1, -1), "known_mask": known[1].expand(B, -1)}
+            y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p, **kk).to(device)
+        return loop(pose_d, pose_m, noise_pose, y_body)
+
+    return run_face, run_body, y_body
+
+
+def _unnormalised(face_s: torch.Tensor, body_s: torch.Tensor, kf: np.ndarray, stats) -> Dict[str, np.ndarray]:
+    """Samples [B, C, 1, T] -> {"face": [B, T, 256], "pose": [B, T, 104], "keyframes"}, un-normalised with `stats`."""
     face_np = face_s.squeeze(2).cpu().numpy().transpose(0, 2, 1)
     pose_np = body_s.squeeze(2).cpu().numpy().transpose(0, 2, 1)
-    kf = y_body["keyframes"].cpu().numpy()
     return {"face": face_np * stats["code_std"] + stats["code_mean"],
             "pose": pose_np * stats["pose_std"] + stats["pose_mean"],
-            "keyframes": kf * stats["pose_std"] + stats["pose_mean"],
-            "audio": prep.dual_audio, "T": T, "sr": SAMPLE_RATE}
+            "keyframes": kf * stats["pose_std"] + stats["pose_mean"]}
 
 
 def _known_keyframes(known_keyframes, T: int, stats, nv: int):
@@ -258,38 +308,52 @@ def _overlapped(face, pose, run_face, run_body, device):
     The loops' once-per-call non-finite check waits for its stream, so it is deferred until both streams are loaded and then
     made per stream; a model that escalates to fp32 there (FiLMTransformer.check_finite) has its loop repeated, as the
     non-deferred loops do."""
+    (face_s,), (body_s,) = _overlapped_jobs([(face, run_face)], [(pose, run_body)], device)
+    return face_s, body_s
+
+
+def _overlapped_jobs(face_jobs, body_jobs, device):
+    """_overlapped for several (model pair, run) jobs per stream: every face job on one side stream, every guide -> body job on the
+    other, in list order.  Each distinct denoiser is checked once on its stream after both are loaded, and every job of a denoiser
+    that escalated is repeated.  Returns the two lists of results."""
     main = torch.cuda.current_stream(device)
     s_face, s_body = torch.cuda.Stream(device), torch.cuda.Stream(device)
     s_face.wait_stream(main)
     s_body.wait_stream(main)
-    diffs = (face[1], pose[1])
+    diffs = [pair[1] for pair, _ in face_jobs + body_jobs]
+    escalated = set()
     for d in diffs:
         d.defer_finite_check = True
     try:
         with torch.cuda.stream(s_face):               # enqueued first: nothing on this stream blocks the host
-            face_s = run_face()
+            face_out = [run() for _, run in face_jobs]
         with torch.cuda.stream(s_body):
-            body_s = run_body()
-        with torch.cuda.stream(s_face):
-            redo_face = face[0].a2p_check_finite() == "escalated"
-        with torch.cuda.stream(s_body):
-            redo_body = pose[0].a2p_check_finite() == "escalated"
+            body_out = [run() for _, run in body_jobs]
+        for stream, jobs in ((s_face, face_jobs), (s_body, body_jobs)):
+            with torch.cuda.stream(stream):
+                for m in {id(_denoiser(pair[0])): pair[0] for pair, _ in jobs}.values():
+                    if m.a2p_check_finite() == "escalated":
+                        escalated.add(id(_denoiser(m)))
     finally:
         for d in diffs:
             d.defer_finite_check = False
     main.wait_stream(s_face)
     main.wait_stream(s_body)
     torch.cuda.synchronize(device)
-    if redo_face:
-        face_s = run_face()
-    if redo_body:
-        body_s = run_body()
-    return face_s, body_s
+    for jobs, out in ((face_jobs, face_out), (body_jobs, body_out)):
+        for i, (pair, run) in enumerate(jobs):
+            if id(_denoiser(pair[0])) in escalated:
+                out[i] = run()
+    return face_out, body_out
 
 
 def __getattr__(name):
-    """continue_recording and regenerate_segment (sample/inpaint.py) are importable from here, next to generate_from_recording."""
+    """continue_recording and regenerate_segment (sample/inpaint.py), generate_conversation and prepare_conversation
+    (sample/conversation.py) are importable from here, next to generate_from_recording."""
     if name in ("continue_recording", "regenerate_segment"):
         from . import inpaint
         return getattr(inpaint, name)
+    if name in ("generate_conversation", "prepare_conversation"):
+        from . import conversation
+        return getattr(conversation, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

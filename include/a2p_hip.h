@@ -13,8 +13,8 @@
  *  - tensors are dense row-major fp32 unless stated; int64 for timesteps
  *    (the reference passes torch.long, gaussian_diffusion.py:911);
  *  - all work is enqueued on `stream` (a hipStream_t passed as void*); nothing
- *    synchronises the device except a2p_ctx_destroy, a2p_kernel_time_ms and a2p_dual_audio
- *    (which reads one float back);
+ *    synchronises the device except a2p_ctx_destroy, a2p_kernel_time_ms, a2p_dual_audio
+ *    (which reads one float back) and a2p_conversation_audio under A2P_NORMALIZE_PEAK (two floats);
  *  - return value: 0 = ok, negative = A2P_ERR_* (no exceptions cross the ABI);
  *    a2p_last_error() returns a static thread-local message;
  *  - inputs are borrowed for the duration of the enqueued work, outputs are
@@ -241,6 +241,26 @@ int a2p_resample(const float* in, int32_t batch, int64_t len, int32_t in_channel
 #define A2P_DUAL_AUDIO_SCRATCH 257
 int a2p_dual_audio(const float* mono, int64_t len, float* peak_scratch, const double* noise, double mean0, double mean1,
                    double std_flat, int32_t reps, float* out, void* stream);
+/* Conversations (sample/conversation.py; the dataset's two-channel audio, data_loaders/get_data.py:79-92, 83-88 flip_person).
+ * a2p_resample_channels: a2p_resample of every channel on its own: in fp32 [len, channels] interleaved -> out fp32 planar
+ * [channels, ceil(n len / o)]; row c is bit-identical to a2p_resample (batch 1, in_channels 1) of channel c extracted as a mono
+ * row.  Same table rules; orig_freq == new_freq: table may be NULL and the channels are copied. */
+int a2p_resample_channels(const float* in, int64_t len, int32_t channels, int32_t orig_freq, int32_t new_freq,
+                          const float* table, int32_t n_phase, int32_t n_taps, int32_t width, float* out, void* stream);
+/* a2p_conversation_audio: y["audio"] of both people of a two-channel recording.  channels fp32 planar [2, ld] (channel k = person
+ * k's microphone), of which the first len samples are used.  Person p's own voice is channel p, the partner's channel 1 - p:
+ *   u_k = channels[k][i] / peak_k (float32; peak_k = max over [0, len) of channel k)  under A2P_NORMALIZE_PEAK,
+ *   u_k = channels[k][i]                                                                under A2P_NORMALIZE_NONE,
+ *   out[p * reps + r][i] = (float((u_p - mean0_p) / std_p), float((u_{1-p} - mean1_p) / std_p))   (float64 arithmetic)
+ * for every person p in the bitmask `people` (bit p) and repetition r < reps; the rows of a person outside `people` are not
+ * written.  out fp32 [2 reps, len, 2].  stats_host: fp64 [2][3] = (mean0_p, mean1_p, std_p) on the host.  Under
+ * A2P_NORMALIZE_PEAK peak_scratch holds A2P_CONVERSATION_SCRATCH floats of device memory, a channel whose peak is not > 0 or not
+ * finite is refused with A2P_ERR_ARG, and `stream` is synchronised once to read the two peaks back. */
+#define A2P_NORMALIZE_NONE 0
+#define A2P_NORMALIZE_PEAK 1
+#define A2P_CONVERSATION_SCRATCH 514
+int a2p_conversation_audio(const float* channels, int64_t ld, int64_t len, int32_t normalize, float* peak_scratch, int32_t people,
+                           const double* stats_host, int32_t reps, float* out, void* stream);
 
 /* ---- unit entry points (parity tests of single kernels / one decoder layer) -----
  * FiLMTransformerDecoderLayer.forward (model/modules/transformer_modules.py:178-217):
