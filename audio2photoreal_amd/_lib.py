@@ -44,7 +44,7 @@ EXPORTS = (
     "a2p_sample_step_windowed", "a2p_window_gather", "a2p_sample_step_inpaint", "a2p_guide_generate_forced", "a2p_vq_encode",
     "a2p_sample_step_multistep", "a2p_sample_step_windowed_multistep", "a2p_multistep_update",
     "a2p_eval_moments", "a2p_eval_pair_dist", "a2p_eval_gemm_f64", "a2p_eval_eigh",
-    "a2p_resample_channels", "a2p_conversation_audio",
+    "a2p_resample_channels", "a2p_conversation_audio", "a2p_dataset_batch",
 )
 
 
@@ -68,6 +68,11 @@ class A2PFrontendConfig(C.Structure):
         + [("a_residual_scale", C.c_float), ("l_residual_scale", C.c_float), ("l_layers", C.c_int32), ("agg_layers", C.c_int32),
            ("agg_skip", C.c_int32), ("agg_residual_scale", C.c_float), ("agg_conv_bias", C.c_int32), ("agg_zero_pad", C.c_int32),
            ("agg_activation", C.c_int32), ("reserved", C.c_int32 * 2)])
+
+
+class A2PDatasetTake(C.Structure):
+    _fields_ = [("motion", C.c_void_p), ("present", C.c_void_p), ("audio", C.c_void_p), ("frames", C.c_int64),
+                ("motion_f64", C.c_int32), ("reserved", C.c_int32)]
 
 
 class A2PError(RuntimeError):
@@ -94,6 +99,7 @@ DUAL_AUDIO_SCRATCH = 257              # A2P_DUAL_AUDIO_SCRATCH (floats)
 CONVERSATION_SCRATCH = 514            # A2P_CONVERSATION_SCRATCH (floats)
 NORMALIZE_NONE, NORMALIZE_PEAK = 0, 1 # A2P_NORMALIZE_*
 WINDOW_MAX = 256                      # A2P_WINDOW_MAX
+DATASET_MAX_BATCH = 64                # A2P_DATASET_MAX_BATCH
 
 
 _libs = {}
@@ -172,6 +178,8 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_eval_eigh": [vp, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_double), vp],
         "a2p_resample_channels": [vp, i64, i32, i32, i32, vp, i32, i32, i32, vp, vp],
         "a2p_conversation_audio": [vp, i64, i64, i32, vp, i32, C.POINTER(C.c_double), i32, vp, vp],
+        "a2p_dataset_batch": [C.POINTER(A2PDatasetTake), i32, i32, i32, C.POINTER(i32), C.POINTER(i64), i32, i32, i32, i32, vp, vp,
+                              f32, f32, f32, i32, vp, vp, vp, vp, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

@@ -30,6 +30,7 @@
 #include "kernels_audio.h"
 #include "kernels_chain.h"
 #include "kernels_chain4.h"
+#include "kernels_dataset.h"
 #include "kernels_eval.h"
 #include "kernels_gemm.h"
 #include "kernels_inpaint.h"
@@ -1004,3 +1005,4 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_guide.h"
 #include "a2p_frontend.h"
 #include "a2p_eval.h"
+#include "a2p_dataset.h"

@@ -487,6 +487,34 @@ int a2p_eval_gemm_f64(int32_t n, const double* a, int64_t a_rs, int64_t a_cs, co
 int a2p_eval_eigh(const double* a, int32_t n, double* w, double* q, double* workspace, int32_t* sweeps_host, double* off_host,
                   void* stream);
 
+/* ---- capture dataset (reference data_loaders/data.py:223-253, tensors.py:71-86; audio2photoreal_amd/data/) ----------------
+ * What Social.__getitem__ + social_collate build for `batch` chunks of the test split, from takes that stay resident on the
+ * device in their stored dtypes.  Chunk b is the frames [start_of[b], start_of[b] + frames) of take take_of[b] (host arrays).
+ *   inp       fp32 [batch, channels, 1, frames]   (motion - mean) / std in fp64, times the presence flag when face != 0
+ *                                                 (data.py:251-252), rounded once to fp32
+ *   keyframes fp32 [batch, ceil(frames / key_step), channels]   the same values at frames 0, key_step, 2 key_step, ...
+ *   missing   fp32 [batch, frames, channels]      the presence flag (face != 0) or ones
+ *   audio     fp32 [batch, frames * samples_per_frame, 2]   (a - audio_mean[c]) / audio_std in fp32; swap_channels != 0 reads
+ *                                                 channel 1 - c (the reference's flip_person)
+ * Every output value is added to +0.0f as collate_tensors' zeroed canvas does (tensors.py:23-28: -0.0 becomes +0.0).
+ * Correctly rounded IEEE operations only: the outputs carry the reference's bits.  mean / std_dev: device fp64 [channels].
+ * One launch on `stream`; no allocation, copy or synchronisation (the chunk table travels in the kernel arguments).  Audio
+ * pointers must be 16-byte aligned and samples_per_frame even. */
+#define A2P_DATASET_MAX_BATCH 64
+typedef struct a2p_dataset_take {
+  const void* motion;      /* device [frames, channels], fp64 (motion_f64 != 0) or fp32: takes of one call may differ */
+  const uint8_t* present;  /* device [frames]: 0 on the missing face frames, 1 elsewhere; NULL: every frame present */
+  const float* audio;      /* device [frames * samples_per_frame, 2] */
+  int64_t frames;
+  int32_t motion_f64;
+  int32_t reserved;
+} a2p_dataset_take;
+int a2p_dataset_batch(const a2p_dataset_take* takes, int32_t n_takes, int32_t channels, int32_t face,
+                      const int32_t* take_of, const int64_t* start_of, int32_t batch, int32_t frames, int32_t key_step,
+                      int32_t samples_per_frame, const double* mean, const double* std_dev, float audio_mean0, float audio_mean1,
+                      float audio_std, int32_t swap_channels, float* inp, float* keyframes, float* missing, float* audio,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
