@@ -45,6 +45,7 @@ EXPORTS = (
     "a2p_sample_step_multistep", "a2p_sample_step_windowed_multistep", "a2p_multistep_update",
     "a2p_eval_moments", "a2p_eval_pair_dist", "a2p_eval_gemm_f64", "a2p_eval_eigh",
     "a2p_resample_channels", "a2p_conversation_audio", "a2p_dataset_batch",
+    "a2p_gemm_ex", "a2p_skinny_gemm_ex",
 )
 
 
@@ -73,6 +74,25 @@ class A2PFrontendConfig(C.Structure):
 class A2PDatasetTake(C.Structure):
     _fields_ = [("motion", C.c_void_p), ("present", C.c_void_p), ("audio", C.c_void_p), ("frames", C.c_int64),
                 ("motion_f64", C.c_int32), ("reserved", C.c_int32)]
+
+
+class A2PGemmCase(C.Structure):
+    """a2p_gemm_case (include/a2p_hip.h): one launch of the GEMM dispatcher, test-only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("A", "W", "bias", "out", "resid", "film", "skip")] + [("ran_host", C.POINTER(C.c_int32))]
+                + [(n, C.c_int64) for n in ("a_rows", "out_elems", "out_off", "ldo", "t_seq_stride", "ldx", "resid_elems", "film_elems",
+                                            "film_seq_stride", "dup_off")]
+                + [(n, C.c_int32) for n in ("M", "N", "K", "ntaps", "a_tap_rows", "epi", "act", "out_f32", "rows_per_seq", "out_seq_pad",
+                                            "film_shift_off", "split", "split_third", "reserved")])
+
+
+class A2PSkinnyCase(C.Structure):
+    """a2p_skinny_case (include/a2p_hip.h), test-only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("A", "W", "bias", "out")] + [(n, C.c_int64) for n in ("lda", "ldw", "ldo")]
+                + [(n, C.c_int32) for n in ("M", "N", "K", "act")])
+
+
+EPI_STORE, EPI_STORE_T, EPI_FILM_RES, EPI_CONV = 0, 1, 2, 3                          # csrc/kernels_gemm.h
+ACT_NONE, ACT_GELU, ACT_MISH, ACT_SILU, ACT_LRELU, ACT_RELU = 0, 1, 2, 3, 4, 5       # csrc/a2p_common.h
 
 
 class A2PError(RuntimeError):
@@ -178,6 +198,8 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_eval_eigh": [vp, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(C.c_double), vp],
         "a2p_resample_channels": [vp, i64, i32, i32, i32, vp, i32, i32, i32, vp, vp],
         "a2p_conversation_audio": [vp, i64, i64, i32, vp, i32, C.POINTER(C.c_double), i32, vp, vp],
+        "a2p_gemm_ex": [vp, C.POINTER(A2PGemmCase), vp],
+        "a2p_skinny_gemm_ex": [vp, C.POINTER(A2PSkinnyCase), i32, vp],
         "a2p_dataset_batch": [C.POINTER(A2PDatasetTake), i32, i32, i32, C.POINTER(i32), C.POINTER(i64), i32, i32, i32, i32, vp, vp,
                               f32, f32, f32, i32, vp, vp, vp, vp, vp],
     }

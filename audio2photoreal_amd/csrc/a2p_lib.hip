@@ -347,16 +347,16 @@ static int gemm_dispatch(KernelTimer& kt, const GemmP& p, hipStream_t s) {
   return 0;
 }
 
-static int launch_gemm(a2p_ctx* c, const GemmP& p, hipStream_t s) {
-  const int bk = c->bf16 ? 64 : 32;
-  ARG(p.K % bk == 0 && p.N % 4 == 0 && p.M > 0, "gemm: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
+// Which gemm_kernel instance a launch takes: element bits (16 | 32), rows per tile / 32 (MT), depth of the tile ring (NB).
+struct GemmPick {
+  int bits, mt, nb;
+};
+static GemmPick gemm_pick(const a2p_ctx* c, const GemmP& p) {
   // bf16: 64x128 tiles at every shape of this path (measured on MI355X, profiles/r01_gemm_ablation.txt: 9600..38400 rows x
   // 512|1024 cols, 64x128 is 0-25% faster than 128x128 -- three co-resident blocks per CU overlap each other's
   // load / MFMA / epilogue phases).  fp32: 128x128 unless that leaves the 256 CUs under two blocks each.
   const int64_t blocks128 = (int64_t)((p.N + 127) / 128) * ((p.M + 127) / 128);
   const bool small = c->bf16 || blocks128 < 512;
-  KernelTimer kt(c, A2P_KERNEL_GEMM);
-  int rc;
   // 16-bit launches of at most one 64x128 workgroup per CU (config 0: 480 rows) are K/64 serial memory round trips with the
   // 2-deep ring; they take the 4-deep one (A2P_GEMM_RING2=1 keeps the 2-deep ring for A/B runs)
   static const bool ring2 = getenv("A2P_GEMM_RING2") != nullptr;
@@ -365,10 +365,22 @@ static int launch_gemm(a2p_ctx* c, const GemmP& p, hipStream_t s) {
   // at B=16 = 1.2 per CU, each a chain of 18 k-tile round trips): 32-row tiles double the workgroups per CU (A2P_GEMM_MT1=0|1)
   static const int mt1 = getenv("A2P_GEMM_MT1") ? atoi(getenv("A2P_GEMM_MT1")) : 1;
   static const int ring4_blocks = getenv("A2P_GEMM_RING4_BLOCKS") ? atoi(getenv("A2P_GEMM_RING4_BLOCKS")) : 256;   // (A/B: the 4-deep ring up to this many 64-row workgroups)
-  if (c->bf16 && mt1 && p.ntaps > 1 && p.N <= 128 && blocks64 <= 3 * 256) rc = gemm_dispatch<h16_t, 1>(kt, p, s);
-  else if (c->bf16 && small && blocks64 <= ring4_blocks && p.ntaps == 1 && !ring2) rc = gemm_dispatch<h16_t, 2, 4>(kt, p, s);
-  else if (c->bf16) rc = small ? gemm_dispatch<h16_t, 2>(kt, p, s) : gemm_dispatch<h16_t, 4>(kt, p, s);
-  else rc = small ? gemm_dispatch<float, 2>(kt, p, s) : gemm_dispatch<float, 4>(kt, p, s);
+  if (c->bf16 && mt1 && p.ntaps > 1 && p.N <= 128 && blocks64 <= 3 * 256) return {16, 1, 2};
+  if (c->bf16 && small && blocks64 <= ring4_blocks && p.ntaps == 1 && !ring2) return {16, 2, 4};
+  if (c->bf16) return {16, small ? 2 : 4, 2};
+  return {32, small ? 2 : 4, 2};
+}
+
+static int launch_gemm(a2p_ctx* c, const GemmP& p, hipStream_t s) {
+  const int bk = c->bf16 ? 64 : 32;
+  ARG(p.K % bk == 0 && p.N % 4 == 0 && p.M > 0, "gemm: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
+  const GemmPick k = gemm_pick(c, p);
+  KernelTimer kt(c, A2P_KERNEL_GEMM);
+  int rc;
+  if (k.bits == 16 && k.mt == 1) rc = gemm_dispatch<h16_t, 1>(kt, p, s);
+  else if (k.bits == 16 && k.nb == 4) rc = gemm_dispatch<h16_t, 2, 4>(kt, p, s);
+  else if (k.bits == 16) rc = k.mt == 2 ? gemm_dispatch<h16_t, 2>(kt, p, s) : gemm_dispatch<h16_t, 4>(kt, p, s);
+  else rc = k.mt == 2 ? gemm_dispatch<float, 2>(kt, p, s) : gemm_dispatch<float, 4>(kt, p, s);
   CHK(rc);
   HIPCHK(hipGetLastError());
   return 0;

@@ -1711,6 +1711,124 @@ __global__ void widen_kernel(const h16_t* a, float* o, int64_t n) {
   if (i < n) o[i] = (float)a[i];
 }
 
+__global__ void narrow_kernel(const float* a, h16_t* o, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) o[i] = (h16_t)a[i];
+}
+
+// Test-only: one launch_gemm call with every field of GemmP in the caller's hands (include/a2p_hip.h a2p_gemm_case).  Operands are
+// cast the way the forwards cast them (launch_cast, or split3_kernel for split rows; K zero-padded to the mode's k-step); a 16-bit
+// output buffer is the caller's fp32 image narrowed before the launch and widened back after it, guards and padding included.
+extern "C" int a2p_gemm_ex(a2p_ctx* c, const a2p_gemm_case* q, void* stream) {
+  ARG(c && q && q->A && q->W, "gemm_ex: null argument");
+  const int M = q->M, N = q->N, K = q->K, epi = q->epi;
+  ARG(M > 0 && N > 0 && K > 0 && N % 4 == 0, "gemm_ex: bad shape M=%d N=%d K=%d", M, N, K);
+  ARG(q->ntaps >= 1 && q->ntaps <= 3 && q->a_tap_rows >= 0 && (q->ntaps == 1 || epi == EPI_CONV), "gemm_ex: bad taps");
+  ARG(epi >= EPI_STORE && epi <= EPI_CONV && q->rows_per_seq >= 1 && q->out_seq_pad >= 0, "gemm_ex: bad epilogue");
+  ARG(q->a_rows >= (int64_t)M + (int64_t)(q->ntaps - 1) * q->a_tap_rows, "gemm_ex: A has too few rows for the taps");
+  {  // the instances gemm_dispatch has (a2p_lib.hip)
+    const int act = q->act, f32 = q->out_f32;
+    const bool has = epi == EPI_FILM_RES || (epi == EPI_STORE_T && act == ACT_NONE && !f32) || (epi == EPI_CONV && act == ACT_LRELU && !f32) ||
+                     (epi == EPI_STORE && (act == ACT_NONE || act == ACT_RELU || (act == ACT_GELU && !f32)));
+    ARG((f32 == 0 || f32 == 1) && has, "gemm_ex: no kernel instance for epi=%d act=%d out_f32=%d", epi, act, f32);
+  }
+  ARG(!q->split || c->bf16, "gemm_ex: split operand rows exist in the 16-bit modes only");
+  ARG(!q->bias || (uintptr_t)q->bias % 16 == 0, "gemm_ex: bias must be 16-byte aligned");
+  const bool out16 = c->bf16 && !q->out_f32 && epi != EPI_FILM_RES;
+  const int64_t nseq1 = (M - 1) / q->rows_per_seq;   // index of the last sequence
+  if (epi == EPI_FILM_RES) {
+    ARG(q->resid && (uintptr_t)q->resid % 16 == 0 && q->ldx >= N && q->ldx % 4 == 0 && q->resid_elems >= (int64_t)(M - 1) * q->ldx + N,
+        "gemm_ex: residual stream too small or misaligned");
+    ARG(!q->film || ((uintptr_t)q->film % 16 == 0 && q->film_seq_stride >= 0 && q->film_seq_stride % 4 == 0 && q->film_shift_off >= 0 &&
+                     q->film_shift_off % 4 == 0 && q->film_elems >= nseq1 * q->film_seq_stride + q->film_shift_off + N),
+        "gemm_ex: FiLM table too small or misaligned");
+    ARG(!q->out_seq_pad && !q->dup_off && !q->split_third && !q->skip, "gemm_ex: field not used by EPI_FILM_RES");
+  } else {
+    ARG(q->out && q->out_off >= 0 && q->out_off % 4 == 0 && (uintptr_t)q->out % 16 == 0 && q->ldo > 0, "gemm_ex: bad output buffer");
+    int64_t last;
+    if (epi == EPI_STORE_T) {
+      ARG(!q->out_f32 && q->act == ACT_NONE && !q->out_seq_pad && !q->dup_off && !q->split_third && !q->skip, "gemm_ex: field not used by EPI_STORE_T");
+      ARG(q->ldo >= q->rows_per_seq && q->t_seq_stride >= (int64_t)N * q->ldo, "gemm_ex: transposed sequences overlap");
+      last = q->out_off + nseq1 * q->t_seq_stride + (int64_t)(N - 1) * q->ldo + q->rows_per_seq - 1;
+    } else {
+      ARG(q->split_third >= 0 && (!q->split_third || (out16 && q->split_third % 4 == 0 && q->split_third >= N)), "gemm_ex: bad split_third");
+      ARG(q->dup_off >= 0 && q->dup_off % 4 == 0 && (!q->dup_off || q->out_f32), "gemm_ex: dup_off needs the fp32 store");
+      ARG(!q->skip || (epi == EPI_CONV && N <= K), "gemm_ex: the averaged skip needs EPI_CONV and N <= K");
+      const int64_t width = q->split_third ? 2 * (int64_t)q->split_third + N : N;
+      ARG(q->ldo % 4 == 0 && q->ldo >= width, "gemm_ex: ldo");
+      last = q->out_off + ((int64_t)(M - 1) + nseq1 * q->out_seq_pad) * q->ldo + width - 1 + q->dup_off;
+    }
+    ARG(last < q->out_elems, "gemm_ex: the write set ends at element %lld of %lld", (long long)last, (long long)q->out_elems);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int X = q->split ? 3 : 1, kp = rup(K, c->bf16 ? 64 : 32), Kc = X * kp;
+  const size_t esz = c->esz;
+  Buf a, w, sk, o16;
+  struct Free { Buf *a, *b, *c, *d; ~Free() { buf_free(*a); buf_free(*b); buf_free(*c); buf_free(*d); } } fr{&a, &w, &sk, &o16};
+  CHK(buf_alloc_tmp(a, (size_t)q->a_rows * Kc * esz));
+  CHK(buf_alloc_tmp(w, (size_t)q->ntaps * N * Kc * esz));
+  if (q->skip) CHK(buf_alloc_tmp(sk, (size_t)M * Kc * esz));
+  if (out16) CHK(buf_alloc_tmp(o16, (size_t)q->out_elems * 2));
+  auto operand = [&](const float* src, Buf& b, int64_t rows, int weight) -> int {
+    if (!q->split) return launch_cast(c, src, K, b.p, kp, rows, K, kp, nullptr, s);
+    const int64_t n = rows * kp;
+    split3_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(src, K, 1, reinterpret_cast<h16_t*>(b.p), rows, K, kp, weight);
+    HIPCHK(hipGetLastError());
+    return 0;
+  };
+  CHK(operand(q->A, a, q->a_rows, 0));
+  CHK(operand(q->W, w, (int64_t)q->ntaps * N, 1));
+  if (q->skip) CHK(operand(q->skip, sk, M, 0));
+  void* out = nullptr;
+  if (out16) {
+    narrow_kernel<<<(int)((q->out_elems + 255) / 256), 256, 0, s>>>(q->out, reinterpret_cast<h16_t*>(o16.p), q->out_elems);
+    HIPCHK(hipGetLastError());
+    out = reinterpret_cast<h16_t*>(o16.p) + q->out_off;
+  } else if (epi != EPI_FILM_RES) {
+    out = q->out + q->out_off;
+  }
+  GemmP p = gemm_base(a.p, Kc, w.p, Kc, q->bias, out, q->ldo, M, N, Kc);
+  p.ntaps = q->ntaps; p.a_tap_stride = (int64_t)q->a_tap_rows * Kc; p.w_tap_stride = (int64_t)N * Kc;
+  p.epi = epi; p.act = q->act; p.out_f32 = q->out_f32;
+  p.resid = q->resid; p.ldx = q->ldx; p.film = q->film; p.film_seq_stride = q->film_seq_stride; p.film_shift_off = q->film_shift_off;
+  p.rows_per_seq = q->rows_per_seq; p.t_seq_stride = q->t_seq_stride; p.out_seq_pad = q->out_seq_pad;
+  if (q->skip) { p.skip = sk.p; p.ld_skip = Kc; p.skip_lo = q->split ? kp : 0; }
+  p.split_third = q->split_third; p.dup_off = q->dup_off;
+  if (q->ran_host) {
+    const GemmPick k = gemm_pick(c, p);
+    q->ran_host[0] = k.bits; q->ran_host[1] = k.mt; q->ran_host[2] = k.nb;
+  }
+  int rc = launch_gemm(c, p, s);
+  if (rc == 0 && out16) {
+    widen_kernel<<<(int)((q->out_elems + 255) / 256), 256, 0, s>>>(reinterpret_cast<const h16_t*>(o16.p), q->out, q->out_elems);
+    if (hipGetLastError() != hipSuccess) { set_err("gemm_ex: widen launch failed"); rc = A2P_ERR_HIP; }
+  }
+  if (hipStreamSynchronize(s) != hipSuccess && rc == 0) { set_err("gemm_ex: stream synchronisation failed"); rc = A2P_ERR_HIP; }
+  return rc;
+}
+
+// Test-only: one skinny GEMM through launch_skinny (ncases == 1) or three through launch_skinny3 (ncases == 3), on fp32 device rows.
+extern "C" int a2p_skinny_gemm_ex(a2p_ctx* c, const a2p_skinny_case* q, int32_t ncases, void* stream) {
+  ARG(c && q && (ncases == 1 || ncases == 3), "skinny_gemm_ex: one case or three");
+  for (int i = 0; i < ncases; ++i) {
+    const a2p_skinny_case& k = q[i];
+    ARG(k.A && k.W && k.out && k.M > 0 && k.N > 0 && k.K > 0 && k.N % 16 == 0 && k.K % 64 == 0, "skinny_gemm_ex: bad shape M=%d N=%d K=%d", k.M, k.N, k.K);
+    ARG(k.lda >= k.K && k.ldw >= k.K && k.ldo >= k.N && k.lda % 4 == 0 && k.ldw % 4 == 0 && k.ldo % 4 == 0, "skinny_gemm_ex: bad row strides");
+    ARG((uintptr_t)k.A % 16 == 0 && (uintptr_t)k.W % 16 == 0 && (uintptr_t)k.out % 16 == 0, "skinny_gemm_ex: rows must be 16-byte aligned");
+    ARG(k.act >= ACT_NONE && k.act <= ACT_RELU, "skinny_gemm_ex: bad activation");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (ncases == 1) {
+    CHK(launch_skinny(q->A, q->lda, q->W, q->ldw, q->bias, q->out, q->ldo, q->M, q->N, q->K, q->act, s));
+  } else {
+    SkinnyArgs a[3];
+    for (int i = 0; i < 3; ++i) a[i] = {q[i].A, q[i].lda, q[i].W, q[i].ldw, q[i].bias, q[i].out, q[i].ldo, q[i].M, q[i].N, q[i].K, q[i].act};
+    CHK(launch_skinny3(a, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
 template <typename T>
 __global__ void transpose_cast_kernel(const float* __restrict__ v, T* __restrict__ vt, int S, int d, int Sld) {
   // v [n][S][d] -> vt [n][d][Sld]

@@ -272,6 +272,50 @@ int a2p_decoder_layer_forward(a2p_ctx* ctx, int32_t layer, float* x, const float
 /* C[M,N] = A[M,K] W[N,K]^T + bias on the MFMA GEMM kernel of the context's precision. */
 int a2p_gemm(a2p_ctx* ctx, const float* A, const float* W, const float* bias, float* C, int32_t M, int32_t N,
              int32_t K, void* stream);
+/* Test-only (never on the product path): ONE launch of the GEMM dispatcher with every epilogue field in the caller's hands, so that
+ * each kernel instance and epilogue can be compared with a float64 restatement on its own (tests/test_gemm_family_hip.py).
+ *   acc[m][n] = sum over tap < ntaps, k < K of A[m + tap * a_tap_rows][k] * W[tap][n][k]   (+ bias[n])
+ * A fp32 [a_rows, K], W fp32 [ntaps, N, K], skip fp32 [M, K] (columns < N are read), all dense.  The operands are cast to the
+ * context's type exactly as the forwards cast them, K zero-padded to the k-step (32 fp32 / 64 16-bit); split != 0 (16-bit modes):
+ * as split-operand rows A' = [hi | lo | hi], W' = [hi | hi | lo] instead.  epi / act: the kernels' EPI_* (0 store, 1 transposed
+ * store, 2 FiLM residual, 3 conv) and ACT_* (0 none, 1 GELU, 4 LeakyReLU(0.2), 5 ReLU) values; a combination without a kernel
+ * instance is A2P_ERR_ARG.
+ *   store / conv:      out[out_off + (m + (m / rows_per_seq) * out_seq_pad) * ldo + n]; split_third > 0: the 16-bit row is
+ *                      [hi | lo | hi] with the pieces split_third elements apart; dup_off > 0 (out_f32): a second copy dup_off further
+ *   transposed store:  out[out_off + (m / rows_per_seq) * t_seq_stride + n * ldo + m % rows_per_seq]
+ *   FiLM residual:     resid[m * ldx + n] += (film[seq * film_seq_stride + n] + 1) * acc + film[seq * film_seq_stride + film_shift_off + n]
+ *                      (film NULL: += acc), seq = m / rows_per_seq; resid points at row 0 and resid_elems floats are addressable from it
+ * out is the fp32 image of the WHOLE output buffer (out_elems elements, guard rows included).  A 16-bit store (16-bit mode,
+ * out_f32 == 0) narrows the image to the 16-bit type, runs on that buffer and widens all of it back, so a value the kernel did
+ * not write returns as it was when the 16-bit type holds it exactly.  ran_host (host memory, may be NULL) receives the
+ * gemm_kernel instance the dispatcher chose: {element bits, MT, NB}.  Shapes whose write set would leave a buffer are
+ * A2P_ERR_ARG and nothing is launched.  Synchronises `stream`. */
+typedef struct a2p_gemm_case {
+  const float* A;
+  const float* W;
+  const float* bias;
+  float* out;
+  float* resid;
+  const float* film;
+  const float* skip;
+  int32_t* ran_host;
+  int64_t a_rows, out_elems, out_off, ldo, t_seq_stride, ldx, resid_elems, film_elems, film_seq_stride, dup_off;
+  int32_t M, N, K, ntaps, a_tap_rows, epi, act, out_f32, rows_per_seq, out_seq_pad, film_shift_off, split, split_third, reserved;
+} a2p_gemm_case;
+int a2p_gemm_ex(a2p_ctx* ctx, const a2p_gemm_case* gemm_case, void* stream);
+/* Test-only: out[M, N] = act(A[M, K] W[N, K]^T + bias) on the skinny fp32 GEMM of the per-step time path; fp32 device rows with row
+ * strides lda / ldw / ldo, K % 64 == 0, N % 16 == 0, bias may be NULL.  ncases == 1: launch_skinny (64 rows per launch);
+ * ncases == 3: the grouped launch of three independent cases (one kernel when every M <= 64, three single launches otherwise).
+ * Synchronises `stream`. */
+typedef struct a2p_skinny_case {
+  const float* A;
+  const float* W;
+  const float* bias;
+  float* out;
+  int64_t lda, ldw, ldo;
+  int32_t M, N, K, act;
+} a2p_skinny_case;
+int a2p_skinny_gemm_ex(a2p_ctx* ctx, const a2p_skinny_case* cases, int32_t ncases, void* stream);
 /* softmax(q k^T / sqrt(dh)) v per head; q [N, Tq, d], k/v [N, S, d], out [N, Tq, d]. */
 int a2p_attention(a2p_ctx* ctx, const float* q, const float* k, const float* v, float* out, int32_t nseq,
                   int32_t tq, int32_t s, void* stream);
