@@ -46,6 +46,7 @@ EXPORTS = (
     "a2p_eval_moments", "a2p_eval_pair_dist", "a2p_eval_gemm_f64", "a2p_eval_eigh",
     "a2p_resample_channels", "a2p_conversation_audio", "a2p_dataset_batch",
     "a2p_gemm_ex", "a2p_skinny_gemm_ex",
+    "a2p_skin_states", "a2p_skin_vertices",
 )
 
 
@@ -120,6 +121,7 @@ CONVERSATION_SCRATCH = 514            # A2P_CONVERSATION_SCRATCH (floats)
 NORMALIZE_NONE, NORMALIZE_PEAK = 0, 1 # A2P_NORMALIZE_*
 WINDOW_MAX = 256                      # A2P_WINDOW_MAX
 DATASET_MAX_BATCH = 64                # A2P_DATASET_MAX_BATCH
+SKIN_MAX_JOINTS, SKIN_MAX_PARAMS, SKIN_MAX_INFLUENCES = 1024, 1024, 16   # A2P_SKIN_MAX_*
 
 
 _libs = {}
@@ -202,6 +204,8 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_skinny_gemm_ex": [vp, C.POINTER(A2PSkinnyCase), i32, vp],
         "a2p_dataset_batch": [C.POINTER(A2PDatasetTake), i32, i32, i32, C.POINTER(i32), C.POINTER(i64), i32, i32, i32, i32, vp, vp,
                               f32, f32, f32, i32, vp, vp, vp, vp, vp],
+        "a2p_skin_states": [vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
+        "a2p_skin_vertices": [vp, i64, i32, vp, vp, i32, vp, vp, i32, i32, f32, f32, f32, vp, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

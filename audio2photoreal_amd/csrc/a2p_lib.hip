@@ -36,6 +36,7 @@
 #include "kernels_inpaint.h"
 #include "kernels_misc.h"
 #include "kernels_multistep.h"
+#include "kernels_skin.h"
 #include "kernels_small.h"
 #include "kernels_tail.h"
 #include "kernels_vq.h"
@@ -1018,3 +1019,4 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_frontend.h"
 #include "a2p_eval.h"
 #include "a2p_dataset.h"
+#include "a2p_skin.h"

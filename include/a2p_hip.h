@@ -559,6 +559,33 @@ int a2p_dataset_batch(const a2p_dataset_take* takes, int32_t n_takes, int32_t ch
                       float audio_std, int32_t swap_channels, float* inp, float* keyframes, float* missing, float* audio,
                       void* stream);
 
+/* ---- posed geometry (reference visualize/ca_body/utils/lbs.py; audio2photoreal_amd/skinning.py) -------------------------------
+ * From un-normalised body poses to joint states, skinning matrices and posed vertices, fp32 like the reference, for all N frames
+ * in one launch each.  Context-free; the skeleton tables are device arrays built and validated once by the caller.  No atomics
+ * and a fixed summation order: a frame's result depends on neither N nor its index, and two runs give the same bits.
+ *
+ * a2p_skin_states: x = cat(pose [N, P_pos], scale [N or 1, P_scale]) (scale_per_frame = 0 shares row 0; P_scale = 0: no scale
+ * parameters); the [7 J, P] parameter transform as compressed rows (row_ptr [7 J + 1], cols / vals ascending in the column) plus
+ * offsets [7 J] gives (tx ty tz rx ry rz sc) per joint; local t = value + joint_offset [J, 3], q = pre_rotation [J, 4] (xyzw)
+ * (x) fromXYZ(r) with half angles (-0.5, 0.5, 0.5), s = exp2(sc); the joints are solved level by level (order [J]: joints sorted
+ * by depth, level_start [n_levels + 1]; parents [J] int32, -1 for a root; every parent sits in an earlier level).  Outputs, either
+ * may be NULL: states [N, J, 8] (translation 3, quaternion xyzw 4, scale 1: solve_skeleton_state) and mats [N, J, 3, 4]
+ * (states_to_matrix) against inv_bind [J, 8] = (rot(bind_q^-1, -bind_t) / bind_s, bind_q^-1, 1 / bind_s).
+ *
+ * a2p_skin_vertices: out [N, V, 3] = (sum over k < K of w[k][v] mats[n][idx[k][v]] [p, 1]) * (gx, gy, gz) with p = base [V, 3]
+ * + unposed (NULL, [V, 3] when unposed_per_frame = 0, else [N, V, 3]).  idx (int32, in [0, J)) and w are stored [K, V]; unused
+ * slots hold weight 0. */
+#define A2P_SKIN_MAX_JOINTS 1024
+#define A2P_SKIN_MAX_PARAMS 1024
+#define A2P_SKIN_MAX_INFLUENCES 16
+int a2p_skin_states(const float* pose, const float* scale, int32_t scale_per_frame, int64_t N, int32_t P_pos, int32_t P_scale,
+                    int32_t J, const int32_t* row_ptr, const int32_t* cols, const float* vals, const float* offsets,
+                    const float* joint_offset, const float* pre_rotation, const int32_t* parents, const int32_t* order,
+                    const int32_t* level_start, int32_t n_levels, const float* inv_bind, float* states, float* mats, void* stream);
+int a2p_skin_vertices(const float* mats, int64_t N, int32_t J, const float* base, const float* unposed, int32_t unposed_per_frame,
+                      const int32_t* idx, const float* w, int32_t V, int32_t K, float gx, float gy, float gz, float* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
