@@ -47,6 +47,7 @@ EXPORTS = (
     "a2p_resample_channels", "a2p_conversation_audio", "a2p_dataset_batch",
     "a2p_gemm_ex", "a2p_skinny_gemm_ex",
     "a2p_skin_states", "a2p_skin_vertices",
+    "a2p_surface_normals", "a2p_surface_to_uv", "a2p_surface_from_uv", "a2p_surface_uv_index",
 )
 
 
@@ -122,6 +123,7 @@ NORMALIZE_NONE, NORMALIZE_PEAK = 0, 1 # A2P_NORMALIZE_*
 WINDOW_MAX = 256                      # A2P_WINDOW_MAX
 DATASET_MAX_BATCH = 64                # A2P_DATASET_MAX_BATCH
 SKIN_MAX_JOINTS, SKIN_MAX_PARAMS, SKIN_MAX_INFLUENCES = 1024, 1024, 16   # A2P_SKIN_MAX_*
+SURFACE_MAX_UV, SURFACE_MAX_CHANNELS = 16384, 16                         # A2P_SURFACE_MAX_* (3 H H fits in int32)
 
 
 _libs = {}
@@ -206,6 +208,10 @@ def load(half: bool = False) -> C.CDLL:
                               f32, f32, f32, i32, vp, vp, vp, vp, vp],
         "a2p_skin_states": [vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
         "a2p_skin_vertices": [vp, i64, i32, vp, vp, i32, vp, vp, i32, i32, f32, f32, f32, vp, vp],
+        "a2p_surface_normals": [vp, i64, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp],
+        "a2p_surface_to_uv": [vp, i64, i32, i32, vp, vp, i32, vp, vp],
+        "a2p_surface_from_uv": [vp, i64, i32, i32, i32, vp, i32, vp, i32, vp, vp],
+        "a2p_surface_uv_index": [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

@@ -38,6 +38,7 @@
 #include "kernels_multistep.h"
 #include "kernels_skin.h"
 #include "kernels_small.h"
+#include "kernels_surface.h"
 #include "kernels_tail.h"
 #include "kernels_vq.h"
 #include "kernels_window.h"
@@ -1020,3 +1021,4 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_eval.h"
 #include "a2p_dataset.h"
 #include "a2p_skin.h"
+#include "a2p_surface.h"

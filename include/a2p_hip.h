@@ -586,6 +586,40 @@ int a2p_skin_vertices(const float* mats, int64_t N, int32_t J, const float* base
                       const int32_t* idx, const float* w, int32_t V, int32_t K, float gx, float gy, float gz, float* out,
                       void* stream);
 
+/* ---- surface maps (reference visualize/ca_body/utils/geom.py; audio2photoreal_amd/surface.py) ---------------------------------
+ * Normals, view cosine and UV maps of the posed mesh, fp32 like the reference, for all N frames in one launch each.  Context-free;
+ * the topology tables are device arrays built and validated once by the caller (vi / vti [F, 3] int32 with entries in [0, V) /
+ * [0, T), vt [T, 2]).  No float atomics and a fixed summation order: a frame's result depends on neither N nor its index, and two
+ * runs give the same bits.  An output must not alias an input.
+ *
+ * a2p_surface_normals: verts [N, V, 3] -> normals [N, V, 3] (vert_normals) and view_cos [N, V] (compute_view_cos; camera [N, 3]
+ * when camera_per_frame, else [1, 3]); either output may be NULL, view_cos needs the camera.  inc_ptr [V + 1] / inc_face: the
+ * faces of vertex v, ascending in the face and then the corner (a face that lists v twice appears twice; an unused vertex has an
+ * empty range and gets normal 0).  The face normals cross(p1 - p0, p2 - p0) are normalised (a length below 1e-5 counts as 1),
+ * summed in table order and normalised by the same rule.
+ *
+ * a2p_surface_to_uv: values [N, V, C] -> out [N, C, H, H] (values_to_uv): b0 x[i0] + b1 x[i1] + b2 x[i2] where the texel's three
+ * entries of index_image [H, H, 3] (int32, in [-1, V)) all differ from -1, else 0; bary_image [H, H, 3].  Every texel is written.
+ *
+ * a2p_surface_from_uv: values_uv [N, C, H', W'] -> out [N, V, C] (sample_uv as GeometryModule.from_uv calls it): the mean over
+ * the 4 slots of v2uv [V, 4] (int32, in [0, T)) of the bilinear sample at vt[slot] (align_corners, zero padding).
+ *
+ * a2p_surface_uv_index: the one-time UV rasterisation at H x H: texel (row i, column j) has centre ((j + 0.5) / H, (i + 0.5) / H);
+ * a face covers it when the centre is inside or on the boundary of its UV triangle; a zero-area triangle covers nothing; the
+ * lowest covering face wins.  face_image [H, H] (-1: none), index_image [H, H, 3] = vi[face] (-1) and bary_image [H, H, 3] = the
+ * reference's bary_coords of the centre (0).  All three images are required and written whole. */
+#define A2P_SURFACE_MAX_UV 16384
+#define A2P_SURFACE_MAX_CHANNELS 16
+int a2p_surface_normals(const float* verts, int64_t N, int32_t V, const int32_t* vi, int32_t F, const int32_t* inc_ptr,
+                        const int32_t* inc_face, const float* camera, int32_t camera_per_frame, float* normals, float* view_cos,
+                        void* stream);
+int a2p_surface_to_uv(const float* values, int64_t N, int32_t V, int32_t C, const int32_t* index_image, const float* bary_image,
+                      int32_t H, float* out, void* stream);
+int a2p_surface_from_uv(const float* values_uv, int64_t N, int32_t C, int32_t Hs, int32_t Ws, const float* vt, int32_t T,
+                        const int32_t* v2uv, int32_t V, float* out, void* stream);
+int a2p_surface_uv_index(const float* vt, int32_t T, const int32_t* vti, const int32_t* vi, int32_t F, int32_t H,
+                         int32_t* index_image, float* bary_image, int32_t* face_image, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
