@@ -48,6 +48,7 @@ EXPORTS = (
     "a2p_gemm_ex", "a2p_skinny_gemm_ex",
     "a2p_skin_states", "a2p_skin_vertices",
     "a2p_surface_normals", "a2p_surface_to_uv", "a2p_surface_from_uv", "a2p_surface_uv_index",
+    "a2p_render_rasterize", "a2p_render_interpolate", "a2p_render_texture",
 )
 
 
@@ -124,6 +125,7 @@ WINDOW_MAX = 256                      # A2P_WINDOW_MAX
 DATASET_MAX_BATCH = 64                # A2P_DATASET_MAX_BATCH
 SKIN_MAX_JOINTS, SKIN_MAX_PARAMS, SKIN_MAX_INFLUENCES = 1024, 1024, 16   # A2P_SKIN_MAX_*
 SURFACE_MAX_UV, SURFACE_MAX_CHANNELS = 16384, 16                         # A2P_SURFACE_MAX_* (3 H H fits in int32)
+RENDER_MAX_SIZE, RENDER_MAX_CHANNELS = 8192, 16                          # A2P_RENDER_MAX_*
 
 
 _libs = {}
@@ -212,6 +214,9 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_surface_to_uv": [vp, i64, i32, i32, vp, vp, i32, vp, vp],
         "a2p_surface_from_uv": [vp, i64, i32, i32, i32, vp, i32, vp, i32, vp, vp],
         "a2p_surface_uv_index": [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp],
+        "a2p_render_rasterize": [vp, i64, i32, vp, i32, vp, i32, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp],
+        "a2p_render_interpolate": [vp, i64, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp],
+        "a2p_render_texture": [vp, vp, i64, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

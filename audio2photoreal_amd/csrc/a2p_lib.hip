@@ -36,6 +36,7 @@
 #include "kernels_inpaint.h"
 #include "kernels_misc.h"
 #include "kernels_multistep.h"
+#include "kernels_render.h"
 #include "kernels_skin.h"
 #include "kernels_small.h"
 #include "kernels_surface.h"
@@ -1022,3 +1023,4 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_dataset.h"
 #include "a2p_skin.h"
 #include "a2p_surface.h"
+#include "a2p_render.h"

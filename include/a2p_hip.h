@@ -620,6 +620,39 @@ int a2p_surface_from_uv(const float* values_uv, int64_t N, int32_t C, int32_t Hs
 int a2p_surface_uv_index(const float* vt, int32_t T, const int32_t* vti, const int32_t* vi, int32_t F, int32_t H,
                          int32_t* index_image, float* bary_image, int32_t* face_image, void* stream);
 
+/* ---- rendered images (reference visualize/ca_body/utils/render.py RenderLayer; audio2photoreal_amd/render.py) -----------------
+ * The posed mesh rasterised to images, fp32 like the reference, all N frames of a call in a fixed number of launches.  Context-
+ * free; vi / vti [F, 3] int32 with entries in [0, V) / [0, T) and vt [T, 2] are device arrays validated once by the caller.  The
+ * only atomic is a 64-bit integer minimum: a frame's result depends on neither N nor its index, and two runs give the same bits.
+ * An output or scratch array must not alias an input.  N = 0 returns 0 without a launch.
+ *
+ * a2p_render_rasterize: verts [N, V, 3]; Rt [N, 3, 4] when rt_per_frame, else [1, 3, 4]; K [N, 3, 3] when k_per_frame, else [1,
+ * 3, 3] (OpenCV: x right, y down, z forward).  p = R x + t, u = K00 (x / z) + K01 (y / z) + K02, v = K11 (y / z) + K12 (the skew
+ * K01 is supported; the other entries are not read).  Pixel (row i, column j) has centre (j + 0.5, i + 0.5); a face covers it when
+ * the centre is inside or on the boundary of the projected triangle (either winding; zero area covers nothing); a face with a
+ * corner at z < near (near > 0) is dropped whole.  Depth is perspective-correct, 1 / z = sum of b_k / z_k over the screen
+ * barycentrics b; the nearest face wins, the lowest face index among equal depth bits; a pixel whose depth is not a positive
+ * finite number is not covered.  Scratch, contents undefined on return: proj [N, V, 3] float and key [N, H, W] 64-bit words.
+ * Outputs, each may be NULL and the others are written whole: face [N, H, W] (-1: background), bary [N, H, W, 3] (perspective-
+ * correct, b_k' = (b_k / z_k) / sum of b_j / z_j; 0) and depth [N, H, W] (0).
+ *
+ * a2p_render_interpolate: values [N, V, C] -> out [N, C, H, W] = b0 x[i0] + b1 x[i1] + b2 x[i2] with (i0, i1, i2) = vi[face]
+ * and the pixel's bary; 0 where face is outside [0, F).
+ *
+ * a2p_render_texture: pixel uv = sum of b_k vt[vti[face][k]] (v <- 1 - v when flip_v), bilinear sample of tex ([N, C, Ht, Wt]
+ * when tex_per_frame, else [1, C, Ht, Wt]) at x = u (Wt - 1), y = v (Ht - 1) clamped to the border, taps nw, ne, sw, se summed in
+ * that order -> out [N, C, H, W]; 0 where face is outside [0, F). */
+#define A2P_RENDER_MAX_SIZE 8192
+#define A2P_RENDER_MAX_CHANNELS 16
+int a2p_render_rasterize(const float* verts, int64_t N, int32_t V, const int32_t* vi, int32_t F, const float* K, int32_t k_per_frame,
+                         const float* Rt, int32_t rt_per_frame, int32_t H, int32_t W, float near, float* proj, uint64_t* key,
+                         int32_t* face, float* bary, float* depth, void* stream);
+int a2p_render_interpolate(const float* values, int64_t N, int32_t V, int32_t C, const int32_t* vi, int32_t F, const int32_t* face,
+                           const float* bary, int32_t H, int32_t W, float* out, void* stream);
+int a2p_render_texture(const int32_t* face, const float* bary, int64_t N, int32_t H, int32_t W, const float* vt, int32_t T,
+                       const int32_t* vti, int32_t F, const float* tex, int32_t tex_per_frame, int32_t C, int32_t Ht, int32_t Wt,
+                       int32_t flip_v, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
