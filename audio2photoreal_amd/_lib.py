@@ -49,6 +49,7 @@ EXPORTS = (
     "a2p_skin_states", "a2p_skin_vertices",
     "a2p_surface_normals", "a2p_surface_to_uv", "a2p_surface_from_uv", "a2p_surface_uv_index",
     "a2p_render_rasterize", "a2p_render_interpolate", "a2p_render_texture",
+    "a2p_conv2d_ub", "a2p_seam_impaint", "a2p_seam_resample",
 )
 
 
@@ -94,6 +95,20 @@ class A2PSkinnyCase(C.Structure):
                 + [(n, C.c_int32) for n in ("M", "N", "K", "act")])
 
 
+class A2PConvSource(C.Structure):
+    """a2p_conv_source (include/a2p_hip.h "decoder layers"): a tensor [N, C, H, W] with frames frame_stride floats apart."""
+    _fields_ = [("data", C.c_void_p), ("frame_stride", C.c_int64), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class A2PConv2dDesc(C.Structure):
+    """a2p_conv2d_desc (include/a2p_hip.h): one launch of a2p_conv2d_ub."""
+    _fields_ = ([("x", A2PConvSource), ("skip_src", A2PConvSource)]
+                + [(n, C.c_void_p) for n in ("weight", "bias", "skip", "skip_weight", "skip_bias", "mask", "out")] + [("N", C.c_int64)]
+                + [(n, C.c_int32) for n in ("C_out", "H", "W", "k", "groups", "bias_mode", "act", "skip_mode")]
+                + [("slope", C.c_float), ("reserved", C.c_int32)])
+
+
 EPI_STORE, EPI_STORE_T, EPI_FILM_RES, EPI_CONV = 0, 1, 2, 3                          # csrc/kernels_gemm.h
 ACT_NONE, ACT_GELU, ACT_MISH, ACT_SILU, ACT_LRELU, ACT_RELU = 0, 1, 2, 3, 4, 5       # csrc/a2p_common.h
 
@@ -126,6 +141,9 @@ DATASET_MAX_BATCH = 64                # A2P_DATASET_MAX_BATCH
 SKIN_MAX_JOINTS, SKIN_MAX_PARAMS, SKIN_MAX_INFLUENCES = 1024, 1024, 16   # A2P_SKIN_MAX_*
 SURFACE_MAX_UV, SURFACE_MAX_CHANNELS = 16384, 16                         # A2P_SURFACE_MAX_* (3 H H fits in int32)
 RENDER_MAX_SIZE, RENDER_MAX_CHANNELS = 8192, 16                          # A2P_RENDER_MAX_*
+CONV_MAX_CHANNELS, CONV_MAX_SIZE = 4096, 16384                           # A2P_CONV_MAX_* (channels per group; plane side)
+CONV_BIAS_NONE, CONV_BIAS_TIED, CONV_BIAS_UNTIED = 0, 1, 2               # A2P_CONV_BIAS_*
+CONV_SKIP_NONE, CONV_SKIP_TENSOR, CONV_SKIP_CONV = 0, 1, 2               # A2P_CONV_SKIP_*
 
 
 _libs = {}
@@ -217,6 +235,9 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_render_rasterize": [vp, i64, i32, vp, i32, vp, i32, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp],
         "a2p_render_interpolate": [vp, i64, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp],
         "a2p_render_texture": [vp, vp, i64, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp],
+        "a2p_conv2d_ub": [C.POINTER(A2PConv2dDesc), vp],
+        "a2p_seam_impaint": [vp, i64, i32, i32, vp, vp, i32, vp, vp],
+        "a2p_seam_resample": [vp, i64, i32, i32, vp, vp, vp, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

@@ -30,6 +30,7 @@
 #include "kernels_audio.h"
 #include "kernels_chain.h"
 #include "kernels_chain4.h"
+#include "kernels_conv.h"
 #include "kernels_dataset.h"
 #include "kernels_eval.h"
 #include "kernels_gemm.h"
@@ -1024,3 +1025,4 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_skin.h"
 #include "a2p_surface.h"
 #include "a2p_render.h"
+#include "a2p_conv.h"

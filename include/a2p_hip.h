@@ -653,6 +653,64 @@ int a2p_render_texture(const int32_t* face, const float* bary, int64_t N, int32_
                        const int32_t* vti, int32_t F, const float* tex, int32_t tex_per_frame, int32_t C, int32_t Ht, int32_t Wt,
                        int32_t flip_v, float* out, void* stream);
 
+/* ---- decoder layers (reference visualize/ca_body/nn/layers.py, nn/blocks.py, utils/seams.py; audio2photoreal_amd/decoder.py) --
+ * The layer family of the body renderer's networks, fp32 like the reference, on the caller's stream.  Context-free: weights
+ * (already folded, w = v g / ||v||), biases, masks and seam tables are device arrays the caller prepared once.  No atomics and a
+ * fixed summation order: a frame's result depends on neither N nor its index, and two runs give the same bits.  An output must
+ * not overlap an input.  N = 0 (planes = 0) returns 0 without a launch.
+ *
+ * a2p_conv2d_ub: direct convolution for few channels; NCHW, stride 1, zero padding k / 2, k = 1 or 3, groups >= 1 with at most
+ * A2P_CONV_MAX_CHANNELS input and output channels per group.  Per output element, in this order:
+ *   v = sum over ci ascending, then ky, kx row-major, of weight[oc][ci][ky][kx] x[n][g C_in/groups + ci][y + ky - k/2][x + kx - k/2]
+ *   v = v + bias                    bias_mode TIED: bias [C_out]; UNTIED: bias [C_out, H, W]
+ *   v = v >= 0 ? v : slope v        when act
+ *   v = v + skip                    skip_mode TENSOR: skip [N, C_out, H, W]; CONV: skip_bias[oc] (0 when NULL) + sum over cs
+ *                                   ascending of skip_weight[oc][cs] skip_src[n][g C_s/groups + cs][y][x] (a 1 x 1 convolution
+ *                                   with the same `groups`; skip_weight [C_out, C_s / groups])
+ *   out = v * mask[y][x]            when mask [H, W] is given
+ * A source (x, skip_src) is [N, C, Hs, Ws] with frames frame_stride floats apart (>= C Hs Ws: a channel window of a larger
+ * tensor is a source).  When (Hs, Ws) differs from (H, W) it is read through nn.UpsamplingBilinear2d((H, W)) -- bilinear,
+ * align_corners = True, any ratio: src = dst (Hs - 1) / (H - 1) in float32, i0 = min((int)src, Hs - 1), i1 = min(i0 + 1, Hs - 1),
+ * l = src - i0, value = (1 - ly) ((1 - lx) a00 + lx a01) + ly ((1 - lx) a10 + lx a11) -- and the upsampled tensor is never
+ * written.  out [N, C_out, H, W] is written whole.
+ *
+ * a2p_seam_impaint: SeamSampler.impaint on value [planes, H, W] in place: value[p][dst[i]] = (value before the call)[p][src[i]]
+ * for the P pairs of flat texel indices in [0, H W); dst holds a texel at most once.  scratch: planes * P floats, contents
+ * undefined on return.
+ *
+ * a2p_seam_resample: SeamSampler.resample, out of place: out = (1 - w) tex + w s with s the grid_sample (bilinear, align_corners
+ * = False, padding_mode border) of the plane at g = 2 (uv - 0.5); uvs [H, W, 2] (u along x), weights [H, W].  x = ((g + 1) W -
+ * 1) / 2 clamped to [0, W - 1]; the taps nw, ne, sw, se are summed in that order. */
+#define A2P_CONV_MAX_CHANNELS 4096
+#define A2P_CONV_MAX_SIZE 16384
+enum { A2P_CONV_BIAS_NONE = 0, A2P_CONV_BIAS_TIED = 1, A2P_CONV_BIAS_UNTIED = 2 };
+enum { A2P_CONV_SKIP_NONE = 0, A2P_CONV_SKIP_TENSOR = 1, A2P_CONV_SKIP_CONV = 2 };
+typedef struct a2p_conv_source {
+  const float* data;
+  int64_t frame_stride;
+  int32_t C, H, W, reserved;
+} a2p_conv_source;
+typedef struct a2p_conv2d_desc {
+  a2p_conv_source x;
+  a2p_conv_source skip_src;
+  const float* weight;
+  const float* bias;
+  const float* skip;
+  const float* skip_weight;
+  const float* skip_bias;
+  const float* mask;
+  float* out;
+  int64_t N;
+  int32_t C_out, H, W, k, groups, bias_mode, act, skip_mode;
+  float slope;
+  int32_t reserved;
+} a2p_conv2d_desc;
+int a2p_conv2d_ub(const a2p_conv2d_desc* desc, void* stream);
+int a2p_seam_impaint(float* value, int64_t planes, int32_t H, int32_t W, const int32_t* dst, const int32_t* src, int32_t P,
+                     float* scratch, void* stream);
+int a2p_seam_resample(const float* tex, int64_t planes, int32_t H, int32_t W, const float* uvs, const float* weights, float* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
