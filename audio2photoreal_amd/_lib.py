@@ -50,6 +50,7 @@ EXPORTS = (
     "a2p_surface_normals", "a2p_surface_to_uv", "a2p_surface_from_uv", "a2p_surface_uv_index",
     "a2p_render_rasterize", "a2p_render_interpolate", "a2p_render_texture",
     "a2p_conv2d_ub", "a2p_seam_impaint", "a2p_seam_resample",
+    "a2p_conv2d_down_ub", "a2p_conv_transpose2d_ub", "a2p_resize_bilinear", "a2p_texture_compose",
 )
 
 
@@ -109,6 +110,12 @@ class A2PConv2dDesc(C.Structure):
                 + [("slope", C.c_float), ("reserved", C.c_int32)])
 
 
+class A2PTexConvDesc(C.Structure):
+    """a2p_tex_conv_desc (include/a2p_hip.h "texture layers"): one launch of a2p_conv2d_down_ub or a2p_conv_transpose2d_ub."""
+    _fields_ = ([("x", A2PConvSource)] + [(n, C.c_void_p) for n in ("weight", "bias", "skip", "out")] + [("N", C.c_int64)]
+                + [(n, C.c_int32) for n in ("C_out", "bias_mode", "act")] + [("slope", C.c_float), ("beta", C.c_float), ("reserved", C.c_int32)])
+
+
 EPI_STORE, EPI_STORE_T, EPI_FILM_RES, EPI_CONV = 0, 1, 2, 3                          # csrc/kernels_gemm.h
 ACT_NONE, ACT_GELU, ACT_MISH, ACT_SILU, ACT_LRELU, ACT_RELU = 0, 1, 2, 3, 4, 5       # csrc/a2p_common.h
 
@@ -144,6 +151,7 @@ RENDER_MAX_SIZE, RENDER_MAX_CHANNELS = 8192, 16                          # A2P_R
 CONV_MAX_CHANNELS, CONV_MAX_SIZE = 4096, 16384                           # A2P_CONV_MAX_* (channels per group; plane side)
 CONV_BIAS_NONE, CONV_BIAS_TIED, CONV_BIAS_UNTIED = 0, 1, 2               # A2P_CONV_BIAS_*
 CONV_SKIP_NONE, CONV_SKIP_TENSOR, CONV_SKIP_CONV = 0, 1, 2               # A2P_CONV_SKIP_*
+TEX_ACT_NONE, TEX_ACT_LRELU, TEX_ACT_SIGMOID = 0, 1, 2                   # A2P_TEX_ACT_*
 
 
 _libs = {}
@@ -238,6 +246,10 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_conv2d_ub": [C.POINTER(A2PConv2dDesc), vp],
         "a2p_seam_impaint": [vp, i64, i32, i32, vp, vp, i32, vp, vp],
         "a2p_seam_resample": [vp, i64, i32, i32, vp, vp, vp, vp],
+        "a2p_conv2d_down_ub": [C.POINTER(A2PTexConvDesc), vp],
+        "a2p_conv_transpose2d_ub": [C.POINTER(A2PTexConvDesc), vp],
+        "a2p_resize_bilinear": [vp, i64, i32, i32, i32, i32, vp, vp],
+        "a2p_texture_compose": [vp, vp, vp, f32, vp, i32, i64, i32, i32, i32, vp, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

@@ -31,6 +31,7 @@
 #include "kernels_chain.h"
 #include "kernels_chain4.h"
 #include "kernels_conv.h"
+#include "kernels_texture.h"
 #include "kernels_dataset.h"
 #include "kernels_eval.h"
 #include "kernels_gemm.h"
@@ -1026,3 +1027,4 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_surface.h"
 #include "a2p_render.h"
 #include "a2p_conv.h"
+#include "a2p_texture.h"
