@@ -5,6 +5,7 @@ forward_tex -- as HIP launches for all frames (csrc/kernels_texture.h), and line
     python -m audio2photoreal_amd.texture --results results.npy --embeddings embs.npz --assets static_assets.pt
                                           --checkpoint body_dec.ckpt --out frames.npy [--size H W]
                                           [--camera-json FILE | --eye X Y Z --target X Y Z --fov D] [--frames A:B] [--png-dir DIR]
+                                          [--uv-size S --n-init-ftrs F --upscale-n-ftrs F --pose-to-shadow-dims P --n-embs E ...]
 
 `conv2d_down_ub`, `conv_transpose2d_ub`, `resize_bilinear` and `compose_texture` are one launch each of the four exports of the
 "texture layers" of include/a2p_hip.h.  `ViewUNet`, `PoseShadow` and `UpscaleNet` are the reference's networks built from its state
@@ -548,6 +549,9 @@ def main(argv=None) -> int:
     ap.add_argument("--n-init-ftrs", type=int, default=8)
     ap.add_argument("--upscale-n-ftrs", type=int, default=8)
     ap.add_argument("--pose-to-shadow-dims", type=int, default=104)
+    for name, default in (("n-pose-enc-channels", 16), ("n-embs", 1024), ("n-embs-enc-channels", 32), ("n-face-embs", 256),
+                          ("n-init-channels", 64), ("n-min-channels", 4)):     # the rest of the decoder's configuration, as in decoder.main
+        ap.add_argument(f"--{name}", type=int, default=default)
     args = ap.parse_args(argv)
     from .decoder import BodyDecoder
     from .skinning import BodySkeleton
@@ -573,7 +577,10 @@ def main(argv=None) -> int:
     assets = torch.load(args.assets, map_location="cpu", weights_only=False)
     state = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
     surface = BodySurface.from_static_assets(assets, uv_size=args.uv_size)
-    decoder = BodyDecoder.from_state_dict(state, assets, surface, uv_size=args.uv_size, n_pose_dims=args.pose_to_shadow_dims - 6)
+    decoder = BodyDecoder.from_state_dict(
+        state, assets, surface, uv_size=args.uv_size, n_pose_dims=args.pose_to_shadow_dims - 6, n_pose_enc_channels=args.n_pose_enc_channels,
+        n_embs=args.n_embs, n_embs_enc_channels=args.n_embs_enc_channels, n_face_embs=args.n_face_embs, n_init_channels=args.n_init_channels,
+        n_min_channels=args.n_min_channels)
     texture = BodyTexture.from_state_dict(state, assets, surface, uv_size=args.uv_size, n_init_ftrs=args.n_init_ftrs,
                                           upscale_n_ftrs=args.upscale_n_ftrs, pose_to_shadow_dims=args.pose_to_shadow_dims)
     skeleton = BodySkeleton.from_static_assets(assets)

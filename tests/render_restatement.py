@@ -48,6 +48,12 @@ def project(verts, K, Rt, dtype=np.float64):
     return np.stack([u, v, zc], -1)
 
 
+def camera_centre(Rt, dtype=np.float64):
+    """[N, 3] = -R^T t of Rt [N, 3, 4]: the camera position in world coordinates."""
+    Rt = np.asarray(Rt, dtype).reshape(-1, 3, 4)
+    return -np.einsum("nrc,nr->nc", Rt[:, :, :3], Rt[:, :, 3]).astype(dtype)
+
+
 # ------------------------------------------------------------------------------------------------ the z-buffer
 def _face_pixels(a, b, c, H, W, dtype):
     """(rows, columns, w0, w1, w2, inside) over the pixels whose centre lies in the corners' box; None when there are none."""
@@ -165,25 +171,33 @@ def sample_texture(tex, vt, vti, face, bary, flip_uv=False, dtype=np.float64):
 
 
 # ------------------------------------------------------------------------------------------------ clearances
-def edge_clearance(verts, vi, K, Rt, H, W, near=NEAR):
-    """The smallest distance in pixels (float64) from any pixel centre of the H x W image to any projected edge of a kept face of
-    any frame.  Above the float32 error of the projected coordinates, no rule and no precision can disagree on a pixel's cover."""
+def edge_distance(verts, vi, K, Rt, H, W, near=NEAR):
+    """[N, H, W] float64: the distance in pixels from each pixel centre to the nearest projected edge of a kept face of its frame;
+    inf for a centre more than a pixel outside the box of every edge (it is then at least a pixel away from all of them)."""
     vi = np.asarray(vi)
     proj = project(verts, K, Rt)
-    best = np.inf
+    out = np.full((len(proj), H, W), np.inf)
     cj, ci = np.arange(W) + 0.5, np.arange(H) + 0.5
     for n in range(len(proj)):
         t = vi[kept_faces(proj[n], vi, near)]
         edges = np.unique(np.sort(np.concatenate([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]]), axis=1), axis=0)
         for a, b in proj[n, edges][:, :, :2]:
             lo, hi = np.minimum(a, b) - 1, np.maximum(a, b) + 1
-            px, py = cj[(cj >= lo[0]) & (cj <= hi[0])][None, :], ci[(ci >= lo[1]) & (ci <= hi[1])][:, None]
-            if not px.size or not py.size:
+            js, is_ = np.nonzero((cj >= lo[0]) & (cj <= hi[0]))[0], np.nonzero((ci >= lo[1]) & (ci <= hi[1]))[0]
+            if not js.size or not is_.size:
                 continue
+            px, py = cj[js][None, :], ci[is_][:, None]
             ab = b - a
             s = np.clip(((px - a[0]) * ab[0] + (py - a[1]) * ab[1]) / (ab @ ab), 0, 1)
-            best = min(best, float(np.sqrt((px - a[0] - s * ab[0]) ** 2 + (py - a[1] - s * ab[1]) ** 2).min()))
-    return best
+            block = (n, slice(is_[0], is_[-1] + 1), slice(js[0], js[-1] + 1))
+            out[block] = np.minimum(out[block], np.sqrt((px - a[0] - s * ab[0]) ** 2 + (py - a[1] - s * ab[1]) ** 2))
+    return out
+
+
+def edge_clearance(verts, vi, K, Rt, H, W, near=NEAR):
+    """The smallest distance in pixels (float64) from any pixel centre of the H x W image to any projected edge of a kept face of
+    any frame.  Above the float32 error of the projected coordinates, no rule and no precision can disagree on a pixel's cover."""
+    return float(edge_distance(verts, vi, K, Rt, H, W, near).min())
 
 
 def depth_clearance(fragments):
