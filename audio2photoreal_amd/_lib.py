@@ -51,6 +51,7 @@ EXPORTS = (
     "a2p_render_rasterize", "a2p_render_interpolate", "a2p_render_texture",
     "a2p_conv2d_ub", "a2p_seam_impaint", "a2p_seam_resample",
     "a2p_conv2d_down_ub", "a2p_conv_transpose2d_ub", "a2p_resize_bilinear", "a2p_texture_compose",
+    "a2p_linear_f32", "a2p_conv2d_down3_ub", "a2p_unskin_vertices", "a2p_face_tex_cond",
 )
 
 
@@ -116,6 +117,12 @@ class A2PTexConvDesc(C.Structure):
                 + [(n, C.c_int32) for n in ("C_out", "bias_mode", "act")] + [("slope", C.c_float), ("beta", C.c_float), ("reserved", C.c_int32)])
 
 
+class A2PDown3Desc(C.Structure):
+    """a2p_down3_desc (include/a2p_hip.h "encode layers"): one launch of a2p_conv2d_down3_ub."""
+    _fields_ = ([("h", A2PConvSource), ("x", A2PConvSource)] + [(n, C.c_void_p) for n in ("w2", "b2", "wr", "br", "out")]
+                + [("N", C.c_int64), ("C_out", C.c_int32), ("slope", C.c_float)])
+
+
 EPI_STORE, EPI_STORE_T, EPI_FILM_RES, EPI_CONV = 0, 1, 2, 3                          # csrc/kernels_gemm.h
 ACT_NONE, ACT_GELU, ACT_MISH, ACT_SILU, ACT_LRELU, ACT_RELU = 0, 1, 2, 3, 4, 5       # csrc/a2p_common.h
 
@@ -152,6 +159,7 @@ CONV_MAX_CHANNELS, CONV_MAX_SIZE = 4096, 16384                           # A2P_C
 CONV_BIAS_NONE, CONV_BIAS_TIED, CONV_BIAS_UNTIED = 0, 1, 2               # A2P_CONV_BIAS_*
 CONV_SKIP_NONE, CONV_SKIP_TENSOR, CONV_SKIP_CONV = 0, 1, 2               # A2P_CONV_SKIP_*
 TEX_ACT_NONE, TEX_ACT_LRELU, TEX_ACT_SIGMOID = 0, 1, 2                   # A2P_TEX_ACT_*
+LINEAR_KSLICE = 256                                                      # A2P_LINEAR_KSLICE
 
 
 _libs = {}
@@ -250,6 +258,10 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_conv_transpose2d_ub": [C.POINTER(A2PTexConvDesc), vp],
         "a2p_resize_bilinear": [vp, i64, i32, i32, i32, i32, vp, vp],
         "a2p_texture_compose": [vp, vp, vp, f32, vp, i32, i64, i32, i32, i32, vp, vp],
+        "a2p_linear_f32": [vp, i64, vp, vp, i64, i32, i32, i32, f32, vp, i64, vp, i64, vp],
+        "a2p_conv2d_down3_ub": [C.POINTER(A2PDown3Desc), vp],
+        "a2p_unskin_vertices": [vp, i64, i32, vp, vp, vp, vp, i32, i32, f32, f32, f32, vp, vp],
+        "a2p_face_tex_cond": [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

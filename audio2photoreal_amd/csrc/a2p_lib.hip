@@ -32,6 +32,7 @@
 #include "kernels_chain4.h"
 #include "kernels_conv.h"
 #include "kernels_texture.h"
+#include "kernels_encode.h"
 #include "kernels_dataset.h"
 #include "kernels_eval.h"
 #include "kernels_gemm.h"
@@ -1028,3 +1029,4 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_render.h"
 #include "a2p_conv.h"
 #include "a2p_texture.h"
+#include "a2p_encode.h"

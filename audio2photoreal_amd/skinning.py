@@ -365,6 +365,35 @@ class BodySkeleton:
         [V, 3], [1, V, 3] or [N, V, 3]."""
         return self.skin(self._solve(poses, scales, False, True)[1], verts_unposed)
 
+    def unpose_vertices(self, poses, verts, scales=None):
+        """[N, V, 3] = LBSModule.unpose: the displacement from the template (the rest vertices when the skeleton has no template)
+        that pose_vertices maps to `verts` [N, V, 3]: verts / global_scaling goes through the inverse of each vertex's blended
+        skinning matrix and the template is subtracted.  The inverse is the closed-form adjugate over the determinant in fp32 (the
+        reference calls Tensor.inverse() on the 4 x 4 matrix).  A singular or non-finite blend gives a non-finite result: the
+        output is checked once per call, and A2PError names the first bad frame and vertex."""
+        mats, t = self._solve(poses, scales, False, True)[1:]
+        N, dev = mats.shape[0], mats.device
+        if not torch.is_tensor(verts):
+            raise A2PError(f"verts must be a tensor on the MI355X (got {type(verts).__name__})")
+        _lib.require_gpu_tensor(verts, "verts")
+        if verts.device != dev:
+            raise A2PError(f"verts is on {verts.device}, poses on {dev}")
+        if tuple(verts.shape) != (N, self.V, 3) or verts.dtype != torch.float32:
+            raise A2PError(f"verts must be float32 [{N}, {self.V}, 3] (got {verts.dtype} {list(verts.shape)})")
+        verts = verts.contiguous()
+        out = torch.empty(N, self.V, 3, dtype=torch.float32, device=dev)
+        g = self.global_scaling
+        with _lib.on_device_of(mats):
+            _lib.check(_lib.load().a2p_unskin_vertices(_lib.ptr(mats), N, self.J, _lib.ptr(verts), _lib.ptr(t["base"]), _lib.ptr(t["idx"]),
+                                                       _lib.ptr(t["w"]), self.V, self.K, float(g[0]), float(g[1]), float(g[2]),
+                                                       _lib.ptr(out), _lib.current_stream(dev)), "a2p_unskin_vertices")
+        finite = torch.isfinite(out)
+        if not bool(finite.all()):
+            n, v = (int(i) for i in torch.nonzero(~finite.all(dim=2))[0])
+            raise A2PError(f"unpose_vertices: frame {n}, vertex {v} is not finite: its blended skinning matrix is singular or not "
+                           "finite (or verts is not finite there)")
+        return out
+
 
 # ------------------------------------------------------------------------------------------------ convenience
 def pose_motion(skeleton: BodySkeleton, motion, vertices: bool = True, device=None) -> dict:

@@ -766,6 +766,69 @@ int a2p_resize_bilinear(const float* x, int64_t planes, int32_t Hs, int32_t Ws, 
 int a2p_texture_compose(const float* t, const float* u, const float* tex_mean, float tex_std, const float* shadow,
                         int32_t shadow_frames, int64_t N, int32_t C, int32_t Sh, int32_t Sw, float* out, void* stream);
 
+/* ---- encode layers (reference visualize/ca_body/nn/layers.py LinearWN, nn/blocks.py ConvDownBlock, utils/lbs.py unskinning /
+ * unpose, models/mesh_vae_drivable.py FaceEncoder; audio2photoreal_amd/encoder.py, skinning.py) --
+ * What lies between the samplers' output and the renderer's embeddings.  Like the decoder and texture layers: fp32, on the
+ * caller's stream, context-free, weights already folded, 64-bit offsets, no atomics and a fixed summation order (a frame's result
+ * depends on neither N nor its index, and two runs give the same bits); an output must not overlap an input; N = 0 returns 0
+ * without a launch.
+ *
+ * a2p_linear_f32: out[n][o] = act(sum over i of x[n][i] weight[o][i] + bias[o]) for x [N, I] with rows ldx >= I floats apart,
+ * weight [O, I] dense, bias [O] or NULL, out [N, O] with rows ldo >= O floats apart; act 0 none, 1 LeakyReLU(slope).  Any I, O >= 1:
+ * no padding or alignment beyond 4 bytes is asked of the caller.  The sum over i is cut into S = ceil(I / A2P_LINEAR_KSLICE) slices
+ * [256 s, min(I, 256 s + 256)); S depends on I alone.  Per output element, in this order:
+ *   a_s = 0;  a_s = fmaf(weight[o][i], x[n][i], a_s) for i ascending over slice s          one fused multiply-add per term
+ *   v = a_0;  v = v + a_s for s = 1 .. S - 1 ascending
+ *   v = v + bias[o]                 when bias is given
+ *   v = v >= 0 ? v : slope v        when act = 1
+ * S > 1 takes scratch, S N O floats (scratch_floats says how many it holds; contents undefined on return), and a second launch;
+ * S = 1 takes none (scratch may be NULL).  Every weight is read from memory once per 64 rows of x.
+ *
+ * a2p_conv2d_down3_ub: the second launch of a ConvDownBlock, lrelu2(conv2(h)) + conv_resize(x); the first, h = lrelu1(conv1(x)), is
+ * an a2p_conv2d_ub call.  h and x are sources [N, C_in, Hs, Ws] as in a2p_conv2d_ub (frame stride, channel windows) of one shape,
+ * read directly; w2 [C_out, C_in, 3, 3]; b2 [C_out, H, W] (untied); wr [C_out, C_in]; br [C_out] or NULL (counts 0); out [N, C_out,
+ * H, W] with H = (Hs - 1) / 2 + 1, W = (Ws - 1) / 2 + 1 (floor division; odd sizes allowed); groups = 1; the channel and size limits
+ * of a2p_conv2d_ub.  Per output element, in this order:
+ *   v = sum over ci ascending, then ky, kx row-major, of w2[co][ci][ky][kx] h[n][ci][2 y - 1 + ky][2 x - 1 + kx]   (0 outside)
+ *   v = v + b2[co][y][x]
+ *   v = v >= 0 ? v : slope v
+ *   r = sum over ci ascending of wr[co][ci] x[n][ci][2 y][2 x];  v = v + (br[co] + r)
+ * The 1 x 1 branch is never written to memory.
+ *
+ * a2p_unskin_vertices: LinearBlendSkinning.unskinning with the two lines of LBSModule.unpose; layouts and limits of
+ * a2p_skin_vertices (mats [N, J, 3, 4]; idx / w [K, V]); verts [N, V, 3]; tmpl [V, 3]; out [N, V, 3].  Per frame and vertex:
+ *   M = sum over k ascending of w[k][v] mats[n][idx[k][v]], entry by entry from 0;  A = M[:, 0:3], t = M[:, 3]
+ *   d = verts[n][v] / (gx, gy, gz) - t                                                 a division, as the reference writes it
+ *   out[n][v] = (adj(A) d) / det(A) - tmpl[v]       adj: cofactors as differences of two products; det = A00 C00 + A01 C01 + A02
+ *                                                   C02 and every row of adj(A) d summed left to right
+ * The reference inverts the 4 x 4 matrix with Tensor.inverse() (an LU); this is the closed form in fp32.  A zero or non-finite
+ * determinant yields a non-finite output and is not checked here.
+ *
+ * a2p_face_tex_cond: raw [N, C, Hs, Ws], bias [C, Hs, Ws], mask [H, W] -> out [N, C, H, W]:
+ *   out[n][c][y][x] = (resize(255 ((raw[n][c] + bias[c]) + 0.5))[y][x] / 255 - 0.5) mask[y][x]
+ * with the taps, weights and order of a2p_resize_bilinear (align_corners = False, any ratio) and the arithmetic inside applied to
+ * each tap; face_tex itself is never written. */
+#define A2P_LINEAR_KSLICE 256
+typedef struct a2p_down3_desc {
+  a2p_conv_source h;
+  a2p_conv_source x;
+  const float* w2;
+  const float* b2;
+  const float* wr;
+  const float* br;
+  float* out;
+  int64_t N;
+  int32_t C_out;
+  float slope;
+} a2p_down3_desc;
+int a2p_linear_f32(const float* x, int64_t ldx, const float* weight, const float* bias, int64_t N, int32_t I, int32_t O, int32_t act,
+                   float slope, float* out, int64_t ldo, float* scratch, int64_t scratch_floats, void* stream);
+int a2p_conv2d_down3_ub(const a2p_down3_desc* desc, void* stream);
+int a2p_unskin_vertices(const float* mats, int64_t N, int32_t J, const float* verts, const float* tmpl, const int32_t* idx,
+                        const float* w, int32_t V, int32_t K, float gx, float gy, float gz, float* out, void* stream);
+int a2p_face_tex_cond(const float* raw, const float* bias, const float* mask, int64_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t H,
+                      int32_t W, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
