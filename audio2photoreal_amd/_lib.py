@@ -52,6 +52,7 @@ EXPORTS = (
     "a2p_conv2d_ub", "a2p_seam_impaint", "a2p_seam_resample",
     "a2p_conv2d_down_ub", "a2p_conv_transpose2d_ub", "a2p_resize_bilinear", "a2p_texture_compose",
     "a2p_linear_f32", "a2p_conv2d_down3_ub", "a2p_unskin_vertices", "a2p_face_tex_cond",
+    "a2p_jpeg_coefficients", "a2p_jpeg_entropy",
 )
 
 
@@ -160,6 +161,7 @@ CONV_BIAS_NONE, CONV_BIAS_TIED, CONV_BIAS_UNTIED = 0, 1, 2               # A2P_C
 CONV_SKIP_NONE, CONV_SKIP_TENSOR, CONV_SKIP_CONV = 0, 1, 2               # A2P_CONV_SKIP_*
 TEX_ACT_NONE, TEX_ACT_LRELU, TEX_ACT_SIGMOID = 0, 1, 2                   # A2P_TEX_ACT_*
 LINEAR_KSLICE = 256                                                      # A2P_LINEAR_KSLICE
+JPEG_MAX_SIZE, JPEG_BLOCK_BITS, JPEG_HUFF_WORDS = 65535, 1665, 544       # A2P_JPEG_*
 
 
 _libs = {}
@@ -262,6 +264,8 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_conv2d_down3_ub": [C.POINTER(A2PDown3Desc), vp],
         "a2p_unskin_vertices": [vp, i64, i32, vp, vp, vp, vp, i32, i32, f32, f32, f32, vp, vp],
         "a2p_face_tex_cond": [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp],
+        "a2p_jpeg_coefficients": [vp, i64, i32, i32, i64, i64, i32, vp, vp, vp],
+        "a2p_jpeg_entropy": [vp, i64, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

@@ -44,6 +44,7 @@
 #include "kernels_small.h"
 #include "kernels_surface.h"
 #include "kernels_tail.h"
+#include "kernels_video.h"
 #include "kernels_vq.h"
 #include "kernels_window.h"
 
@@ -1030,3 +1031,4 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_conv.h"
 #include "a2p_texture.h"
 #include "a2p_encode.h"
+#include "a2p_video.h"

@@ -572,6 +572,10 @@ def main(argv=None) -> int:
     ap.add_argument("--size", type=int, nargs=2, default=(256, 256), metavar=("H", "W"), help="height and width of one camera's panel")
     ap.add_argument("--frames", default=None, metavar="A:B", help="frames A..B-1 of the time axis only")
     ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write frame_<sequence>_<frame>.png per frame")
+    ap.add_argument("--video", default=None, metavar="FILE", help="also write a Motion-JPEG AVI file, encoded on the GPU (video.py); R > 1 "
+                    "sequences go to <stem>_<r>.avi")
+    ap.add_argument("--audio", default=None, metavar="FILE", help="with --video: the recording's wav file, written as 16-bit PCM beside the frames")
+    ap.add_argument("--fps", type=float, default=30.0, help="with --video: frames per second")
     ap.add_argument("--body-embs", choices=("per_frame", "rest"), default="per_frame", help="rest: encode the template once (not the reference's loop)")
     ap.add_argument("--max-bytes", type=int, default=1 << 30, help="activation budget of one chunk of frames")
     ap.add_argument("--uv-size", type=int, default=1024)
@@ -585,6 +589,8 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if args.defaults is not None and args.target is not None:
         raise A2PError("--target goes with --eye, not with --defaults")
+    if args.audio is not None and args.video is None:
+        raise A2PError("--audio goes with --video")
     from .decoder import BodyDecoder
     from .skinning import BodySkeleton
     from .surface import BodySurface
@@ -628,10 +634,18 @@ def main(argv=None) -> int:
     else:
         rest = skeleton.pose_vertices(poses.reshape(-1, poses.shape[-1])[:1]).cpu().numpy()  # frames the default camera
         K, Rt = R._camera_from_args(args, rest, H, W)
-    frames = render_codes_motion(face_decoder, face_encoder, body_encoder, decoder, texture, skeleton, R.BodyRasterizer(surface, H, W), poses,
-                                 face, K, Rt, camera_pos, body_embs=args.body_embs, max_bytes=args.max_bytes).cpu().numpy()
+    on_gpu = render_codes_motion(face_decoder, face_encoder, body_encoder, decoder, texture, skeleton, R.BodyRasterizer(surface, H, W), poses,
+                                 face, K, Rt, camera_pos, body_embs=args.body_embs, max_bytes=args.max_bytes)
+    frames = on_gpu.cpu().numpy()
     np.save(args.out, frames)
     print(f"{args.out}: frames {list(frames.shape)} uint8")
+    if args.video is not None:
+        from . import video
+        audio, rate = video.wav_audio(args.audio) if args.audio is not None else (None, None)
+        for r in range(on_gpu.shape[0]):
+            path = video.sequence_path(args.video, r, on_gpu.shape[0])
+            video.write_video(path, on_gpu[r], fps=args.fps, audio=audio, audio_rate=rate)
+            print(f"{path}: {on_gpu.shape[1]} frames at {args.fps:g} fps")
     if args.png_dir is not None:
         import os
         from PIL import Image

@@ -829,6 +829,50 @@ int a2p_unskin_vertices(const float* mats, int64_t N, int32_t J, const float* ve
 int a2p_face_tex_cond(const float* raw, const float* bias, const float* mask, int64_t N, int32_t C, int32_t Hs, int32_t Ws, int32_t H,
                       int32_t W, float* out, void* stream);
 
+/* ---- video frames (reference visualize/render_codes.py BodyRenderer.render_full_video, which hands the frames to mediapy and
+ * ffmpeg; audio2photoreal_amd/video.py) --
+ * Baseline JPEG (ITU-T T.81, sequential DCT, Huffman) of uint8 RGB frames for a Motion-JPEG stream, in two stages.  Context-free,
+ * on the caller's stream, 64-bit offsets, no float atomics; a frame's coefficients and bytes depend on that frame and the tables
+ * alone, never on N or the frame's index; an output must not overlap an input; N = 0 launches no frame kernel.
+ *
+ * a2p_jpeg_coefficients: rgb [N, H, W, 3] uint8 with frames frame_stride and rows row_stride BYTES apart (row_stride >= 3 W: a
+ * column window of a wider image is read in place) -> out int16 [N, mcu_rows, mcu_cols, blocks_per_mcu, 64], every block in zig-zag
+ * order.  subsampling 420: MCU 16 x 16, blocks Y00 Y01 Y10 Y11 Cb Cr; 444: MCU 8 x 8, blocks Y Cb Cr; mcu_rows = ceil(H / MCU),
+ * mcu_cols = ceil(W / MCU).  qtab: uint16 [2][64], luminance then chrominance, in natural order (index 8 v + u), every entry >= 1.
+ * The arithmetic is fp32 with no intermediate rounding to integers:
+ *   Y  = 0.299 R + 0.587 G + 0.114 B;  Cb = -0.168735892 R - 0.331264108 G + 0.5 B + 128;  Cr = 0.5 R - 0.418687589 G - 0.081312411 B + 128
+ *   samples right of / below the image repeat its last column / row;  4:2:0 chroma = ((a + b) + (c + d)) / 4 over each 2 x 2 group
+ *   f = sample - 128
+ *   F(u, v) = 1/4 C(u) C(v) sum over x, y of f(x, y) cos((2 x + 1) u pi / 16) cos((2 y + 1) v pi / 16),  C(0) = 1 / sqrt 2, else 1:
+ *             a row pass then a column pass of 8-point sums, each one product and seven fmaf with the index ascending
+ *   q = rintf(F / Q[v][u])  (IEEE division, ties to even);  AC coefficients are clamped to +-1023
+ * Sizes up to A2P_JPEG_MAX_SIZE, the format's limit.  The loads are 4 bytes wide where rgb, frame_stride and row_stride are
+ * multiples of 4 and single bytes otherwise; the results are the same.
+ *
+ * a2p_jpeg_entropy: coef int16 in that layout (any values: a DC difference is clamped to +-2047, an AC coefficient to +-1023) ->
+ * every frame's entropy-coded segment.  The restart interval is one MCU row (DRI = mcu_cols): the DC prediction of every component
+ * starts at 0 in every interval, every interval is padded with 1-bits to a byte, and every interval but a frame's last is followed
+ * by RSTm (0xFF, 0xD0 + m), m = the row's index mod 8.  DC: the category's code, then the amplitude bits; AC: (run, size) codes, ZRL
+ * for runs of 16, EOB when the tail is zero (none when coefficient 63 is not); 0x00 follows every 0xFF data byte.  huff: uint32
+ * [A2P_JPEG_HUFF_WORDS]: DC luminance [16] and chrominance [16] by category, AC luminance [256] and chrominance [256] by symbol,
+ * each (length << 16) | code, length <= 16.  A block codes to at most A2P_JPEG_BLOCK_BITS bits, which is what the kernel reserves.
+ * The call has two forms, used in this order with the same interval and offsets arrays:
+ *   out = NULL   sizes: interval int64 [N, mcu_rows] gets the offset of every interval inside its frame's segment and offsets int64
+ *                [N + 1] the start of every frame in a packed stream, offsets[n + 1] - offsets[n] = head_bytes + segment + tail_bytes;
+ *                offsets[N] is the stream's length
+ *   out given    writes: per frame head (head_bytes, copied from `head`; left untouched when head is NULL), the segment, tail
+ *                likewise, at out + offsets[n].  No byte at or beyond out_bytes is written: an out_bytes below offsets[N] truncates
+ *                the stream and is the caller's error.
+ * Nothing is truncated inside the kernels: the bytes are counted before they are written. */
+#define A2P_JPEG_MAX_SIZE 65535
+#define A2P_JPEG_BLOCK_BITS 1665
+#define A2P_JPEG_HUFF_WORDS 544
+int a2p_jpeg_coefficients(const uint8_t* rgb, int64_t N, int32_t H, int32_t W, int64_t frame_stride, int64_t row_stride,
+                          int32_t subsampling, const uint16_t* qtab, int16_t* out, void* stream);
+int a2p_jpeg_entropy(const int16_t* coef, int64_t N, int32_t mcu_rows, int32_t mcu_cols, int32_t blocks_per_mcu, const uint32_t* huff,
+                     const uint8_t* head, int32_t head_bytes, const uint8_t* tail, int32_t tail_bytes, int64_t* interval,
+                     int64_t* offsets, uint8_t* out, int64_t out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
