@@ -53,6 +53,7 @@ EXPORTS = (
     "a2p_conv2d_down_ub", "a2p_conv_transpose2d_ub", "a2p_resize_bilinear", "a2p_texture_compose",
     "a2p_linear_f32", "a2p_conv2d_down3_ub", "a2p_unskin_vertices", "a2p_face_tex_cond",
     "a2p_jpeg_coefficients", "a2p_jpeg_entropy",
+    "a2p_vq_train_workspace_bytes", "a2p_vq_train_step",
 )
 
 
@@ -116,6 +117,12 @@ class A2PTexConvDesc(C.Structure):
     """a2p_tex_conv_desc (include/a2p_hip.h "texture layers"): one launch of a2p_conv2d_down_ub or a2p_conv_transpose2d_ub."""
     _fields_ = ([("x", A2PConvSource)] + [(n, C.c_void_p) for n in ("weight", "bias", "skip", "out")] + [("N", C.c_int64)]
                 + [(n, C.c_int32) for n in ("C_out", "bias_mode", "act")] + [("slope", C.c_float), ("beta", C.c_float), ("reserved", C.c_int32)])
+
+
+class A2PVqTrainHyper(C.Structure):
+    """a2p_vq_train_hyper (include/a2p_hip.h "tokenizer training"): the scalars of one training step."""
+    _fields_ = [(n, C.c_double) for n in ("lr", "bias_correction1", "bias_correction2", "weight_decay", "commit", "loss_vel",
+                                          "ema_decay", "ema_epsilon")]
 
 
 class A2PDown3Desc(C.Structure):
@@ -266,6 +273,9 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_face_tex_cond": [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp],
         "a2p_jpeg_coefficients": [vp, i64, i32, i32, i64, i64, i32, vp, vp, vp],
         "a2p_jpeg_entropy": [vp, i64, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp],
+        "a2p_vq_train_workspace_bytes": [i32, i32, i32, i32, i32, i32, C.POINTER(i64)],
+        "a2p_vq_train_step": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                              C.POINTER(A2PVqTrainHyper), vp, vp, vp, vp, i64, vp],
     }
     def note_failure(result, func, args, lib=lib):   # ctypes errcheck hook: remember WHICH build returned the error
         if result < 0:

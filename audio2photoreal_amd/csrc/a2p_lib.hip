@@ -46,6 +46,7 @@
 #include "kernels_tail.h"
 #include "kernels_video.h"
 #include "kernels_vq.h"
+#include "kernels_vq_train.h"
 #include "kernels_window.h"
 
 static thread_local char g_err[1024] = "";
@@ -1032,3 +1033,4 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_texture.h"
 #include "a2p_encode.h"
 #include "a2p_video.h"
+#include "a2p_vq_train.h"

@@ -442,6 +442,36 @@ int a2p_vq_encode(const float* poses, int32_t batch, int32_t T, int32_t depth, i
                   int32_t vertices, const float* const* codebooks, const float* const* code_norms, const float* const* conv_w,
                   const float* const* conv_b, int64_t* tokens_out, float* latents_out, void* stream);
 
+/* ---- tokenizer training (train/train_vq.py ModelTrainer.run_train_step) ---------------------------------------------
+ * One fused step of TemporalVertexCodec in training mode: forward, SmoothL1 losses (mean reduction, beta 1; the "velocity" term
+ * differences the CHANNEL axis, as the reference does), backward through decoder, straight-through residual VQ (only level 0
+ * carries commitment gradient) and encoder, AdamW (torch's single-tensor path, betas (0.9, 0.99), eps 1e-8) and the EMA codebook
+ * update (cluster_size, embed_avg, embed = embed_avg / (laplace_smoothing(cluster_size) * cluster_size.sum())).  Every level
+ * quantises with the books as they stood when the step began.  Dead-code expiry is not built: in the reference the EMA update
+ * of the same forward overwrites what it writes.  fp32 state and activations (dot products accumulate in double and round once),
+ * five launches whatever the shapes, no host synchronisation, no float
+ * atomics: the same state and batch give the same bits.
+ * params / exp_avg / exp_avg_sq: one flat fp32 buffer each, the tensors of TemporalVertexCodec.parameters() in order
+ * (encoder.enc.{0,2,4,6,8}.{weight,bias}, decoder.project_mean_shape.{weight,bias}, decoder.dec.{0,2,4,6,8}.{weight,bias});
+ * project_mean_shape never gets a gradient and is left untouched, moments included.  embed / embed_avg / cluster_size: `depth`
+ * device pointers ([categories, latent] x2, [categories]); the pointer arrays are host memory.  All state is updated in place.
+ * tokens_out int64 [batch, T, depth].  loss_record: 6 device floats the step ADDS to (loss, loss_motion, loss_commit, loss_vel,
+ * perplexity of the last level, 1): zero it, run steps, read it when convenient.  grads_out: NULL or a flat buffer like params
+ * that receives this step's gradient (the project_mean_shape range is not written).  workspace: 16-byte aligned device memory of
+ * a2p_vq_train_workspace_bytes; it needs no initialisation.  Bounds as a2p_vq_encode; A2P_ERR_ARG, before any launch, when
+ * 2 (T + 7) latent floats + 64 bytes exceed 64 KB of LDS (T <= 120 at latent 64). */
+typedef struct a2p_vq_train_hyper {
+  double lr, bias_correction1, bias_correction2;   /* 1 - beta^step of this step, as torch.optim.AdamW computes them */
+  double weight_decay, commit, loss_vel;
+  double ema_decay, ema_epsilon;                   /* the reference: 0.99, 1e-5 */
+} a2p_vq_train_hyper;
+int a2p_vq_train_workspace_bytes(int32_t batch, int32_t T, int32_t depth, int32_t categories, int32_t latent, int32_t vertices,
+                                 int64_t* bytes_out);
+int a2p_vq_train_step(const float* x, int32_t batch, int32_t T, int32_t depth, int32_t categories, int32_t latent,
+                      int32_t vertices, float* params, float* exp_avg, float* exp_avg_sq, float* const* embed,
+                      float* const* embed_avg, float* const* cluster_size, const a2p_vq_train_hyper* hyper, int64_t* tokens_out,
+                      float* loss_record, float* grads_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- audio front end ------------------------------------------------------------------
  * What FiLMTransformer.forward computes from y["audio"] before anything else, in every step and pass (model/diffusion.py:
  * 354-358): encode_audio (:285-293, both stereo channels through the vq-wav2vec conv feature extractor of model/utils.py:18-26,
