@@ -188,6 +188,7 @@ struct A2POpts {
   int time_table = 1000;    // A2P_TIME_TABLE: rows of the time-MLP table (a2p_ctx::tct_table) built at a2p_finalize_weights; 0 = compute the time MLP in every forward
   int no_fused_in = 0;      // A2P_NO_FUSED_IN=1: face model: pack_input_split3 + gemm_kernel + the gen-1 PRE kernel instead of chain4_kernel<MT, CHAIN_IN> (A/B, tests)
   int no_fused_final = 0;   // A2P_NO_FUSED_FINAL=1: face model: final_layer behind the last tall POST kernel as split3_kernel + gemm_kernel instead of inside it (A/B, tests)
+  int fused_tail = 1;       // A2P_FUSED_TAIL=0: guided DDPM step: step_tail_kernel behind the last tall POST kernel instead of inside it (chain4_kernel<3, POST, 3>; A/B, tests)
   int graph = 0;            // A2P_GRAPH=1: non-chain forwards replay a captured graph instead of stream launches (measured: same GPU
                             // time per step -- the launches are not host-bound -- at a tenth of the host time; off by default)
   int no_small = 0;         // A2P_NO_SMALL=1: per-op kernels for forwards below 960 rows instead of kernels_small.h
@@ -205,7 +206,7 @@ static void load_opts(A2POpts& o) {
   o.side_early_join = flag("A2P_SIDE_EARLY_JOIN"); o.no_shared_half = flag("A2P_NO_SHARED_HALF");
   o.graph = flag("A2P_GRAPH");
   o.no_ksplit = flag("A2P_NO_KSPLIT"); o.force_ksplit = flag("A2P_ATTN_KSPLIT"); o.ksplit_nw = num("A2P_KSPLIT_NW", 0); o.ksplit_qt = num("A2P_KSPLIT_QT", 0);
-  o.no_fused_kf = flag("A2P_NO_FUSED_KF"); o.no_fused_final = flag("A2P_NO_FUSED_FINAL"); o.no_fused_in = flag("A2P_NO_FUSED_IN"); o.time_table = num("A2P_TIME_TABLE", 1000); o.attn2 = num("A2P_ATTN2", 0); o.attn3 = num("A2P_ATTN3", 1); o.chain_v = num("A2P_CHAIN_V", 0);
+  o.no_fused_kf = flag("A2P_NO_FUSED_KF"); o.no_fused_final = flag("A2P_NO_FUSED_FINAL"); o.no_fused_in = flag("A2P_NO_FUSED_IN"); o.fused_tail = num("A2P_FUSED_TAIL", 1); o.time_table = num("A2P_TIME_TABLE", 1000); o.attn2 = num("A2P_ATTN2", 0); o.attn3 = num("A2P_ATTN3", 1); o.chain_v = num("A2P_CHAIN_V", 0);
   o.no_small = flag("A2P_NO_SMALL"); o.chain_rows = num("A2P_CHAIN_ROWS", 1100);
 }
 
@@ -246,6 +247,9 @@ struct a2p_ctx {
   std::vector<Buf> ch_stream4w;        // POST streams with 256-column hidden chunks [layer]
   Buf ch_stream4_in, ch_aux_in;        // CHAIN_IN (input_projection + layer 0's PRE work in one tall kernel): stream [W_hi | W_hi | W_lo | Q|K | V], aux [bias_in 512 | 0 | bias_qkv]
   int64_t in4_launches = 0;            // launches of chain4_kernel<MT, CHAIN_IN> (a2p_debug_read "chain_in_launches")
+  int64_t tail_fused_launches = 0;     // last-layer tall POST kernels that carried the step tail in their epilogue (a2p_debug_read "fused_tail_launches")
+  const struct StepP* step_tail = nullptr;   // a2p_sample_step, around its forward: the guided DDPM tail the last POST kernel may take over (decoder_layer_chain) ...
+  bool step_tail_done = false;         // ... and whether it did (then no step_tail_kernel launch follows)
   std::vector<Buf> ch_stream4;         // kernels_chain4.h: half-stage streams [layer*5 + kind] (CH_MID, CH_POST of the face model; empty Buf otherwise)
   std::vector<Buf> ch_stream, ch_aux;  // packed weight streams [layout * L*5 + layer*5 + kind] (layout 0: 4-wave LDS slices, 1: 8-wave; kinds: a2p_lib_run.h CH_*) / bias blocks [layer*5 + kind]
   int ch_nw = 4;                       // waves per chain workgroup of the forward being enqueued (4 or 8; chain_pick_nw)

@@ -491,7 +491,11 @@ static int launch_chain4(a2p_ctx* c, int mode, const ChainP& p0, hipStream_t s) 
     else if (p.has_next) A2P_LAUNCH(kt, (chain4_kernel<MT, CHAIN_POST>), grid, 512, s, p);      \
     else A2P_LAUNCH(kt, (chain4_kernel<MT, CHAIN_POST, 1>), grid, 512, s, p);                   \
   } while (0)
-  if (fin) {
+  if (fin && p.pair_B) {   // paired panels: one workgroup per 24 frames of a (conditional, unconditional) sequence pair
+    ARG(mt == 3, "paired panels are 48 rows");
+    ++c->tail_fused_launches;
+    A2P_LAUNCH(kt, (chain4_kernel<3, CHAIN_POST, 3>), p.pair_B * ((p.rows_per_seq + 23) / 24), 512, s, p);
+  } else if (fin) {
     if (mt == 3) A2P_LAUNCH(kt, (chain4_kernel<3, CHAIN_POST, 2>), grid, 512, s, p);
     else if (mt == 4) A2P_LAUNCH(kt, (chain4_kernel<4, CHAIN_POST, 2>), grid, 512, s, p);
     else A2P_LAUNCH(kt, (chain4_kernel<5, CHAIN_POST, 2>), grid, 512, s, p);
@@ -762,6 +766,15 @@ static int decoder_layer_chain(a2p_ctx* c, int l, int N, int T, const CrossKV& k
     p.aux_kb = (c->ff + c->C + 255) / 256;
     *fused_x3 = chain4_final_fused(c, CHAIN_POST, p);
     if (!*fused_x3) { p.fin_x3 = 0; p.fin_out = fin_out0; p.aux_kb = (c->ff + 255) / 256; }
+    // A guided DDPM step (a2p_sample_step) whose last POST kernel runs 48-row panels: paired panels, the step tail in the kernel's epilogue (chain4_kernel<3, POST, 3>);
+    // the model output rows are not written at all.  Same bits as step_tail_kernel behind the kernel (A2P_FUSED_TAIL=0; tests/test_fused_step_tail_hip.py).
+    const StepP* st = c->step_tail;
+    if (*fused_x3 && st && c->opt.fused_tail && N == 2 * st->B && st->Tn == T && st->C == 256 && chain4_pick_mt(c, p.M) == 3) {
+      p.pair_B = st->B;
+      p.tl_clip = st->clip; p.tl_nsteps = st->n_steps; p.tl_scale = st->scale; p.tl_t = st->t_idx; p.tl_tables = st->tables;
+      p.tl_x = st->x; p.tl_noise = st->noise; p.tl_xnext = st->x_next; p.tl_x0 = st->x0; p.tl_nonfinite = st->nonfinite;
+      c->step_tail_done = true;
+    }
   }
   return launch_chain(c, fuse_kf ? CHAIN_MIDPOST : CHAIN_POST, p, s);
 }
@@ -1254,14 +1267,21 @@ extern "C" int a2p_sample_step(a2p_ctx* c, int32_t sampler, const float* x, cons
   // _WrappedModel.__call__ (respace.py:140-145): new_ts = timestep_map[ts]; reuse tmpa as int64 scratch
   int64_t* t_orig = reinterpret_cast<int64_t*>(c->tmpa.p);
   map_timesteps_kernel<<<1, 256, 0, s>>>(t_idx, timestep_map, t_orig, c->pB);
-  int rows = 0;
-  CHK(run_forward(c, x, t_orig, A2P_PASS_CFG, &rows, s));
   StepP sp;
   memset(&sp, 0, sizeof(sp));
-  sp.mo = c->mo.f(); sp.mo_seq_rows = rows; sp.mo_ld = c->C; sp.B = c->pB; sp.C = c->C; sp.Tn = c->pT;
+  sp.mo = c->mo.f(); sp.mo_ld = c->C; sp.B = c->pB; sp.C = c->C; sp.Tn = c->pT;
   sp.pass = A2P_PASS_CFG; sp.scale = scale; sp.sampler = sampler; sp.x = x; sp.t_idx = t_idx; sp.tables = tables;
   sp.n_steps = n_steps; sp.noise = noise; sp.eta = eta; sp.clip = clip_denoised; sp.x_next = x_next; sp.x0 = pred_xstart;
   sp.nonfinite = reinterpret_cast<int*>(c->nonfinite.p);
+  // DDPM: the forward's last POST kernel takes the tail over where it can (decoder_layer_chain); every other sampler and every other forward leaves it to step_tail_kernel
+  c->step_tail = sampler == A2P_SAMPLER_DDPM ? &sp : nullptr;
+  c->step_tail_done = false;
+  int rows = 0;
+  const int rc = run_forward(c, x, t_orig, A2P_PASS_CFG, &rows, s);
+  c->step_tail = nullptr;
+  if (rc != 0) return rc;
+  if (c->step_tail_done) return 0;
+  sp.mo_seq_rows = rows;
   return launch_step_tail(c, sp, s);
 }
 
@@ -1967,6 +1987,11 @@ extern "C" int a2p_debug_read(a2p_ctx* c, const char* name, void* host, int64_t 
   if (n == "final_fused_launches") {   // int64: last-layer tall POST kernels that computed final_layer as a split-operand island (tests)
     ARG(bytes >= 8, "final_fused_launches is one int64");
     *reinterpret_cast<int64_t*>(host) = c->fin_fused_launches;
+    return 0;
+  }
+  if (n == "fused_tail_launches") {   // int64: last-layer tall POST kernels that carried the guided DDPM step tail in their epilogue (tests)
+    ARG(bytes >= 8, "fused_tail_launches is one int64");
+    *reinterpret_cast<int64_t*>(host) = c->tail_fused_launches;
     return 0;
   }
   if (n == "chain4_launches") {   // int64: launches of the tall chain kernels (kernels_chain4.h) on this context so far (tests, bench)

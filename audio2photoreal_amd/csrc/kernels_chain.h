@@ -132,6 +132,19 @@ struct ChainP {
   // diagnostic (A2P_CHAIN_CLK=1): blocks 0..7 write {s_memtime, s_memrealtime} at kernel begin / end to clk[block][2][2]: the
   // shader clock the kernel actually ran at inside the step (DVFS) = d(memtime) / d(memrealtime @ 100 MHz)
   unsigned long long* clk;
+  // kernels_chain4.h, LAST = 3: the last POST kernel of a guided DDPM step with the step tail (kernels_misc.h step_tail_kernel) in its epilogue.  Panels are PAIRED:
+  // workgroup (b, q) holds frames [24 q, 24 q + 24) of sequence b in its rows 0-23 and the same frames of sequence pair_B + b in its rows 24-47, so it owns both
+  // operands of the guidance combine of those frames.  Nothing is written to fin_out; the tl_* operands are StepP's ([pair_B][fin_n][rows_per_seq] layouts).
+  int pair_B;                  // samples (0: ordinary panels)
+  int tl_clip, tl_nsteps;
+  const float* tl_scale;       // [pair_B]
+  const int64_t* tl_t;         // [pair_B] table row of each sample
+  const float* tl_tables;
+  const float* tl_x;
+  const float* tl_noise;
+  float* tl_xnext;
+  float* tl_x0;                // may be NULL
+  int* tl_nonfinite;           // may be NULL
 };
 
 // one 16 KiB stage of a packed stream: stage = rows [row0, row0+128) x k [k0, k0+64) of W[., ldw]

@@ -33,6 +33,7 @@
 // >= 16 * MT (a panel touches at most two sequences) and a multiple of 8 (staged V^T store); everything else takes kernels_chain.h.
 #pragma once
 #include "kernels_chain.h"
+#include "kernels_misc.h"   // the step tail's arithmetic (LAST = 3), under ITS contraction mode
 
 #pragma clang fp contract(off)
 
@@ -183,12 +184,32 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
     *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(base) + (elem << 2)) = v;
   };
   auto lds_off = [&](const void* q) __attribute__((always_inline)) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)q; };
+  // LAST = 3: PAIRED panel (ChainP::pair_B) -- rows 0-23 are frames [pr_f0, pr_f0 + 24) of sequence pr_b, rows 24-47 the same frames of sequence pair_B + pr_b.
+  // Every phase of the chain is row-wise, so which rows share a panel changes no bit of any row.  Frames past the sequence's end repeat its last frame and are dropped at the end.
+  constexpr bool PAIR = LAST == 3;
+  static_assert(!PAIR || MT == 3, "paired panels are 2 x 24 rows");
+  [[maybe_unused]] int pr_b = 0, pr_f0 = 0;
+  if constexpr (PAIR) {
+    const int hp = (p.rows_per_seq + 23) / 24, pb = m0 / BM;
+    pr_b = pb / hp;
+    pr_f0 = (pb - pr_b * hp) * 24;
+  }
+  auto row_of = [&](int r) __attribute__((always_inline)) -> int {   // global row of panel row r, clamped to a valid one
+    if constexpr (PAIR) {
+      const int h = r >= 24 ? 1 : 0;
+      int f = pr_f0 + r - 24 * h;
+      f = f < p.rows_per_seq ? f : p.rows_per_seq - 1;
+      return (pr_b + h * p.pair_B) * p.rows_per_seq + f;
+    } else {
+      const int m = m0 + r;
+      return m < p.M ? m : p.M - 1;
+    }
+  };
   int row_m[MT], fsel[MT], pos[MT];
-  const int seqA = m0 / p.rows_per_seq;
+  const int seqA = PAIR ? pr_b : m0 / p.rows_per_seq;
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
-    int m = m0 + mt * 16 + l15;
-    m = m < p.M ? m : p.M - 1;
+    const int m = row_of(mt * 16 + l15);
     row_m[mt] = m;
     const int sq = m / p.rows_per_seq;
     fsel[mt] = sq != seqA ? 1024 : 0;                 // second sequence of the panel: its FiLM rows sit 1024 floats further
@@ -294,8 +315,7 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
   {
     if constexpr (MODE != CHAIN_IN) {
       for (int r0 = wid; r0 < BM; r0 += NW) {   // one 1 KiB row per wave instruction
-        int m = m0 + r0;
-        m = m < p.M ? m : p.M - 1;
+        int m = row_of(r0);
         m = (p.src_rows > 0 && m >= p.src_rows) ? m - p.src_rows : m;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.ain + (int64_t)m * p.ld_ain + ((lane ^ (r0 & 15)) << 3)),
                                          (__attribute__((address_space(3))) void*)(panelA + r0 * D), 16, 0, 0);
@@ -305,7 +325,7 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
     if (tid < LY::FLAG_F) flags[tid] = 0u;
     // epilogue block: 28 pieces of 1 KiB (256 floats); piece q -> source pointer + destination offset
     const int nseq = p.M / p.rows_per_seq;
-    const int seqB = seqA + 1 < nseq ? seqA + 1 : seqA;
+    const int seqB = PAIR ? seqA + p.pair_B : seqA + 1 < nseq ? seqA + 1 : seqA;
     for (int q = wid; q < 28; q += NW) {
       if (MODE == CHAIN_IN && (q < 8 || q >= 12)) continue;   // (norm-B gamma / beta only: no attention output, no FiLM in front of layer 0)
       const float* src;
@@ -773,7 +793,7 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
       }
     }
     stamp(7);
-    if constexpr (LAST == 2) {
+    if constexpr (LAST >= 2) {
       // Last decoder layer, <= 64 rows: final_layer (model/diffusion.py:397) as a split-operand exact island on the rows in registers -- out = hi W_hi^T + lo W_hi^T + hi W_lo^T
       // with x = hi + lo (16-bit pieces), fp32 accumulation: what split3_kernel + gemm_kernel compute behind the non-fused kernel (19.7 MB of fp32 rows out, 29.5 MB of
       // split rows out and in again at B=8: 12.5 + ~30 us per step), without the round trip.  hi panel over the A panel, lo panel over the two hidden-chunk buffers (contiguous,
@@ -823,6 +843,54 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
       __builtin_amdgcn_sched_barrier(0);
       gemm(std::integral_constant<int, 2>{}, std::integral_constant<int, KC>{}, std::integral_constant<int, D>{}, acc, panelA, false);    // hi x W_lo
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (PAIR) {
+        // The step tail (kernels_misc.h step_tail_kernel, guided DDPM path) on the 24 frames x 256 features this workgroup holds BOTH model outputs of: guidance combine,
+        // [T][C] -> [C][T], clamp, posterior mean + noise.  Same expressions, same order: the bits of the separate launch, without its launch, the 2 x fin_n x 4 bytes per
+        // row it reads back, and the fp32 rows this kernel would store for it.  Thread -> (feature, frame) with the frame fastest: 96-byte runs along T.
+        constexpr int C = 256, SP = C + 1, NEL = 24 * C / 512;   // staging pitch: consecutive frames of one feature on consecutive banks
+        static_assert(24 * C % 512 == 0 && 48 * SP * 4 <= BM * D * 2 + BM * HLD * 2, "staging tile");
+        const int T = p.rows_per_seq;
+        // x_t and the noise first: their round trip runs under the two barriers and the staging writes
+        float xv[NEL], nv[NEL];
+#pragma unroll
+        for (int k = 0; k < NEL; ++k) {
+          const int i = tid + 512 * k, c = i / 24, t = pr_f0 + (i - c * 24);
+          const int64_t o = ((int64_t)pr_b * C + c) * T + (t < T ? t : T - 1);
+          xv[k] = p.tl_x[o];
+          nv[k] = p.tl_noise[o];
+        }
+        // (and the per-sample operands: read once, here -- behind the stores below the compiler would have to fetch them again for every element)
+        const float sc = p.tl_scale[pr_b];
+        const int ts = (int)p.tl_t[pr_b];
+        const float c1 = p.tl_tables[TAB_C1 * p.tl_nsteps + ts], c2 = p.tl_tables[TAB_C2 * p.tl_nsteps + ts], lv = p.tl_tables[TAB_LOGVAR * p.tl_nsteps + ts];
+        chain_bar();   // every wave is done with the hi / lo panels: the staging tile lies over them
+        float* const stg = reinterpret_cast<float*>(smem);   // [48][SP] fp32 model output rows
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+          for (int tt = 0; tt < 2; ++tt) {
+            const f32x4 v = acc[tt][mt] + *reinterpret_cast<const f32x4*>(aux + FT * 128 + col_of(tt));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) stg[(mt * 16 + l15) * SP + col_of(tt) + e] = v[e];
+          }
+        chain_bar();
+        bool bad = false;
+#pragma unroll
+        for (int k = 0; k < NEL; ++k) {
+          const int i = tid + 512 * k, c = i / 24, f = i - c * 24, t = pr_f0 + f;
+          if (t >= T) continue;
+          const float g = cfg_combine(stg[f * SP + c], stg[(24 + f) * SP + c], sc);
+          bad |= not_finite(g);
+          float x0 = g;
+          if (p.tl_clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+          const int64_t o = ((int64_t)pr_b * C + c) * T + t;
+          if (p.tl_x0) p.tl_x0[o] = x0;
+          p.tl_xnext[o] = ddpm_update_exact(x0, xv[k], nv[k], c1, c2, lv, ts);
+        }
+        if (bad && p.tl_nonfinite) atomicOr(p.tl_nonfinite, 1);   // rare path, as in step_tail_kernel
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        return;
+      }
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         const int m = m0 + mt * 16 + l15;

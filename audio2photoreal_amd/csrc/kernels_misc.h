@@ -328,6 +328,20 @@ __device__ __forceinline__ float ddpm_update(float x0, float x, float noise, con
   return mean + nz * expf(0.5f * tab[TAB_LOGVAR * ns + t]) * noise;
 }
 
+// The guided DDPM path of step_tail_kernel, one element, WITH EVERY ROUNDING SPELLED OUT: the chain kernel that carries the tail in its epilogue (kernels_chain4.h, LAST = 3)
+// must give step_tail_kernel's bits, and what a contracting compiler makes of `u + sc * (a - u)` and of ddpm_update's expressions depends on the code around them (the
+// same source inlined into the epilogue, table entries in registers: the mean came out as one fma, 1 ulp off).  The forms below are the ones step_tail_kernel has always
+// been compiled to -- the guidance combine one fma, the two products of the posterior mean rounded separately, the noise term one fma -- and both kernels call them.
+#pragma clang fp contract(off)
+__device__ __forceinline__ float cfg_combine(float a, float u, float sc) { return fmaf(sc, a - u, u); }
+__device__ __forceinline__ bool not_finite(float g) { return !(fabsf(g) <= 3.4028234e38f); }
+__device__ __forceinline__ float ddpm_update_exact(float x0, float x, float noise, float c1, float c2, float logvar, int t) {
+  const float mean = c1 * x0 + c2 * x;
+  const float nz = t != 0 ? 1.f : 0.f;
+  return fmaf(noise, nz * expf(0.5f * logvar), mean);
+}
+#pragma clang fp contract(fast)
+
 // Fused tail of one sampling step: classifier-free-guidance combine (model/cfg_sampler.py:33),
 // [B,T,C] -> [B,C,1,T] (gaussian_diffusion.py:312-313), optional clamp, posterior update.
 struct StepP {
@@ -364,11 +378,11 @@ __global__ __launch_bounds__(256) void step_tail_kernel(StepP p) {
       const float a = p.mo[((int64_t)b * p.mo_seq_rows + t) * p.mo_ld + c];
       if (p.pass == 2) {
         const float u = p.mo[((int64_t)(p.B + b) * p.mo_seq_rows + t) * p.mo_ld + c];
-        g = u + sc * (a - u);
+        g = cfg_combine(a, u, sc);
       } else {
         g = a;
       }
-      bad |= !(fabsf(g) <= 3.4028234e38f);   // inf or nan (a nan fails every comparison); inf - inf of the two passes is nan
+      bad |= not_finite(g);   // inf or nan (a nan fails every comparison); inf - inf of the two passes is nan
       if (p.out_btc) p.out_btc[((int64_t)b * p.Tn + t) * p.C + c] = g;
     }
     tile[i][tx] = g;
@@ -389,7 +403,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(StepP p) {
     if (p.sampler >= 0) {
       const float nv = p.noise ? p.noise[o] : 0.f;
       p.x_next[o] = p.sampler == 0 ? ddim_update(x0, xv, nv, p.tables, p.n_steps, ts, p.eta)
-                                   : ddpm_update(x0, xv, nv, p.tables, p.n_steps, ts);
+                                   : ddpm_update_exact(x0, xv, nv, p.tables[TAB_C1 * p.n_steps + ts], p.tables[TAB_C2 * p.n_steps + ts], p.tables[TAB_LOGVAR * p.n_steps + ts], ts);
     }
   }
 }
