@@ -52,7 +52,7 @@ EXPORTS = (
     "a2p_conv2d_ub", "a2p_seam_impaint", "a2p_seam_resample",
     "a2p_conv2d_down_ub", "a2p_conv_transpose2d_ub", "a2p_resize_bilinear", "a2p_texture_compose",
     "a2p_linear_f32", "a2p_conv2d_down3_ub", "a2p_unskin_vertices", "a2p_face_tex_cond",
-    "a2p_jpeg_coefficients", "a2p_jpeg_entropy",
+    "a2p_jpeg_coefficients", "a2p_jpeg_entropy", "a2p_jpeg_restarts", "a2p_jpeg_decode_entropy", "a2p_jpeg_pixels",
     "a2p_vq_train_workspace_bytes", "a2p_vq_train_step",
 )
 
@@ -169,6 +169,11 @@ CONV_SKIP_NONE, CONV_SKIP_TENSOR, CONV_SKIP_CONV = 0, 1, 2               # A2P_C
 TEX_ACT_NONE, TEX_ACT_LRELU, TEX_ACT_SIGMOID = 0, 1, 2                   # A2P_TEX_ACT_*
 LINEAR_KSLICE = 256                                                      # A2P_LINEAR_KSLICE
 JPEG_MAX_SIZE, JPEG_BLOCK_BITS, JPEG_HUFF_WORDS = 65535, 1665, 544       # A2P_JPEG_*
+JPEG_TABLES, JPEG_TABLE_WORDS = 4, 96                                    # A2P_JPEG_TABLES, A2P_JPEG_TABLE_WORDS
+JPEG_CAUSES = {1: "the number of RSTm markers is not ceil(mcus / Ri) - 1", 2: "an RSTm marker is out of order",      # A2P_JPEG_ERR_*
+               3: "a marker that is no RSTm, or a 0xFF at the end, inside the entropy-coded segment", 4: "a code that is in no Huffman table",
+               5: "a run past coefficient 63", 6: "the interval ends inside a code", 7: "an amplitude beyond 8-bit baseline",
+               8: "bytes left over behind the interval's last block"}
 
 
 _libs = {}
@@ -273,6 +278,9 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_face_tex_cond": [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp],
         "a2p_jpeg_coefficients": [vp, i64, i32, i32, i64, i64, i32, vp, vp, vp],
         "a2p_jpeg_entropy": [vp, i64, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, i64, vp],
+        "a2p_jpeg_restarts": [vp, i64, vp, i64, i64, vp, vp, vp],
+        "a2p_jpeg_decode_entropy": [vp, i64, vp, vp, i64, i32, i32, i32, i32, vp, i32, vp, vp, vp],
+        "a2p_jpeg_pixels": [vp, i64, i32, i32, i32, i32, i32, vp, vp, i64, i64, vp],
         "a2p_vq_train_workspace_bytes": [i32, i32, i32, i32, i32, i32, C.POINTER(i64)],
         "a2p_vq_train_step": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                               C.POINTER(A2PVqTrainHyper), vp, vp, vp, vp, i64, vp],

@@ -45,6 +45,7 @@
 #include "kernels_surface.h"
 #include "kernels_tail.h"
 #include "kernels_video.h"
+#include "kernels_video_decode.h"
 #include "kernels_vq.h"
 #include "kernels_vq_train.h"
 #include "kernels_window.h"

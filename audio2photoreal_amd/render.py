@@ -327,10 +327,10 @@ def _camera_from_args(args, verts: np.ndarray, H: int, W: int):
     return K[None], Rt[None]
 
 
-def write_pngs(images: dict, directory: str) -> int:
+def write_pngs(images: dict, directory: str, first: int = 0) -> int:
     """<name>_<sequence>_<frame>.png for every frame of every image: normals as 127.5 (1 + n) (black background), the view cosine
     as grey 255 |cos|, the mask as 0 / 255, depth as grey from white (nearest) to dark (farthest) over the clip, positions scaled
-    to their bounding box.  Returns the number of files."""
+    to their bounding box; a uint8 image is written as it is.  `first`: the number of the first frame.  Returns the number of files."""
     from PIL import Image
     os.makedirs(directory, exist_ok=True)
     count = 0
@@ -338,7 +338,9 @@ def write_pngs(images: dict, directory: str) -> int:
     for name, x in images.items():
         x = x.reshape((-1,) + x.shape[-4:]) if x.ndim == 5 else x[None]
         hit = covered[name].reshape(x.shape).any(2, keepdims=True)
-        if name == "normals":
+        if x.dtype == np.uint8:
+            pix = x
+        elif name == "normals":
             pix = 127.5 * (1.0 + x) * hit
         elif name in ("view_cos", "mask"):
             pix = 255.0 * np.abs(x)
@@ -352,7 +354,7 @@ def write_pngs(images: dict, directory: str) -> int:
             for t in range(pix.shape[1]):
                 frame = pix[b, t]
                 img = Image.fromarray(frame[0], "L") if frame.shape[0] == 1 else Image.fromarray(np.ascontiguousarray(frame.transpose(1, 2, 0)), "RGB")
-                img.save(os.path.join(directory, f"{name}_{b:02d}_{t:05d}.png"))
+                img.save(os.path.join(directory, f"{name}_{b:02d}_{first + t:05d}.png"))
                 count += 1
     return count
 

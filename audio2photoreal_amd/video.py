@@ -11,6 +11,12 @@ with the recording's audio, `read_video` takes such a file apart again, and `ren
 slice, so the frames of a long clip never exist at once.  The frames are uint8 tensors that live on the GPU; there is no CPU
 encoder.
 
+The way back (csrc/kernels_video_decode.h): `parse_jpeg_header` reads a file's marker segments on the host, `decode_coefficients` is
+the integer stage (a2p_jpeg_restarts finds the restart intervals, a2p_jpeg_decode_entropy decodes one interval per lane; exact) and
+`pixels` the arithmetic one (a2p_jpeg_pixels: dequantisation, inverse DCT, chroma replication, colour transform; fp32).
+`decode_jpeg_frames` turns JFIF files into uint8 GPU frames, `MJPEGReader` / `read_video_frames` do so for an AVI file, indexed
+through mmap and decoded slice by slice; only compressed bytes go to the GPU, and there is no CPU decoder.
+
 Differences from the reference, on purpose: MJPEG / PCM in AVI instead of H.264 / AAC in MP4 (about ten times the bytes per second
 of video), no ffmpeg, and a file stays below 2 GiB (OpenDML `AVIX` segments are not written)."""
 from __future__ import annotations
@@ -477,6 +483,489 @@ def read_video(path) -> dict:
     return out
 
 
+# ------------------------------------------------------------------------------------------------ reading: headers on the host
+SAMPLINGS = {"444": (3, 1, 1, 3), "422": (3, 2, 1, 4), "420": (3, 2, 2, 6), "gray": (1, 1, 1, 1)}   # name -> (components, luma h, luma v, blocks per MCU)
+_SOF_NAMES = {0xC1: "extended sequential DCT (SOF1)", 0xC2: "progressive DCT (SOF2)", 0xC3: "lossless (SOF3)",
+              0xC5: "differential sequential DCT (SOF5)", 0xC6: "differential progressive DCT (SOF6)", 0xC7: "differential lossless (SOF7)",
+              0xC9: "arithmetic-coded sequential DCT (SOF9)", 0xCA: "arithmetic-coded progressive DCT (SOF10)",
+              0xCB: "arithmetic-coded lossless (SOF11)", 0xCD: "arithmetic-coded differential sequential DCT (SOF13)",
+              0xCE: "arithmetic-coded differential progressive DCT (SOF14)", 0xCF: "arithmetic-coded differential lossless (SOF15)"}
+DEFAULT_DHT = {0x00: _DC_LUMA, 0x10: _AC_LUMA, 0x01: _DC_CHROMA, 0x11: _AC_CHROMA}     # Tc << 4 | Th -> (BITS, HUFFVAL) of Annex K
+
+
+def parse_jpeg_header(data) -> dict:
+    """The marker segments of one baseline JPEG file (bytes or a uint8 array), read on the host: {"size": (H, W), "components": [(id,
+    h, v, tq)], "sampling": "444" | "422" | "420" | "gray", "dqt": {id: uint16 [64] in scan order}, "dht": {Tc << 4 | Th: (BITS,
+    HUFFVAL)}, "default_dht": True when the file carries no DHT and the Annex K tables stand in (the AVI MJPEG convention), "dri":
+    the restart interval in MCUs (0: none), "scan": [(id, td, ta)], "segment": (begin, end) of the entropy-coded segment, "order":
+    the marker codes in file order}.  Read: 8-bit baseline (SOF0) with one component, or three with luminance sampled 1 x 1, 2 x 1 or
+    2 x 2 over 1 x 1 chrominance, in one scan.  Everything else raises A2PError with the name of what the file asks for."""
+    d = data if isinstance(data, bytes) else bytes(data)
+    n = len(d)
+    if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
+        raise A2PError("not a JPEG file: it does not start with SOI")
+    out = {"dqt": {}, "dht": {}, "dri": 0, "order": [0xD8], "size": None, "components": None, "default_dht": False}
+    at = 2
+    while True:
+        if at + 4 > n or d[at] != 0xFF:
+            raise A2PError(f"no marker at byte {at} (the file ends before SOS, or fill bytes precede a marker)")
+        code, length = d[at + 1], d[at + 2] << 8 | d[at + 3]
+        if length < 2 or at + 2 + length > n:
+            raise A2PError(f"the segment of marker {code:#x} at byte {at} runs past the file")
+        body = bytes(d[at + 4:at + 2 + length])
+        out["order"].append(code)
+        if code == 0xDB:
+            while body:
+                if body[0] >> 4:
+                    raise A2PError("16-bit quantisation tables are not read (8-bit baseline JPEG is)")
+                if len(body) < 65:
+                    raise A2PError("a DQT segment is cut short")
+                out["dqt"][body[0] & 15] = np.frombuffer(body[1:65], np.uint8).astype(np.uint16)
+                body = body[65:]
+        elif code == 0xC4:
+            while body:
+                bits = tuple(body[1:17])
+                if len(body) < 17 or len(body) < 17 + sum(bits):
+                    raise A2PError("a DHT segment is cut short")
+                if body[0] >> 4 > 1 or body[0] & 15 > 1:
+                    raise A2PError(f"Huffman table {body[0]:#x}: baseline JPEG holds DC and AC tables 0 and 1")
+                out["dht"][body[0]] = (bits, tuple(body[17:17 + sum(bits)]))
+                body = body[17 + sum(bits):]
+        elif code == 0xC0:
+            if len(body) < 6 or len(body) < 6 + 3 * body[5]:
+                raise A2PError("the SOF0 segment is cut short")
+            if body[0] != 8:
+                raise A2PError(f"{body[0]}-bit samples are not read (8-bit baseline JPEG is)")
+            out["size"] = (body[1] << 8 | body[2], body[3] << 8 | body[4])
+            out["components"] = [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(body[5])]
+        elif code in _SOF_NAMES:
+            raise A2PError(f"{_SOF_NAMES[code]} JPEG is not read (baseline sequential Huffman-coded SOF0 is)")
+        elif code == 0xDD:
+            if len(body) != 2:
+                raise A2PError("a DRI segment of the wrong length")
+            out["dri"] = body[0] << 8 | body[1]
+        elif code == 0xDA:
+            if out["components"] is None:
+                raise A2PError("SOS comes before SOF0")
+            break
+        elif not (0xE0 <= code <= 0xEF or code == 0xFE):
+            raise A2PError(f"marker {code:#x} is not part of baseline JPEG")
+        at += 2 + length
+    comps = out["components"]
+    if len(comps) not in (1, 3):
+        raise A2PError(f"{len(comps)} components are not read (grayscale and three-component YCbCr are)")
+    if out["size"][0] < 1 or out["size"][1] < 1:
+        raise A2PError(f"a frame of {out['size'][0]} x {out['size'][1]} (a height given by DNL is not read)")
+    if len(comps) == 1:
+        out["sampling"] = "gray"
+    else:
+        luma = comps[0][1:3]
+        if comps[1][1:3] != (1, 1) or comps[2][1:3] != (1, 1) or luma not in ((1, 1), (2, 1), (2, 2)):
+            raise A2PError(f"sampling factors {[c[1:3] for c in comps]} are not read (luminance 1 x 1, 2 x 1 or 2 x 2 over 1 x 1 "
+                           "chrominance is: 4:4:4, 4:2:2, 4:2:0)")
+        out["sampling"] = {(1, 1): "444", (2, 1): "422", (2, 2): "420"}[luma]
+    if len(body) < 1 or body[0] != len(comps) or len(body) != 4 + 2 * len(comps):
+        raise A2PError(f"a scan of {body[0] if body else 0} of the {len(comps)} components is not read (one interleaved scan is)")
+    out["scan"] = [(body[1 + 2 * i], body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15) for i in range(body[0])]
+    if tuple(body[-3:]) != (0, 63, 0):
+        raise A2PError("a scan with spectral selection or successive approximation is not read (a sequential scan is)")
+    if [s[0] for s in out["scan"]] != [c[0] for c in comps]:
+        raise A2PError("the scan lists the components in another order than the frame")
+    if not out["dht"]:
+        out["dht"], out["default_dht"] = dict(DEFAULT_DHT), True
+    for cid, td, ta in out["scan"]:
+        if td > 1 or ta > 1 or td not in out["dht"] or (0x10 | ta) not in out["dht"]:
+            raise A2PError(f"component {cid} uses Huffman tables DC {td} / AC {ta}, which the file does not define")
+    for c in comps:
+        if c[3] not in out["dqt"]:
+            raise A2PError(f"component {c[0]} uses quantisation table {c[3]}, which the file does not define")
+    begin = at + 2 + length
+    end = d.rfind(b"\xff\xd9", begin)
+    out["segment"] = (begin, end if end >= 0 else n)
+    if end >= 0:
+        out["order"].append(0xD9)
+    return out
+
+
+def decoder_table(bits, vals) -> np.ndarray:
+    """int32 [JPEG_TABLE_WORDS]: a Huffman table as a2p_jpeg_decode_entropy takes it: maxcode[16], offset[16], the symbols as bytes."""
+    if len(bits) != 16 or sum(bits) != len(vals) or len(vals) > 256:
+        raise A2PError("a Huffman table is 16 counts and as many symbols, at most 256, as they add up to")
+    t = np.zeros(_lib.JPEG_TABLE_WORDS, np.int32)
+    code = k = 0
+    for length in range(1, 17):
+        t[length - 1] = -1
+        if bits[length - 1]:
+            t[16 + length - 1] = k - code
+            code, k = code + bits[length - 1], k + bits[length - 1]
+            if code > 1 << length:
+                raise A2PError(f"a Huffman table with {bits[length - 1]} codes of {length} bits is no prefix code")
+            t[length - 1] = code - 1
+        code <<= 1
+    t[32:].view(np.uint8)[:len(vals)] = np.asarray(vals, np.uint8)
+    return t
+
+
+def _decoder_tables(header) -> np.ndarray:
+    t = np.zeros((_lib.JPEG_TABLES, _lib.JPEG_TABLE_WORDS), np.int32)
+    t[:, :16] = -1
+    for key, (bits, vals) in header["dht"].items():
+        t[(key >> 4) * 2 + (key & 15)] = decoder_table(bits, vals)
+    return t
+
+
+def _header_key(h):
+    return (h["size"], tuple(h["components"]), h["dri"], tuple(h["scan"]), tuple(sorted((k, v.tobytes()) for k, v in h["dqt"].items())),
+            tuple(sorted(h["dht"].items())))
+
+
+def header_qtabs(header) -> np.ndarray:
+    """uint16 [components, 64]: the quantisation table of every component, in scan order, as `pixels` takes them."""
+    return np.stack([header["dqt"][c[3]] for c in header["components"]]).astype(np.uint16)
+
+
+def _jpeg_files(data, offsets):
+    """(buffer, int64 [N + 1]): a list of bytes, or one uint8 array with offsets, as one host buffer."""
+    if offsets is None:
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            data = [data]
+        files = [bytes(f) for f in data]
+        off = np.zeros(len(files) + 1, np.int64)
+        np.cumsum([len(f) for f in files], out=off[1:])
+        return b"".join(files), off
+    off = np.asarray(offsets, np.int64)
+    buf = data.detach().cpu().numpy() if torch.is_tensor(data) else np.asarray(data)
+    if buf.dtype != np.uint8 or buf.ndim != 1 or off.ndim != 1 or len(off) < 1 or (np.diff(off) < 0).any() or off[0] < 0 or off[-1] > len(buf):
+        raise A2PError("data with offsets must be one uint8 array and ascending int64 offsets [N + 1] inside it")
+    return buf.tobytes(), off
+
+
+def _parse_all(buf, off):
+    """The header of every file; a file whose bytes up to the segment equal its predecessor's shares that header's tables."""
+    view, out, prev = memoryview(buf), [], None
+    for n in range(len(off) - 1):
+        a, b = int(off[n]), int(off[n + 1])
+        if prev is not None and b - a >= prev[1] and view[a:a + prev[1]] == prev[0]:
+            h = dict(out[-1])
+            end = buf.rfind(b"\xff\xd9", a + prev[1], b)
+            h["segment"] = (prev[1], end - a if end >= 0 else b - a)
+        else:
+            try:
+                h = parse_jpeg_header(view[a:b])
+            except A2PError as e:
+                raise A2PError(f"frame {n}: {e}") from None
+            prev = (bytes(view[a:a + h["segment"][0]]), h["segment"][0])
+        out.append(h)
+    return out
+
+
+def _device_of(device):
+    if not torch.cuda.is_available():
+        raise A2PError("the frames are decoded on the MI355X; there is no CPU implementation")
+    return torch.device("cuda" if device is None else device)
+
+
+def _status_text(word):
+    return f"interval {int(word) >> 4}: {_lib.JPEG_CAUSES.get(int(word) & 15, 'cause %d' % (int(word) & 15))}"
+
+
+def decode_grid(header):
+    """(mcu_rows, mcu_cols, blocks_per_mcu) of a parsed header."""
+    _, hs, vs, bpm = SAMPLINGS[header["sampling"]]
+    return -(-header["size"][0] // (8 * vs)), -(-header["size"][1] // (8 * hs)), bpm
+
+
+# ------------------------------------------------------------------------------------------------ reading: the launches
+def _entropy_stage(segments, header, dev):
+    """a2p_jpeg_restarts and a2p_jpeg_decode_entropy over the entropy-coded segments (bytes-likes) of frames that share `header`:
+    (coef int16 [n, mcu_rows, mcu_cols, blocks_per_mcu, 64], status int32 [2, n]: the scan's and the decoder's) on dev.  The bytes go
+    to the GPU in one copy; nothing is read back."""
+    rows, cols, bpm = decode_grid(header)
+    intervals = -(-rows * cols // header["dri"]) if header["dri"] else 1
+    n = len(segments)
+    ends = np.cumsum([len(s) for s in segments], dtype=np.int64)
+    segs = np.stack([ends - np.array([len(s) for s in segments], np.int64), ends], 1)
+    data = torch.frombuffer(bytearray().join(segments) or bytearray(1), dtype=torch.uint8).to(dev)
+    key = (str(dev), "decoder", _header_key(header)[5])
+    if key not in _device_tables:
+        _device_tables[key] = torch.from_numpy(_decoder_tables(header)).to(dev)
+    tables = _device_tables[key]
+    selectors = sum((td << i) | (ta << (4 + i)) for i, (_, td, ta) in enumerate(header["scan"]))
+    seg_t = torch.from_numpy(segs).to(dev)
+    ranges = torch.empty(n, intervals + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(2, n, dtype=torch.int32, device=dev)
+    coef = torch.empty(n, rows, cols, bpm, 64, dtype=torch.int16, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = _lib.current_stream(dev)
+        _lib.check(lib.a2p_jpeg_restarts(_lib.ptr(data), int(ends[-1]), _lib.ptr(seg_t), n, intervals, _lib.ptr(ranges), _lib.ptr(status[0]),
+                                         stream), "a2p_jpeg_restarts")
+        _lib.check(lib.a2p_jpeg_decode_entropy(_lib.ptr(data), int(ends[-1]), _lib.ptr(ranges), _lib.ptr(status[0]), n, rows, cols, bpm,
+                                               header["dri"], _lib.ptr(tables), selectors, _lib.ptr(coef), _lib.ptr(status[1]), stream),
+                   "a2p_jpeg_decode_entropy")
+    return coef, status
+
+
+def _bad_frames(status):
+    """[(index, status word)] of the frames a status array [2, n] (on the host) marks; the scan's verdict comes first."""
+    return [(i, int(status[0, i] or status[1, i])) for i in np.nonzero((status != 0).any(0))[0]]
+
+
+def decode_coefficients(data, offsets=None, device=None):
+    """The integer stage: a list of JFIF files as bytes (or one uint8 array with `offsets` [N + 1], as encode_jpeg_frames returns them)
+    that share one header -> (coef, header): int16 [N, mcu_rows, mcu_cols, blocks_per_mcu, 64] on the GPU, the quantised coefficients
+    in scan order (what `coefficients` writes and `entropy_segments` reads), and the parsed header of the first file.  Exact: entropy
+    coding is lossless.  A frame the decoder rejects raises A2PError naming the frame, the restart interval and the cause."""
+    buf, off = _jpeg_files(data, offsets)
+    dev = _device_of(device)
+    headers = _parse_all(buf, off)
+    if not headers:
+        raise A2PError("decode_coefficients needs at least one file")
+    if any(_header_key(h) != _header_key(headers[0]) for h in headers[1:]):
+        raise A2PError("decode_coefficients takes files that share one header (size, sampling, tables); decode_jpeg_frames groups mixed ones")
+    view = memoryview(buf)
+    segments = [view[int(off[n]) + h["segment"][0]:int(off[n]) + h["segment"][1]] for n, h in enumerate(headers)]
+    coef, status = _entropy_stage(segments, headers[0], dev)
+    bad = _bad_frames(status.cpu().numpy())
+    if bad:
+        raise A2PError(f"frame {bad[0][0]} is rejected: {_status_text(bad[0][1])}" + (f" ({len(bad)} frames in all)" if len(bad) > 1 else ""))
+    return coef, headers[0]
+
+
+def _out_arg(out, N, H, W, dev):
+    if out is None:
+        return torch.empty(N, H, W, 3, dtype=torch.uint8, device=dev)
+    if not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W, 3):
+        raise A2PError(f"out must be a uint8 GPU tensor [{N}, {H}, {W}, 3] (got {type(out).__name__} "
+                       f"{list(out.shape) if torch.is_tensor(out) else ''})")
+    sn, sh, sw, sc = out.stride()
+    if N and (sc != 1 or sw != 3 or (H > 1 and sh < 3 * W) or (N > 1 and sn < (H - 1) * sh + 3 * W)):
+        raise A2PError(f"out must hold pixels of 3 dense bytes, rows at least 3 W bytes apart and frames that do not overlap (strides {out.stride()})")
+    return out
+
+
+def pixels(coef, height: int, width: int, qtabs, sampling: str = "420", out=None):
+    """The arithmetic stage, one launch of a2p_jpeg_pixels: int16 coefficients [N, mcu_rows, mcu_cols, blocks_per_mcu, 64] on the GPU
+    -> uint8 frames [N, height, width, 3].  qtabs: uint16 [components, 64] in scan order, one table per component (header_qtabs);
+    sampling: "444", "422", "420" or "gray".  out: a uint8 GPU tensor [N, height, width, 3] whose rows and frames may be strided (a
+    column window of a wider image): only the window is written."""
+    if str(sampling) not in SAMPLINGS:
+        raise A2PError(f"sampling={sampling!r}: need one of {sorted(SAMPLINGS)}")
+    ncomp, hs, vs, bpm = SAMPLINGS[str(sampling)]
+    if not torch.is_tensor(coef):
+        raise A2PError(f"coef must be a torch tensor on the GPU (got {type(coef).__name__})")
+    _lib.require_gpu_tensor(coef, "coef")
+    H, W = int(height), int(width)
+    if not (1 <= H <= _lib.JPEG_MAX_SIZE and 1 <= W <= _lib.JPEG_MAX_SIZE):
+        raise A2PError(f"a frame of {height} x {width} is outside [1, {_lib.JPEG_MAX_SIZE}]")
+    want = (-(-H // (8 * vs)), -(-W // (8 * hs)), bpm, 64)
+    if coef.dtype != torch.int16 or coef.dim() != 5 or tuple(coef.shape[1:]) != want:
+        raise A2PError(f"coef must be int16 [N, {want[0]}, {want[1]}, {bpm}, 64] for {H} x {W} frames sampled {sampling} (got {coef.dtype} "
+                       f"{list(coef.shape)})")
+    q = qtabs.detach().cpu().numpy() if torch.is_tensor(qtabs) else np.asarray(qtabs)
+    if q.shape != (ncomp, 64) or not np.issubdtype(q.dtype, np.integer) or q.min() < 1 or q.max() > 255:
+        raise A2PError(f"qtabs must be [{ncomp}, 64] integers in [1, 255], one table per component in scan order (got {list(q.shape)})")
+    coef = coef.contiguous()
+    N, dev = coef.shape[0], coef.device
+    out = _out_arg(out, N, H, W, dev)
+    if N == 0:
+        return out
+    key = (str(dev), "dequant", q.astype(np.uint16).tobytes())
+    if key not in _device_tables:
+        _device_tables[key] = torch.from_numpy(q.astype(np.int16)).to(dev)
+    with _lib.on_device_of(coef):
+        _lib.check(_lib.load().a2p_jpeg_pixels(_lib.ptr(coef), N, H, W, ncomp, hs, vs, _lib.ptr(_device_tables[key]), _lib.ptr(out),
+                                               out.stride(0) if N > 1 else (H - 1) * out.stride(1) + 3 * W, out.stride(1) if H > 1 else 3 * W,
+                                               _lib.current_stream(dev)), "a2p_jpeg_pixels")
+    return out
+
+
+def decode_jpeg_frames(data, offsets=None, out=None, max_bytes: int = 1 << 28, on_error: str = "raise", device=None):
+    """Baseline JPEG files -> uint8 frames [N, H, W, 3] on the GPU.  data: a list of bytes, one JFIF file each, or one uint8 array with
+    `offsets` [N + 1] as encode_jpeg_frames returns them.  All frames share one size; frames with identical headers go through one
+    set of launches (a2p_jpeg_restarts, a2p_jpeg_decode_entropy, a2p_jpeg_pixels), frames with other tables are grouped by header.
+    The coefficients of at most max_bytes (at least one frame) exist at a time; per slice the entropy-coded bytes go to the GPU in
+    one copy, and the status of every frame comes back in one read at the end.  out: a uint8 GPU tensor [N, H, W, 3], rows and
+    frames may be strided.  A frame the decoder rejects raises A2PError naming the frame, the restart interval and the cause;
+    on_error="mark" returns (frames, [bad indices]) instead, the bad frames zeroed.  A frame's bytes depend on that frame alone."""
+    if on_error not in ("raise", "mark"):
+        raise ValueError(f"on_error={on_error!r}: need 'raise' or 'mark'")
+    buf, off = _jpeg_files(data, offsets)
+    dev = _device_of(device if out is None or not torch.is_tensor(out) else out.device)
+    headers = _parse_all(buf, off)
+    N = len(headers)
+    if N == 0:
+        if out is None:
+            raise A2PError("decode_jpeg_frames needs at least one file (the frame size comes from the files)")
+        return (out, []) if on_error == "mark" else out
+    H, W = headers[0]["size"]
+    for n, h in enumerate(headers):
+        if h["size"] != (H, W):
+            raise A2PError(f"frame {n} is {h['size'][0]} x {h['size'][1]}, frame 0 is {H} x {W}: the frames of one call share one size")
+    out = _out_arg(out, N, H, W, dev)
+    groups = {}
+    for n, h in enumerate(headers):
+        groups.setdefault(_header_key(h), []).append(n)
+    view, statuses, order = memoryview(buf), [], []
+    for idx in groups.values():
+        h0 = headers[idx[0]]
+        rows, cols, bpm = decode_grid(h0)
+        step = max(1, int(max_bytes) // (rows * cols * bpm * 128))
+        for a in range(0, len(idx), step):
+            part = idx[a:a + step]
+            segments = [view[int(off[n]) + headers[n]["segment"][0]:int(off[n]) + headers[n]["segment"][1]] for n in part]
+            coef, status = _entropy_stage(segments, h0, dev)
+            run = part[-1] - part[0] + 1 == len(part)              # a run of neighbours is decoded in place
+            got = pixels(coef, H, W, header_qtabs(h0), h0["sampling"], out[part[0]:part[-1] + 1] if run else None)
+            if not run:
+                out[torch.as_tensor(part, device=dev)] = got
+            statuses.append(status)
+            order += part
+    status = torch.cat(statuses, 1).cpu().numpy()
+    bad = sorted((order[i], word) for i, word in _bad_frames(status))
+    if bad and on_error == "raise":
+        raise A2PError(f"frame {bad[0][0]} is rejected: {_status_text(bad[0][1])}" + (f" ({len(bad)} frames in all)" if len(bad) > 1 else ""))
+    if bad:
+        out[torch.as_tensor([n for n, _ in bad], device=dev)] = 0
+    return (out, [n for n, _ in bad]) if on_error == "mark" else out
+
+
+# ------------------------------------------------------------------------------------------------ reading: the container
+class MJPEGReader:
+    """An AVI file of MJPEGWriter (or one laid out like it: `hdrl` with strh / strf per stream, `movi` with `##dc` and `##wb`
+    chunks, below 2 GiB) read back as frames on the GPU.  The `movi` chunks are indexed once through mmap; the file is never
+    loaded.  len(), fps, size (height, width), audio (int16 [samples] or [samples, channels], or None), audio_rate; frame_bytes(i)
+    is frame i as a JFIF file; read(start, count) returns uint8 GPU frames [count, height, width, 3]; iterating yields the clip
+    in slices of slice_frames frames, so a long clip never exists at once."""
+
+    def __init__(self, path, slice_frames: int = 64, device=None):
+        import mmap
+        self.path, self.slice_frames, self.device = os.fspath(path), max(1, int(slice_frames)), device
+        self._f = open(self.path, "rb")
+        size = os.fstat(self._f.fileno()).st_size
+        if size < 12:
+            self._f.close()
+            raise ValueError(f"{path} is not a RIFF AVI file")
+        self._m = mmap.mmap(self._f.fileno(), 0, access=mmap.ACCESS_READ)
+        m = self._m
+        if m[:4] != b"RIFF" or m[8:12] != b"AVI ":
+            self.close()
+            raise ValueError(f"{path} is not a RIFF AVI file")
+        self.fps = self.size = self.audio_rate = None
+        self._video, self._audio, self._channels, kinds = [], [], None, []
+
+        def walk(a, b, inside):
+            while a + 8 <= b:
+                fourcc, size = m[a:a + 4], struct.unpack_from("<I", m, a + 4)[0]
+                body = a + 8
+                if body + size > b:
+                    raise ValueError(f"{path}: chunk {fourcc!r} at {a} runs past its list")
+                if fourcc == b"LIST":
+                    walk(body + 4, body + size, m[body:body + 4])
+                elif fourcc == b"strh":
+                    kinds.append(m[body:body + 4])
+                    if kinds[-1] == b"vids":
+                        scale, rate = struct.unpack_from("<II", m, body + 20)
+                        self.fps = rate / scale
+                elif fourcc == b"strf" and kinds and kinds[-1] == b"vids":
+                    w, h = struct.unpack_from("<ii", m, body + 4)
+                    self.size = (h, w)
+                elif fourcc == b"strf" and kinds and kinds[-1] == b"auds":
+                    tag, self._channels, rate, _, _, width = struct.unpack_from("<HHIIHH", m, body)
+                    if tag != 1 or width != 16:
+                        raise ValueError(f"{path}: the audio is format {tag} with {width} bits; 16-bit PCM is read")
+                    self.audio_rate = rate
+                elif inside == b"movi" and fourcc[2:] == b"dc":
+                    self._video.append((body, size))
+                elif inside == b"movi" and fourcc[2:] == b"wb":
+                    self._audio.append((body, size))
+                a = body + size + (size & 1)
+
+        try:
+            walk(12, min(len(m), 8 + struct.unpack_from("<I", m, 4)[0]), b"AVI ")
+        except Exception:
+            self.close()
+            raise
+
+    def __len__(self):
+        return len(self._video)
+
+    @property
+    def chunks(self):
+        """[(offset of the payload in the file, size)] of the video chunks."""
+        return list(self._video)
+
+    @property
+    def audio(self):
+        if self._channels is None:
+            return None
+        pcm = np.frombuffer(b"".join(self._m[a:a + n] for a, n in self._audio), "<i2").reshape(-1, self._channels)
+        return pcm[:, 0].copy() if self._channels == 1 else pcm.copy()
+
+    def frame_bytes(self, i: int) -> bytes:
+        a, n = self._video[i]
+        return self._m[a:a + n]
+
+    def read(self, start: int = 0, count=None, out=None):
+        """uint8 GPU frames [count, height, width, 3]: frames start .. start + count - 1 (count=None: to the end)."""
+        start = int(start)
+        stop = len(self) if count is None else start + int(count)
+        if not (0 <= start <= stop <= len(self)):
+            raise A2PError(f"frames [{start}, {stop}) are outside the file's {len(self)}")
+        if stop == start:
+            if self.size is None:
+                raise A2PError(f"{self.path} holds no video stream")
+            return torch.empty(0, self.size[0], self.size[1], 3, dtype=torch.uint8, device=_device_of(self.device))
+        try:
+            return decode_jpeg_frames([self.frame_bytes(i) for i in range(start, stop)], out=out, device=self.device)
+        except A2PError as e:
+            raise A2PError(f"{self.path}, from frame {start}: {e}") from None
+
+    def __iter__(self):
+        for a in range(0, len(self), self.slice_frames):
+            yield self.read(a, min(self.slice_frames, len(self) - a))
+
+    def close(self):
+        for name in ("_m", "_f"):
+            obj = getattr(self, name, None)
+            if obj is not None:
+                obj.close()
+                setattr(self, name, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def read_video_frames(path, start: int = 0, count=None, slice_frames: int = 64, device=None) -> dict:
+    """{"frames": uint8 GPU tensor [count, height, width, 3], "fps", "audio", "audio_rate"} of an AVI file of MJPEGWriter: frames
+    start .. start + count - 1 (count=None: to the end), decoded slice_frames at a time into one tensor.  A frame's bytes do not
+    depend on the slicing."""
+    with MJPEGReader(path, slice_frames, device) as r:
+        start = int(start)
+        stop = len(r) if count is None else start + int(count)
+        if not (0 <= start <= stop <= len(r)):
+            raise A2PError(f"frames [{start}, {stop}) are outside the file's {len(r)}")
+        frames = None
+        for a in range(start, stop, r.slice_frames):
+            b = min(stop, a + r.slice_frames)
+            if frames is None:
+                first = r.read(a, b - a)
+                if b == stop:
+                    frames = first
+                    break
+                frames = torch.empty(stop - start, *first.shape[1:], dtype=torch.uint8, device=first.device)
+                frames[:b - a] = first
+            else:
+                r.read(a, b - a, out=frames[a - start:b - start])
+        if frames is None:
+            frames = r.read(start, 0)
+        return {"frames": frames, "fps": r.fps, "audio": r.audio, "audio_rate": r.audio_rate}
+
+
 # ------------------------------------------------------------------------------------------------ rendering into a file
 def render_codes_video(face_decoder, face_encoder, body_encoder, decoder, texture, skeleton, rasterizer, poses, face_codes, K, Rt, path,
                        audio=None, audio_rate=None, fps=30, quality: int = 90, subsampling: str = "420", slice_frames: int = 32, **kw) -> int:
@@ -508,8 +997,57 @@ def sequence_path(path: str, index: int, count: int) -> str:
     return f"{stem}_{index:02d}{ext}"
 
 
+def _extract_main(argv) -> int:
+    """--extract clip.avi --out frames.npy [--frames A:B] [--png-dir DIR] [--wav out.wav]: the frames of an AVI file, decoded on the GPU."""
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m audio2photoreal_amd.video --extract",
+                                 description="The frames (and the audio) of a Motion-JPEG AVI file, decoded on the MI355X.")
+    ap.add_argument("--extract", required=True, metavar="AVI", help="the AVI file, as this module writes it")
+    ap.add_argument("--out", required=True, help="frames.npy: uint8 [T, H, W, 3]")
+    ap.add_argument("--frames", default=None, metavar="A:B", help="the frames A .. B - 1 (default: all)")
+    ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write frame_00_<frame>.png per frame")
+    ap.add_argument("--wav", default=None, metavar="FILE", help="also write the audio as a 16-bit PCM wav file")
+    ap.add_argument("--slice-frames", type=int, default=64, help="frames on the GPU at a time")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise A2PError("the frames are decoded on the MI355X; there is no CPU implementation")
+    with MJPEGReader(args.extract, args.slice_frames) as r:
+        a, b = 0, len(r)
+        if args.frames is not None:
+            lo, _, hi = args.frames.partition(":")
+            a, b = int(lo) if lo else 0, int(hi) if hi else len(r)
+        if not (0 <= a <= b <= len(r)) or r.size is None:
+            raise A2PError(f"--frames {args.frames}: {args.extract} holds {len(r)} frames")
+        frames = np.lib.format.open_memmap(args.out, mode="w+", dtype=np.uint8, shape=(b - a, r.size[0], r.size[1], 3))
+        for s in range(a, b, r.slice_frames):
+            frames[s - a:min(b, s + r.slice_frames) - a] = r.read(s, min(b, s + r.slice_frames) - s).cpu().numpy()
+        frames.flush()
+        print(f"{args.out}: frames {a} .. {b - 1} of {len(r)}, {r.size[0]} x {r.size[1]} at {r.fps:g} fps")
+        if args.png_dir is not None:
+            from .render import write_pngs
+            count = sum(write_pngs({"frame": np.ascontiguousarray(frames[t].transpose(2, 0, 1))[None]}, args.png_dir, first=a + t)
+                        for t in range(b - a))                            # one frame at a time; the name carries its index in the file
+            print(f"{args.png_dir}: {count} png files")
+        if args.wav is not None:
+            import wave
+            audio = r.audio
+            if audio is None:
+                raise A2PError(f"{args.extract} holds no audio stream")
+            with wave.open(args.wav, "wb") as w:
+                w.setnchannels(1 if audio.ndim == 1 else audio.shape[1])
+                w.setsampwidth(2)
+                w.setframerate(r.audio_rate)
+                w.writeframes(audio.astype("<i2").tobytes())
+            print(f"{args.wav}: {audio.shape[0]} samples at {r.audio_rate} Hz")
+    return 0
+
+
 def main(argv=None) -> int:
     import argparse
+    import sys
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if any(a == "--extract" or a.startswith("--extract=") for a in argv):
+        return _extract_main(argv)
     ap = argparse.ArgumentParser(prog="python -m audio2photoreal_amd.video",
                                  description="uint8 frames (and a wav file) to a Motion-JPEG AVI file, encoded on the MI355X.")
     ap.add_argument("--frames", required=True, help="frames.npy: uint8 [T, H, W, 3] or [R, T, H, W, 3] (what python -m "

@@ -903,6 +903,65 @@ int a2p_jpeg_entropy(const int16_t* coef, int64_t N, int32_t mcu_rows, int32_t m
                      const uint8_t* head, int32_t head_bytes, const uint8_t* tail, int32_t tail_bytes, int64_t* interval,
                      int64_t* offsets, uint8_t* out, int64_t out_bytes, void* stream);
 
+/* ---- reading video frames (audio2photoreal_amd/video.py decode_jpeg_frames, MJPEGReader) --
+ * Baseline sequential, 8-bit, Huffman-coded JPEG back to uint8 RGB, the mirror of the two stages above: an integer stage (restart
+ * scan, entropy decoding; exact) and an arithmetic stage (fp32).  Context-free, on the caller's stream, 64-bit offsets, integer
+ * atomics only (a minimum); a frame's result depends on that frame and the tables alone; an output must not overlap an input; N = 0
+ * launches nothing.  The host parses the marker segments (video.py parse_jpeg_header); the GPU sees entropy-coded bytes only and
+ * trusts none of them: every byte index is compared with its interval's end before the byte is read, every loop is bounded by the
+ * geometry, and nothing is written outside the frame's own ranges, coefficients and status.
+ *
+ * Read: one component (an MCU is one block), or three with luminance sampled 1 x 1 (4:4:4, blocks Y Cb Cr), 2 x 1 (4:2:2, Y0 Y1 Cb
+ * Cr) or 2 x 2 (4:2:0, Y00 Y01 Y10 Y11 Cb Cr) over 1 x 1 chrominance; any Huffman tables with codes up to 16 bits; any restart
+ * interval.  Not read, and rejected by the host before any launch: progressive, extended and arithmetic-coded frames, 12-bit
+ * samples, 16-bit quantisation tables, four components, other sampling factors.
+ *
+ * status: int32 per frame, 0 or (interval << 4) | cause of the first failing interval, cause one of A2P_JPEG_ERR_*.
+ *
+ * a2p_jpeg_restarts: data uint8 [data_bytes], the entropy-coded segments of N frames; segments int64 [N][2], begin and end of every
+ * frame's segment in data (clamped to [0, data_bytes]) -> ranges int64 [N][intervals + 1]: ranges[k], k < intervals, is where
+ * interval k starts, ranges[intervals] the segment's end; interval k ends 2 bytes (its RSTm) before ranges[k + 1], the last one at
+ * the end.  intervals = ceil(mcus / Ri), 1 without DRI.  A frame passes when it holds exactly intervals - 1 markers, RST0 .. RST7
+ * cyclically, and no other: 0xFF is followed by 0x00 or the RSTm due.  One workgroup per frame scans chunks of 4096 bytes: count,
+ * prefix sum within the workgroup, write positions.
+ *
+ * a2p_jpeg_decode_entropy: those ranges -> coef int16 [N, mcu_rows, mcu_cols, blocks_per_mcu, 64] in scan order, the layout of
+ * a2p_jpeg_coefficients (blocks_per_mcu 1, 3, 4 or 6); coef and status are zeroed on the stream first and only non-zero
+ * coefficients are stored.  One lane per restart interval: byte unstuffing, Huffman decoding from tables in LDS, amplitude
+ * extension, DC prediction from 0 in every interval.  restart_interval = 0 (no DRI) is ONE interval and therefore one lane per
+ * frame: slow and correct.  restart_status: the status of a2p_jpeg_restarts or NULL; frames it marks are left zero.  tables: int32
+ * [A2P_JPEG_TABLES][A2P_JPEG_TABLE_WORDS], DC 0, DC 1, AC 0, AC 1, each maxcode[16] (largest code of length l + 1, -1 for none),
+ * offset[16] (index of that length's first symbol minus its first code), then the 256 symbols as bytes.  selectors: bit c the DC
+ * table of component c, bit 4 + c its AC table.  A DC category above 11 or an AC size above 10 is not 8-bit baseline and stops the
+ * lane, as do a code in no table, a run past coefficient 63, an interval that ends inside a code and a byte left over.
+ *
+ * a2p_jpeg_pixels: coef in that layout, qtab uint16 [components][64] in scan order (as DQT stores them, one per component in scan
+ * order) -> out uint8 [N, H, W, 3] with frames frame_stride and rows row_stride BYTES apart (row_stride >= 3 W: a clip decodes
+ * straight into a column window of a wider image; no byte outside the window is written).  fp32, one product and seven fmaf per
+ * 8-point sum with the index ascending:
+ *   F = coef Q;  t(y, u) = sum over v of F(v, u) c(v, y), then s(y, x) = sum over u of t(y, u) c(u, x),  c(u, x) = C(u) / 2 cos((2 x + 1) u pi / 16)
+ *   sample = clamp(s + 128, 0, 255)  (T.81 A.3.1);  a chroma sample serves its whole luma_h x luma_v group (replication, the inverse
+ *   of the encoder's box mean; libjpeg's triangle "fancy" upsampling is deliberately not reproduced)
+ *   R = Y + 1.402 Cr';  G = Y - 0.344136286 Cb' - 0.714136286 Cr';  B = Y + 1.772 Cb'  (Cb' = Cb - 128, Cr' = Cr - 128; G adds the Cb
+ *   term first);  rintf, clamp to [0, 255], crop to H x W.  One component goes to all three channels. */
+#define A2P_JPEG_TABLES 4
+#define A2P_JPEG_TABLE_WORDS 96
+#define A2P_JPEG_ERR_RST_COUNT 1
+#define A2P_JPEG_ERR_RST_ORDER 2
+#define A2P_JPEG_ERR_MARKER 3
+#define A2P_JPEG_ERR_NO_CODE 4
+#define A2P_JPEG_ERR_RUN 5
+#define A2P_JPEG_ERR_ENDS_IN_CODE 6
+#define A2P_JPEG_ERR_AMPLITUDE 7
+#define A2P_JPEG_ERR_TRAILING 8
+int a2p_jpeg_restarts(const uint8_t* data, int64_t data_bytes, const int64_t* segments, int64_t N, int64_t intervals, int64_t* ranges,
+                      int32_t* status, void* stream);
+int a2p_jpeg_decode_entropy(const uint8_t* data, int64_t data_bytes, const int64_t* ranges, const int32_t* restart_status, int64_t N,
+                            int32_t mcu_rows, int32_t mcu_cols, int32_t blocks_per_mcu, int32_t restart_interval, const int32_t* tables,
+                            int32_t selectors, int16_t* coef, int32_t* status, void* stream);
+int a2p_jpeg_pixels(const int16_t* coef, int64_t N, int32_t H, int32_t W, int32_t components, int32_t luma_h, int32_t luma_v,
+                    const uint16_t* qtab, uint8_t* out, int64_t frame_stride, int64_t row_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
