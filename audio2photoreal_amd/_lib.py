@@ -19,9 +19,13 @@ LIB_PATH_F16 = os.environ.get("A2P_LIB_F16") or os.path.join(_HERE, "liba2p_hip_
 FACE, POSE = 0, 1
 PREC_F32, PREC_BF16 = 0, 1
 PASS_COND, PASS_UNCOND, PASS_CFG = 0, 1, 2
+PASS_KEYS, PASS_CFG_AUDIO, PASS_CFG_DUAL = 3, 4, 5    # body model: audio and keyframes dropped separately (a2p_hip.h)
+GUIDE_JOINT, GUIDE_AUDIO, GUIDE_DUAL = 0, 1, 2        # a2p_set_guidance
+GUIDANCE_MODES = {"joint": GUIDE_JOINT, "audio": GUIDE_AUDIO, "dual": GUIDE_DUAL}   # y["guidance"]
 SAMPLER_DDIM, SAMPLER_DDPM = 0, 1
 KERNEL_GEMM, KERNEL_ATTN_SELF, KERNEL_ATTN_CROSS, KERNEL_LNROPE, KERNEL_CHAIN = 0, 1, 2, 3, 4
 KERNEL_CHAIN_PRE, KERNEL_CHAIN_MID, KERNEL_CHAIN_POST, KERNEL_CHAIN_MIDPOST, KERNEL_POSE_TAIL = 5, 6, 7, 8, 9   # finer classes (a2p_hip.h)
+KERNEL_GUIDE_COMBINE = 10
 # a2p_table_id
 TABLE_NAMES = (
     "posterior_mean_coef1", "posterior_mean_coef2", "posterior_variance", "posterior_log_variance_clipped",
@@ -54,6 +58,7 @@ EXPORTS = (
     "a2p_linear_f32", "a2p_conv2d_down3_ub", "a2p_unskin_vertices", "a2p_face_tex_cond",
     "a2p_jpeg_coefficients", "a2p_jpeg_entropy", "a2p_jpeg_restarts", "a2p_jpeg_decode_entropy", "a2p_jpeg_pixels",
     "a2p_vq_train_workspace_bytes", "a2p_vq_train_step",
+    "a2p_set_guidance",
 )
 
 
@@ -218,6 +223,7 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_debug_read": [vp, C.c_char_p, vp, i64],
         "a2p_reload_env": [vp],
         "a2p_set_batch_hint": [vp, i32],
+        "a2p_set_guidance": [vp, i32, vp],
         "a2p_check_finite": [vp, vp],
         "a2p_attention_logit_max": [vp, C.POINTER(C.c_float), vp],
         "a2p_precision_verdict": [vp, C.POINTER(C.c_float), C.POINTER(i32), vp],

@@ -262,6 +262,12 @@ struct a2p_ctx {
   std::map<int64_t, ChainTune> ch_tune4;   // per forward size: kernels_chain.h (1) or kernels_chain4.h (4), measured in situ (chain_pick_family)
   int ch_fam_mid = 4, ch_fam_post = 4;     // chain kernel families of the forward being enqueued (MID kernels, POST kernels)
   Buf hidden, kc, vtc, k2c, vt2c, slot_cond, slot_unc, slot_cfg;
+  // separate guidance of audio and keyframes (a2p_set_guidance; body model): per-sequence slot tables of the 2B / 3B sequence passes,
+  // audio + hidden [1+b | 0 | 0] and keyframes [1+b | 1+b | 0], filled for slot3_B samples by the first forward that needs them
+  Buf slot_a3, slot_kf3;
+  int slot3_B = 0;
+  int guide_mode = 0;                  // A2P_GUIDE_*: what the guided entry points (a2p_sample_step*) evaluate
+  const float* scale_kf = nullptr;     // fp32 [B] device, caller-owned: y["scale_keyframes"] of A2P_GUIDE_DUAL
   Buf nonfinite;         // device flag of a2p_check_finite (one int, OR-ed by step_tail_kernel)
   Buf clk;               // A2P_CHAIN_CLK=1: 64 chain launches x 8 blocks x {memtime, realtime} x {begin, end}
   unsigned clk_turn = 0;
@@ -710,6 +716,7 @@ extern "C" int a2p_ctx_create(const a2p_config* cfg, a2p_ctx** out) {
     A(c->kf_pack, (size_t)B * c->KFmax * c->KdPad * c->esz); A(c->kf_tok, (size_t)B * c->KFmax * d * 4);
   }
   A(c->slot_cond, B * 4); A(c->slot_unc, B * 4); A(c->slot_cfg, N * 4); A(c->nonfinite, 64);
+  if (c->pose) { A(c->slot_a3, N * 4); A(c->slot_kf3, N * 4); }   // a three-branch pass runs 3 B <= Nmax sequences
   // logit maximum: "none yet" (0x80808080 < every ordered float).  Synchronous: callers run on non-blocking streams, which do not
   // order behind the null stream -- a first attention could otherwise atomicMax before the sentinel lands and lose its value
   if (rc == 0 && (hipMemsetAsync(reinterpret_cast<int*>(c->nonfinite.p) + 1, 0x80, 4, nullptr) != hipSuccess ||
@@ -736,6 +743,16 @@ extern "C" int a2p_set_batch_hint(a2p_ctx* c, int32_t global_batch) {
   return 0;
 }
 
+extern "C" int a2p_set_guidance(a2p_ctx* c, int32_t mode, const float* scale_keyframes) {
+  ARG(c, "null ctx");
+  ARG(mode >= A2P_GUIDE_JOINT && mode <= A2P_GUIDE_DUAL, "bad guidance mode %d", mode);
+  ARG(mode == A2P_GUIDE_JOINT || c->pose, "guidance mode %d separates audio from keyframes: the face model has no keyframes", mode);
+  ARG(mode != A2P_GUIDE_DUAL || scale_keyframes, "A2P_GUIDE_DUAL needs scale_keyframes");
+  c->guide_mode = mode;
+  c->scale_kf = mode == A2P_GUIDE_DUAL ? scale_keyframes : nullptr;
+  return 0;
+}
+
 static void graphs_drop(a2p_ctx* c);   // a2p_lib_run.h: waits for the device, then destroys every captured forward
 
 extern "C" int a2p_reload_env(a2p_ctx* c) {
@@ -759,7 +776,7 @@ extern "C" int a2p_ctx_destroy(a2p_ctx* c) {
                 &c->k2c, &c->vt2c, &c->slot_cond, &c->slot_unc, &c->slot_cfg, &c->x, &c->xn, &c->xr, &c->qk, &c->vt, &c->ao,
                 &c->hff, &c->inpack, &c->mo, &c->cb[0], &c->cb[1], &c->cb[2], &c->cb[3], &c->emb, &c->th, &c->tct, &c->tvec,
                 &c->mt, &c->tokn, &c->tokr, &c->film, &c->ktail, &c->vtail, &c->ce_pack, &c->pooled, &c->tmpa, &c->tmpb,
-                &c->kf_pack, &c->kf_tok, &c->clk, &c->t3, &c->nonfinite, &c->tail_w, &c->tail_b};
+                &c->kf_pack, &c->kf_tok, &c->clk, &c->t3, &c->nonfinite, &c->tail_w, &c->tail_b, &c->slot_a3, &c->slot_kf3};
   for (Buf* b : all) buf_free(*b);
   for (int i = 0; i < 7; ++i) buf_free(c->conv_wt[i]);
   for (auto& b : c->ch_stream) buf_free(b);

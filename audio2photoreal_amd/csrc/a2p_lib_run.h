@@ -882,6 +882,28 @@ __global__ void slot_tables_kernel(int* cond, int* unc, int* cfg, int B) {
   }
 }
 
+// The passes that drop audio and keyframes separately (body model; include/a2p_hip.h A2P_PASS_KEYS .. _CFG_DUAL), as sequence blocks of
+// B: [e(K,A) | e(K,0)] for A2P_PASS_CFG_AUDIO, [e(K,A) | e(K,0) | e(0,0)] for A2P_PASS_CFG_DUAL.  a3: audio K/V and pooled-hidden slots
+// (the closed form is rule 3 with slot_b = B, as for A2P_PASS_CFG; the time path reads the table), kf3: keyframe K/V slots (table only;
+// the two-block pass reads its first 2B entries).  cap: entries per table.
+__global__ void slot_tables3_kernel(int* a3, int* kf3, int B, int cap) {
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    a3[b] = 1 + b; kf3[b] = 1 + b;
+    a3[B + b] = 0; kf3[B + b] = 1 + b;
+    if (2 * B + b < cap) { a3[2 * B + b] = 0; kf3[2 * B + b] = 0; }
+  }
+}
+static bool pass_split(int pass) { return pass >= A2P_PASS_KEYS && pass <= A2P_PASS_CFG_DUAL; }
+static int pass_nseq(int pass, int B) {
+  return pass == A2P_PASS_CFG_DUAL ? 3 * B : ((pass == A2P_PASS_CFG || pass == A2P_PASS_CFG_AUDIO) ? 2 * B : B);
+}
+// slot rule of the audio K/V of a pass (AttnP::slot_rule): 1 = 1 + seq, 2 = 0, 3 = seq < B ? 1 + seq : 0
+static int pass_audio_rule(int pass) {
+  if (pass == A2P_PASS_COND) return 1;
+  if (pass == A2P_PASS_UNCOND || pass == A2P_PASS_KEYS) return 2;
+  return 3;
+}
+
 extern "C" int a2p_prepare_cond(a2p_ctx* c, const float* cond_embed, int32_t B, int32_t S0, const float* keyframes,
                                 const uint8_t* key_mask, int32_t n_key, int32_t T, void* stream) {
   ARG(c && cond_embed, "null argument");
@@ -1026,9 +1048,13 @@ static int forward_ext(a2p_ctx* c, const float* x_in, const int64_t* t_orig, hip
 static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, int pass, int* mo_seq_rows, hipStream_t s, bool ext,
                         bool use_chain, bool use_small) {
   const int d = c->d, B = c->pB, T = c->pT, L = c->L, F = c->F;
-  const int N = pass == A2P_PASS_CFG ? 2 * B : B;
+  const int N = pass_nseq(pass, B);
   c->clk_turn = 0;
-  const int* slots = (const int*)(pass == A2P_PASS_CFG ? c->slot_cfg.p : (pass == A2P_PASS_COND ? c->slot_cond.p : c->slot_unc.p));
+  // audio K/V and pooled-hidden slot of every sequence; the keyframe K/V follow it except in the passes that drop the two separately
+  const int* slots = (const int*)(pass == A2P_PASS_CFG_DUAL ? c->slot_a3.p
+                                  : (pass == A2P_PASS_CFG || pass == A2P_PASS_CFG_AUDIO) ? c->slot_cfg.p
+                                  : pass == A2P_PASS_COND ? c->slot_cond.p : c->slot_unc.p);
+  const int* slots_kf = (const int*)(pass == A2P_PASS_KEYS ? c->slot_cond.p : (pass_split(pass) ? c->slot_kf3.p : (const void*)slots));
   // The time path (7 latency-bound launches, ~70 us at B=8) is not needed before the first out_proj epilogue and can run on
   // the side stream next to input projection / norm1+QKV / self attention of layer 0 (-2..3 % step time).  On by default since
   // round 2 (A2P_NO_SIDE_STREAM=1 turns it off): in round 1, with the two queues active, 1-30 % of forwards on some boxes
@@ -1074,7 +1100,7 @@ static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, in
     p.out_f32 = c->bf16 ? 1 : 0;   // gemm_kernel<float> stores fp32 either way; the flag only selects a 16-bit kernel instance
     // guidance without the shared layer-0 half (per-op and small-forward paths): the second half's copy of the rows is written by
     // the same epilogue (16-bit modes: the fp32-output store) instead of a copy kernel behind the GEMM
-    const bool dup = N == 2 * B && !shared_half;
+    const bool dup = N >= 2 * B && !shared_half;
     const bool dup_in_epilogue = dup && c->bf16;
     if (dup_in_epilogue) p.dup_off = (int64_t)B * T * d;
     CHK(launch_gemm(c, p, s));
@@ -1083,6 +1109,11 @@ static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, in
       dup_rows_kernel<<<(int)((n4 + 255) / 256), 256, 0, s>>>(reinterpret_cast<const float4*>(c->x.p),
                                                              reinterpret_cast<float4*>(c->x.f() + (size_t)B * T * d), n4);
     }
+    if (N == 3 * B) {   // the third branch's copy of the rows
+      const int64_t n4 = (int64_t)B * T * d / 4;
+      dup_rows_kernel<<<(int)((n4 + 255) / 256), 256, 0, s>>>(reinterpret_cast<const float4*>(c->x.p),
+                                                             reinterpret_cast<float4*>(c->x.f() + (size_t)2 * B * T * d), n4);
+    }
   }
   CrossKV kv, kv2;
   bool fused_x3 = false;
@@ -1090,14 +1121,15 @@ static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, in
     kv.K = c->offT(c->kc, (int64_t)l * d); kv.k_slot_stride = (int64_t)c->Sld * L * d; kv.ldk = (int64_t)L * d;
     kv.VT = c->offT(c->vtc, (int64_t)l * d * c->Sld); kv.vt_slot_stride = (int64_t)L * d * c->Sld; kv.ldvt = c->Sld;
     kv.slots = slots; kv.S_main = c->pS0;
-    kv.slot_rule = pass == A2P_PASS_CFG ? 3 : (pass == A2P_PASS_COND ? 1 : 2); kv.slot_b = B;   // slot_tables_kernel's contents
+    kv.slot_rule = pass_audio_rule(pass); kv.slot_b = B;   // slot_tables_kernel's contents
     kv.ktail = c->ktail.f() + (size_t)l * d; kv.vtail = c->vtail.f() + (size_t)l * d;
     kv.tail_row_stride = (int64_t)L * d; kv.tail_sample_stride = (int64_t)2 * L * d; kv.S_tail = 2; kv.tail_mod = B;
     if (c->pose) {
       kv2.K = c->offT(c->k2c, (int64_t)l * d); kv2.k_slot_stride = (int64_t)64 * L * d; kv2.ldk = (int64_t)L * d;
       kv2.VT = c->offT(c->vt2c, (int64_t)l * d * 64); kv2.vt_slot_stride = (int64_t)L * d * 64; kv2.ldvt = 64;
-      kv2.slots = slots; kv2.S_main = c->pK; kv2.S_tail = 0; kv2.tail_mod = 1;
-      kv2.slot_rule = kv.slot_rule; kv2.slot_b = B;
+      kv2.slots = slots_kf; kv2.S_main = c->pK; kv2.S_tail = 0; kv2.tail_mod = 1;
+      // (keyframes kept in every branch but the last of three: no closed form among the kernels' rules, they read the table)
+      kv2.slot_rule = pass == A2P_PASS_KEYS ? 1 : (pass_split(pass) ? 0 : kv.slot_rule); kv2.slot_b = B;
     }
     FilmRef fr;
     fr.base = c->film.f() + (size_t)l * F * 2 * d;
@@ -1182,9 +1214,19 @@ static int run_forward(a2p_ctx* c, const float* x_in, const int64_t* t_orig, int
     return A2P_ERR_STATE;
   }
   ARG(x_in && t_orig, "null argument");
-  ARG(pass >= 0 && pass <= 2, "bad pass %d", pass);
+  ARG(pass >= 0 && pass <= A2P_PASS_CFG_DUAL, "bad pass %d", pass);
   const int B = c->pB, T = c->pT;
-  const int N = pass == A2P_PASS_CFG ? 2 * B : B;
+  const int N = pass_nseq(pass, B);
+  if (pass_split(pass)) {
+    ARG(c->pose, "pass %d drops audio and keyframes separately: the face model has no keyframes", pass);
+    ARG(N <= c->Nmax, "three guidance branches of batch %d are %d sequences, the context holds %d: construct the model with max_batch >= %d",
+        B, N, c->Nmax, (N + 1) / 2);
+    if (pass != A2P_PASS_KEYS && c->slot3_B != B) {   // (outside any capture: forward_body's launches only read the tables)
+      slot_tables3_kernel<<<1, 256, 0, s>>>((int*)c->slot_a3.p, (int*)c->slot_kf3.p, B, c->Nmax);
+      HIPCHK(hipGetLastError());
+      c->slot3_B = B;
+    }
+  }
   // Row panels pay off once there are enough of them: every workgroup streams the whole weight set of its chain, so a
   // forward of < ~1000 rows (config 0: B=1, T=240 -> 480 rows = 10 panels) is faster as many small 2-D tiles
   // (measured: 0.99 vs 1.10 ms per step at 480 rows, equal at 1200, chain ahead from 2400 rows on).
@@ -1237,17 +1279,41 @@ static int launch_step_tail(a2p_ctx* c, StepP& sp, hipStream_t s) {
   return 0;
 }
 
+// The pass a guided entry point evaluates (a2p_set_guidance), and the combine of the passes that guide audio and keyframes
+// separately (guide_combine_kernel: the guided output into both sequence blocks the step tails read).  A2P_PASS_CFG: nothing.
+static int guided_pass(const a2p_ctx* c) {
+  return c->guide_mode == A2P_GUIDE_DUAL ? A2P_PASS_CFG_DUAL : (c->guide_mode == A2P_GUIDE_AUDIO ? A2P_PASS_CFG_AUDIO : A2P_PASS_CFG);
+}
+static int guide_combine(a2p_ctx* c, int pass, const float* scale, int rows, hipStream_t s) {
+  if (pass != A2P_PASS_CFG_AUDIO && pass != A2P_PASS_CFG_DUAL) return 0;
+  ARG(pass != A2P_PASS_CFG_DUAL || c->scale_kf, "A2P_PASS_CFG_DUAL needs scale_keyframes (a2p_set_guidance)");
+  GuideP gp;
+  memset(&gp, 0, sizeof(gp));
+  gp.mo = c->mo.f(); gp.mo_seq_rows = rows; gp.B = c->pB; gp.C = c->C; gp.Tn = c->pT; gp.dual = pass == A2P_PASS_CFG_DUAL ? 1 : 0;
+  gp.scale = scale; gp.scale_kf = c->scale_kf;
+  const int64_t per = (int64_t)gp.Tn * gp.C / 4;   // (a2p_ctx_create: nfeats % 4 == 0)
+  dim3 grid((unsigned)((per + 255) / 256), (unsigned)gp.B);
+  KernelTimer kt(c, A2P_KERNEL_GUIDE_COMBINE);
+  A2P_LAUNCH(kt, guide_combine_kernel, grid, 256, s, gp);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" int a2p_denoise_forward(a2p_ctx* c, const float* x, const int64_t* t_orig, const float* scale, int32_t pass, float* out,
                                    void* stream) {
   ARG(c && out, "null argument");
   ARG(pass != A2P_PASS_CFG || scale, "A2P_PASS_CFG needs scale");
+  ARG((pass != A2P_PASS_CFG_AUDIO && pass != A2P_PASS_CFG_DUAL) || scale, "pass %d needs scale", pass);
   hipStream_t s = (hipStream_t)stream;
   int rows = 0;
   CHK(run_forward(c, x, t_orig, pass, &rows, s));
+  CHK(guide_combine(c, pass, scale, rows, s));
   StepP sp;
   memset(&sp, 0, sizeof(sp));
   sp.mo = c->mo.f(); sp.mo_seq_rows = rows; sp.mo_ld = c->C; sp.B = c->pB; sp.C = c->C; sp.Tn = c->pT;
-  sp.pass = pass; sp.scale = scale; sp.out_btc = out; sp.sampler = -1; sp.nonfinite = reinterpret_cast<int*>(c->nonfinite.p);
+  // (separately guided passes: the combine left the guided rows in the first two blocks, the tail reads them as A2P_PASS_CFG)
+  sp.pass = pass == A2P_PASS_KEYS ? A2P_PASS_COND : (pass_split(pass) ? A2P_PASS_CFG : pass);
+  sp.scale = scale; sp.out_btc = out; sp.sampler = -1; sp.nonfinite = reinterpret_cast<int*>(c->nonfinite.p);
   return launch_step_tail(c, sp, s);
 }
 
@@ -1274,13 +1340,15 @@ extern "C" int a2p_sample_step(a2p_ctx* c, int32_t sampler, const float* x, cons
   sp.n_steps = n_steps; sp.noise = noise; sp.eta = eta; sp.clip = clip_denoised; sp.x_next = x_next; sp.x0 = pred_xstart;
   sp.nonfinite = reinterpret_cast<int*>(c->nonfinite.p);
   // DDPM: the forward's last POST kernel takes the tail over where it can (decoder_layer_chain); every other sampler and every other forward leaves it to step_tail_kernel
-  c->step_tail = sampler == A2P_SAMPLER_DDPM ? &sp : nullptr;
+  const int pass = guided_pass(c);
+  c->step_tail = (sampler == A2P_SAMPLER_DDPM && pass == A2P_PASS_CFG) ? &sp : nullptr;
   c->step_tail_done = false;
   int rows = 0;
-  const int rc = run_forward(c, x, t_orig, A2P_PASS_CFG, &rows, s);
+  const int rc = run_forward(c, x, t_orig, pass, &rows, s);
   c->step_tail = nullptr;
   if (rc != 0) return rc;
   if (c->step_tail_done) return 0;
+  CHK(guide_combine(c, pass, scale, rows, s));
   sp.mo_seq_rows = rows;
   return launch_step_tail(c, sp, s);
 }
@@ -1298,7 +1366,8 @@ extern "C" int a2p_sample_step_inpaint(a2p_ctx* c, int32_t sampler, const float*
   int64_t* t_orig = reinterpret_cast<int64_t*>(c->tmpa.p);
   map_timesteps_kernel<<<1, 256, 0, s>>>(t_idx, timestep_map, t_orig, c->pB);
   int rows = 0;
-  CHK(run_forward(c, x, t_orig, A2P_PASS_CFG, &rows, s));
+  CHK(run_forward(c, x, t_orig, guided_pass(c), &rows, s));
+  CHK(guide_combine(c, guided_pass(c), scale, rows, s));
   InpaintStepP ip;
   memset(&ip, 0, sizeof(ip));
   ip.mo = c->mo.f(); ip.mo_seq_rows = rows; ip.B = c->pB; ip.C = c->C; ip.Tn = c->pT;
@@ -1340,7 +1409,8 @@ extern "C" int a2p_sample_step_windowed(a2p_ctx* c, int32_t sampler, const float
   int64_t* t_orig = reinterpret_cast<int64_t*>(c->tmpa.p);
   map_timesteps_kernel<<<1, 256, 0, s>>>(t_idx, timestep_map, t_orig, c->pB);
   int rows = 0;
-  CHK(run_forward(c, x_win, t_orig, A2P_PASS_CFG, &rows, s));
+  CHK(run_forward(c, x_win, t_orig, guided_pass(c), &rows, s));
+  CHK(guide_combine(c, guided_pass(c), scale, rows, s));
   WinStepP wp;
   memset(&wp, 0, sizeof(wp));
   wp.mo = c->mo.f(); wp.mo_seq_rows = rows; wp.R = c->pB / W; wp.W = W; wp.C = c->C; wp.Tw = c->pT; wp.Ttot = T_total;
@@ -1367,7 +1437,8 @@ extern "C" int a2p_sample_step_multistep(a2p_ctx* c, const float* x, const int64
   int64_t* t_orig = reinterpret_cast<int64_t*>(c->tmpa.p);
   map_timesteps_kernel<<<1, 256, 0, s>>>(t_idx, timestep_map, t_orig, c->pB);
   int rows = 0;
-  CHK(run_forward(c, x, t_orig, A2P_PASS_CFG, &rows, s));
+  CHK(run_forward(c, x, t_orig, guided_pass(c), &rows, s));
+  CHK(guide_combine(c, guided_pass(c), scale, rows, s));
   MsStepP mp;
   memset(&mp, 0, sizeof(mp));
   mp.mo = c->mo.f(); mp.mo_seq_rows = rows; mp.B = c->pB; mp.C = c->C; mp.Tn = c->pT;
@@ -1396,7 +1467,8 @@ extern "C" int a2p_sample_step_windowed_multistep(a2p_ctx* c, const float* x_win
   int64_t* t_orig = reinterpret_cast<int64_t*>(c->tmpa.p);
   map_timesteps_kernel<<<1, 256, 0, s>>>(t_idx, timestep_map, t_orig, c->pB);
   int rows = 0;
-  CHK(run_forward(c, x_win, t_orig, A2P_PASS_CFG, &rows, s));
+  CHK(run_forward(c, x_win, t_orig, guided_pass(c), &rows, s));
+  CHK(guide_combine(c, guided_pass(c), scale, rows, s));
   MsWinStepP wp;
   memset(&wp, 0, sizeof(wp));
   wp.mo = c->mo.f(); wp.mo_seq_rows = rows; wp.R = c->pB / W; wp.W = W; wp.C = c->C; wp.Tw = c->pT; wp.Ttot = T_total;

@@ -408,6 +408,45 @@ __global__ __launch_bounds__(256) void step_tail_kernel(StepP p) {
   }
 }
 
+// Guidance of audio and keyframes separately (body model; A2P_PASS_CFG_AUDIO / _CFG_DUAL): the forward left the branches' rows in
+// mo as sequence blocks [e(K,A) | e(K,0)] or [e(K,A) | e(K,0) | e(0,0)]; the guided output g is written over BOTH of the first two
+// blocks, so that every step tail (which reads sequences b and B+b and computes fmaf(scale, a - u, u)) sees a = u = g and returns
+// g's bits: scale * 0 + g.  A non-finite g still reaches the tails' flag (inf - inf and nan - nan are nan).  One thread owns the
+// same four columns of one row in all blocks: no element is read by one thread and written by another.  Every rounding spelled
+// out, as in cfg_combine: two differences, two fused multiply-adds.
+struct GuideP {
+  float* mo;              // [nseq][mo_seq_rows][C]; the first Tn rows of a sequence are its frames
+  int64_t mo_seq_rows;
+  int B, C, Tn, dual;
+  const float* scale;     // [B]  y["scale"]: audio
+  const float* scale_kf;  // [B]  y["scale_keyframes"]: keyframes (dual only)
+};
+#pragma clang fp contract(off)
+__device__ __forceinline__ float audio_combine(float ka, float k, float s) { return fmaf(s, ka - k, k); }
+__device__ __forceinline__ float dual_combine(float ka, float k, float n, float s, float sk) { return fmaf(s, ka - k, fmaf(sk, k - n, n)); }
+#pragma clang fp contract(fast)
+__global__ __launch_bounds__(256) void guide_combine_kernel(GuideP p) {
+  const int b = blockIdx.y;
+  const int64_t per = (int64_t)p.Tn * p.C / 4, i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // float4s of one sequence's frames (C % 4 == 0)
+  if (i >= per) return;
+  const int64_t seq4 = p.mo_seq_rows * p.C / 4;
+  float4* const m = reinterpret_cast<float4*>(p.mo);
+  const int64_t o_ka = (int64_t)b * seq4 + i, o_k = (int64_t)(p.B + b) * seq4 + i;
+  const float4 ka = m[o_ka], k = m[o_k];
+  const float s = p.scale[b];
+  float4 g;
+  if (p.dual) {
+    const float4 n = m[(int64_t)(2 * p.B + b) * seq4 + i];
+    const float sk = p.scale_kf[b];
+    g = float4{dual_combine(ka.x, k.x, n.x, s, sk), dual_combine(ka.y, k.y, n.y, s, sk), dual_combine(ka.z, k.z, n.z, s, sk),
+               dual_combine(ka.w, k.w, n.w, s, sk)};
+  } else {
+    g = float4{audio_combine(ka.x, k.x, s), audio_combine(ka.y, k.y, s), audio_combine(ka.z, k.z, s), audio_combine(ka.w, k.w, s)};
+  }
+  m[o_ka] = g;
+  m[o_k] = g;
+}
+
 // stand-alone elementwise forms (x, x0, noise all [B, per_sample])
 __global__ void ddim_update_kernel(const float* x0, const float* x, const int64_t* t_idx, const float* tab, int ns,
                                    const float* noise, float eta, int64_t per, int64_t total, float* out) {

@@ -254,6 +254,7 @@ class FiLMTransformer(nn.Module):
         self._ctx, self._ctx_key, self._weights_key, self._ctx_lib = ctx, key, None, lib
         self._env_sig = _lib.env_signature()      # the context read the A2P_* switches just now
         self._hint_sent = 0
+        self._guide_sent, self._guide_ref = _lib.GUIDE_JOINT, None     # a fresh context guides jointly
         self.invalidate_cond()
         return lib
 
@@ -372,12 +373,52 @@ class FiLMTransformer(nn.Module):
         self._cond_key = (_lib.content_key(src, kf, mask), T)
         self._cond_refs = (src, kf, mask)
 
+    # ------------------------------------------------------------------ guidance of audio and keyframes separately
+    def _guidance(self, y, B: int):
+        """`y["guidance"]` and `y["scale_keyframes"]` checked on the host, before anything touches the library:
+        (_lib.GUIDE_* id, scale_keyframes or None).  The mode is a Python string, never a tensor value: every shard of a batch
+        takes the same plan.  absent / "joint": one scale moves both conditions (the reference); "audio": keyframes always on,
+        y["scale"] guides the audio; "dual": y["scale_keyframes"] fp32 [B] guides the keyframes, y["scale"] the audio on top of
+        them -- three branches, 3B sequences (INTEGRATION.md "Guiding audio and keyframes separately")."""
+        mode = "joint" if y is None or y.get("guidance") is None else y["guidance"]
+        if not isinstance(mode, str) or mode not in _lib.GUIDANCE_MODES:
+            raise _lib.A2PError(f"y['guidance'] = {mode!r}: expected one of {sorted(_lib.GUIDANCE_MODES)}")
+        if mode == "joint":
+            return _lib.GUIDE_JOINT, None
+        if self.data_format != "pose":
+            raise _lib.A2PError(f"y['guidance'] = {mode!r} separates the audio from the keyframes: the {self.data_format} model has no "
+                                "keyframes (only 'joint')")
+        if mode == "audio":
+            return _lib.GUIDE_AUDIO, None
+        sk = y.get("scale_keyframes")
+        if sk is None:
+            raise _lib.A2PError("y['guidance'] = 'dual' needs y['scale_keyframes'] (fp32 [B]): the guidance scale of the keyframes")
+        if not torch.is_tensor(sk) or sk.dtype != torch.float32 or tuple(sk.shape) != (B,):
+            got = f"{sk.dtype} {tuple(sk.shape)}" if torch.is_tensor(sk) else type(sk).__name__
+            raise _lib.A2PError(f"y['scale_keyframes'] must be a float32 tensor of shape ({B},) like y['scale'] (got {got})")
+        cap = max(self.max_batch, B)              # what _ensure_ctx sizes the context for; it holds 2 * cap sequences
+        if 3 * B > 2 * cap:
+            raise _lib.A2PError(f"y['guidance'] = 'dual' runs 3 x {B} = {3 * B} sequences, max_batch={cap} holds {2 * cap}: construct the "
+                                f"model with max_batch >= {(3 * B + 1) // 2}")
+        return _lib.GUIDE_DUAL, sk
+
+    def _send_guidance(self, guide, device) -> None:
+        """Tell the context what its guided entry points evaluate (a2p_set_guidance).  Joint after joint: no call at all."""
+        mode, sk = guide
+        if mode == _lib.GUIDE_JOINT and self._guide_sent == _lib.GUIDE_JOINT:
+            return
+        skd = None if sk is None else sk.to(device=device, dtype=torch.float32).contiguous()
+        _lib.check(self._lib().a2p_set_guidance(self._ctx, mode, _lib.ptr(skd)), "a2p_set_guidance")
+        self._guide_sent, self._guide_ref = mode, skd       # the library reads scale_keyframes in every step: keep it alive
+
     # ------------------------------------------------------------------ forward
-    def _run(self, x, times, y, pass_id, scale=None) -> torch.Tensor:
+    def _run(self, x, times, y, pass_id, scale=None, guide=None) -> torch.Tensor:
         if x.dim() == 3:  # [B, T, C] accepted by the reference too (model/diffusion.py:345)
             x = x.permute(0, 2, 1).unsqueeze(2)
         x = x.to(torch.float32).contiguous()
         self.prepare(x, y)
+        if guide is not None:
+            self._send_guidance(guide, x.device)
         B, T = x.shape[0], x.shape[-1]
         out = torch.empty(B, T, self.nfeats, device=x.device, dtype=torch.float32)
         ts = times.to(device=x.device, dtype=torch.int64).contiguous()
@@ -387,16 +428,28 @@ class FiLMTransformer(nn.Module):
                                                        _lib.current_stream(x.device)), "a2p_denoise_forward")
         return out
 
-    def forward(self, x: torch.Tensor, times: torch.Tensor, y=None, cond_drop_prob: float = 0.0) -> torch.Tensor:
-        if cond_drop_prob == 0.0:
-            return self._run(x, times, y, _lib.PASS_COND)
-        if cond_drop_prob == 1.0:
-            return self._run(x, times, y, _lib.PASS_UNCOND)
-        raise NotImplementedError("stochastic conditioning dropout is a training feature (out of scope)")
+    def forward(self, x: torch.Tensor, times: torch.Tensor, y=None, cond_drop_prob: float = 0.0, *,
+                keyframe_drop_prob: Optional[float] = None) -> torch.Tensor:
+        """`cond_drop_prob` drops the audio (tokens and pooled hidden); `keyframe_drop_prob` drops the keyframe tokens of the body
+        model, None = the same value (the reference, whose two dropout masks share one probability)."""
+        kd = cond_drop_prob if keyframe_drop_prob is None else keyframe_drop_prob
+        if cond_drop_prob not in (0.0, 1.0) or kd not in (0.0, 1.0):
+            raise NotImplementedError("stochastic conditioning dropout is a training feature (out of scope)")
+        if kd != cond_drop_prob and self.data_format != "pose":
+            raise _lib.A2PError(f"keyframe_drop_prob={keyframe_drop_prob!r}: the {self.data_format} model has no keyframes")
+        if kd != cond_drop_prob and kd == 1.0:
+            raise NotImplementedError("audio kept with the keyframes dropped (cond_drop_prob=0, keyframe_drop_prob=1) has no pass in the "
+                                      "library: no guidance mode needs that branch")
+        if kd != cond_drop_prob:
+            return self._run(x, times, y, _lib.PASS_KEYS)
+        return self._run(x, times, y, _lib.PASS_COND if cond_drop_prob == 0.0 else _lib.PASS_UNCOND)
 
     def forward_cfg(self, x, times, y) -> torch.Tensor:
-        """Both guidance passes batched as 2B sequences + the lerp (model/cfg_sampler.py:30-33)."""
-        return self._run(x, times, y, _lib.PASS_CFG, y["scale"])
+        """The guidance branches batched as 2B (y["guidance"] absent, "joint", "audio") or 3B ("dual") sequences + their combination
+        (model/cfg_sampler.py:30-33; `_guidance`)."""
+        guide = self._guidance(y, x.shape[0])
+        pass_id = (_lib.PASS_CFG, _lib.PASS_CFG_AUDIO, _lib.PASS_CFG_DUAL)[guide[0]]
+        return self._run(x, times, y, pass_id, y["scale"], guide)
 
     def wants_early_check(self) -> bool:
         return self.precision != "fp32" and self.auto_escalate
@@ -455,8 +508,10 @@ class FiLMTransformer(nn.Module):
 
     def sample_step(self, sampler: int, x, t_idx, timestep_map, tables, y, noise, eta: float, clip_denoised: bool):
         """Fused p_mean_variance + ddim_sample / p_sample for one step (include/a2p_hip.h a2p_sample_step)."""
+        guide = self._guidance(y, x.shape[0])
         x = x.to(torch.float32).contiguous()
         self.prepare(x, y)
+        self._send_guidance(guide, x.device)
         x_next, x0 = torch.empty_like(x), torch.empty_like(x)
         sc = y["scale"].to(device=x.device, dtype=torch.float32).contiguous()
         nz = None if noise is None else noise.to(device=x.device, dtype=torch.float32).contiguous()
@@ -472,8 +527,10 @@ class FiLMTransformer(nn.Module):
         """One step of windowed joint sampling (include/a2p_hip.h a2p_sample_step_windowed): x [R*W, C, 1, T_w] windows,
         `starts` a ctypes int32 array of the W window starts, `weights` fp32 [W, T_w], `noise` global [R, C, 1, T_total] or None.
         Returns (x_next, pred_xstart) of the windows and (x_next, pred_xstart) global [R, C, 1, T_total]."""
+        guide = self._guidance(y, x.shape[0])
         x = x.to(torch.float32).contiguous()
         self.prepare(x, y)
+        self._send_guidance(guide, x.device)
         W = len(starts)
         B, Cf, T_w = x.shape[0], x.shape[1], x.shape[-1]
         R = B // W
@@ -499,6 +556,7 @@ class FiLMTransformer(nn.Module):
         """One step with held elements (include/a2p_hip.h a2p_sample_step_inpaint): a2p_sample_step whose x0 prediction takes
         `known` where `known_mask` is set.  `known` fp32 and `known_mask` uint8 are contiguous [B, C, 1, T] on x's device.
         Returns (x_next, pred_xstart)."""
+        guide = self._guidance(y, x.shape[0])
         x = x.to(torch.float32).contiguous()
         if (known.dtype != torch.float32 or known_mask.dtype != torch.uint8 or known.shape != x.shape or known_mask.shape != x.shape
                 or not known.is_contiguous() or not known_mask.is_contiguous() or known.device != x.device
@@ -507,6 +565,7 @@ class FiLMTransformer(nn.Module):
                                 f"{x.device} (got {known.dtype} {tuple(known.shape)} on {known.device}, {known_mask.dtype} "
                                 f"{tuple(known_mask.shape)} on {known_mask.device})")
         self.prepare(x, y)
+        self._send_guidance(guide, x.device)
         x_next, x0 = torch.empty_like(x), torch.empty_like(x)
         sc = y["scale"].to(device=x.device, dtype=torch.float32).contiguous()
         nz = None if noise is None else noise.to(device=x.device, dtype=torch.float32).contiguous()
@@ -523,6 +582,7 @@ class FiLMTransformer(nn.Module):
         x_next = CX x + B x0 + P x0_prev from `coefs` fp32 [A2P_NMS, n_steps] (GaussianDiffusion._multistep_coefs).  `x0_prev`: the
         previous step's pred_xstart [B, C, 1, T], or None (first order).  `known` fp32 / `known_mask` uint8 [B, C, 1, T]: held
         elements, as sample_step_inpaint takes them, or both None.  Returns (x_next, pred_xstart)."""
+        guide = self._guidance(y, x.shape[0])
         x = x.to(torch.float32).contiguous()
         if (known is None) != (known_mask is None):
             raise _lib.A2PError("multistep step: known and known_mask go together")
@@ -537,6 +597,7 @@ class FiLMTransformer(nn.Module):
             raise _lib.A2PError(f"multistep step: x0_prev {tuple(hist.shape)} does not match x {tuple(x.shape)}")
         cf = coefs.to(device=x.device, dtype=torch.float32).contiguous()
         self.prepare(x, y)
+        self._send_guidance(guide, x.device)
         x_next, x0 = torch.empty_like(x), torch.empty_like(x)
         sc = y["scale"].to(device=x.device, dtype=torch.float32).contiguous()
         with _lib.on_device_of(x):
@@ -551,6 +612,7 @@ class FiLMTransformer(nn.Module):
         """The windowed form of sample_step_multistep (include/a2p_hip.h a2p_sample_step_windowed_multistep): sample_step_windowed's
         windows and outputs, `x0_prev` the previous step's window pred_xstart [R*W, C, 1, T_w] or None.
         Returns (x_next, pred_xstart) of the windows and (x_next, pred_xstart) global [R, C, 1, T_total]."""
+        guide = self._guidance(y, x.shape[0])
         x = x.to(torch.float32).contiguous()
         W = len(starts)
         B, Cf, T_w = x.shape[0], x.shape[1], x.shape[-1]
@@ -564,6 +626,7 @@ class FiLMTransformer(nn.Module):
                                 f"{None if hist is None else tuple(hist.shape)})")
         cf = coefs.to(device=x.device, dtype=torch.float32).contiguous()
         self.prepare(x, y)
+        self._send_guidance(guide, x.device)
         x_next, x0 = torch.empty_like(x), torch.empty_like(x)
         xg = torch.empty(R, Cf, 1, int(T_total), device=x.device, dtype=torch.float32)
         x0g = torch.empty_like(xg)

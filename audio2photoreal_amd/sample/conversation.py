@@ -181,7 +181,8 @@ def _same_stats(a, b) -> bool:
 
 def generate_conversation(people, waveform, sr: int, num_repetitions: int = 1, top_p: float = 0.97, face_scale: float = 10.0,
                           pose_scale: float = 2.0, seed=10, normalize: str = "peak", sampler: str = "ddim", min_overlap: int = 120,
-                          overlap: bool = True, share_features: bool = True, chain_keyframes: bool = False) -> Dict[str, object]:
+                          overlap: bool = True, share_features: bool = True, chain_keyframes: bool = False,
+                          pose_guidance: str = "joint", pose_keyframe_scale: Optional[float] = None) -> Dict[str, object]:
     """Face and body motion of the people of a two-channel conversation recording (channel k: person k's microphone).
 
     `people`: a pair of (face, pose, stats) triples as `generate_from_recording` takes them; an entry may be None, a partner who is
@@ -199,6 +200,9 @@ def generate_conversation(people, waveform, sr: int, num_repetitions: int = 1, t
     (`person_seeds`); from s_p on they are the keyframe uniforms, face noise and body noise that generate_from_recording /
     generate_from_long_recording draw with seed=s_p.
 
+    `pose_guidance` / `pose_keyframe_scale`: how the body model is guided, as generate_from_recording takes them ("joint", "audio"
+    or "dual" with a keyframe scale; "dual" runs 1.5x the sequences and needs the pose model's max_batch >= ceil(1.5 x batch)).
+
     Returns {"people": [dict or None, dict or None], "T", "sr": 48000} (plus "window_starts" for long recordings); each person's
     dict has the keys and shapes of generate_from_recording's (or generate_from_long_recording's) result, un-normalised with that
     person's stats, its "audio" being (own, partner).  Bad input raises A2PError / ValueError before any GPU work."""
@@ -210,6 +214,8 @@ def generate_conversation(people, waveform, sr: int, num_repetitions: int = 1, t
             raise _lib.A2PError(f"people[{p}] must be a (face, pose, stats) triple or None")
     _check_sampler(sampler)
     _check_normalize(normalize)
+    from .generate import pose_guidance_plan
+    pose_scale = pose_guidance_plan(pose_scale, pose_guidance, pose_keyframe_scale)
     R = int(num_repetitions)
     if R < 1:
         raise _lib.A2PError(f"num_repetitions must be at least 1 (got {num_repetitions})")

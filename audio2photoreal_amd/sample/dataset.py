@@ -27,7 +27,7 @@ import torch
 from .. import _lib
 from .._lib import A2PError
 from ..data import capture as cap
-from .generate import _generate_sequences, _setup_model, fixseed, load_data_stats, save_results
+from .generate import _generate_sequences, _setup_model, fixseed, load_data_stats, pose_guidance_plan, save_results
 from .recording import MULTISTEP, SAMPLERS
 
 _MODEL_DEFAULTS = dict(heads=8, not_rotary=False, unconstrained=False, noise_schedule="cosine", sigma_small=True, lambda_vel=0.0,
@@ -44,6 +44,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num_repetitions", type=int, default=3, help="samples per chunk (default 3)")
     ap.add_argument("--timestep_respacing", default="ddim100", help="ddimN (default ddim100)")
     ap.add_argument("--guidance_param", type=float, default=2.5, help="classifier-free guidance scale (default 2.5)")
+    ap.add_argument("--pose_guidance", default="joint", help="pose checkpoints: joint (default: --guidance_param moves audio and keyframes "
+                                                             "together) | audio (keyframes as they are, guidance on the audio) | dual")
+    ap.add_argument("--pose_keyframe_scale", type=float, default=None, help="with --pose_guidance dual: the keyframes' guidance scale "
+                                                                            "(--guidance_param is then the audio's)")
     ap.add_argument("--resume_trans", default=None, help="guide transformer checkpoint (pose): sample the keyframes instead of "
                                                          "taking the ground truth's motion[::30]")
     ap.add_argument("--seed", type=int, default=10)
@@ -87,7 +91,8 @@ def _model_args(cli) -> argparse.Namespace:
                               timestep_respacing=cli.timestep_respacing, guidance_param=cli.guidance_param,
                               num_samples=cli.num_samples, batch_size=cli.num_samples, num_repetitions=cli.num_repetitions,
                               curr_seq_length=merged["max_seq_length"], seed=cli.seed, output_dir=out,
-                              resume_trans=cli.resume_trans if fmt == "pose" else None)
+                              resume_trans=cli.resume_trans if fmt == "pose" else None,
+                              pose_guidance=cli.pose_guidance, pose_keyframe_scale=cli.pose_keyframe_scale)
 
 
 def _check_cli(cli) -> None:
@@ -100,6 +105,7 @@ def _check_cli(cli) -> None:
         raise A2PError("--num_samples and --num_repetitions must be at least 1")
     if cli.num_samples > _lib.DATASET_MAX_BATCH:
         raise A2PError(f"--num_samples is at most {_lib.DATASET_MAX_BATCH}")
+    pose_guidance_plan(cli.guidance_param, cli.pose_guidance, cli.pose_keyframe_scale)
     if cli.json and not cli.evaluate:
         raise A2PError("--json goes with --evaluate")
 
@@ -163,6 +169,8 @@ def run(cli) -> Dict[str, object]:
     """The command on parsed arguments: {"results": path, "metrics": dict | None, "timing": seconds per phase, "chunks": n}."""
     _check_cli(cli)
     args = _model_args(cli)
+    if cli.pose_guidance != "joint" and args.data_format != "pose":
+        raise A2PError(f"--pose_guidance {cli.pose_guidance} separates the audio from the keyframes: a {args.data_format} checkpoint has no keyframes")
     stats_path = os.path.join(cli.data_root, "data_stats.pth")
     if not os.path.isfile(stats_path):
         raise A2PError(f"{stats_path} not found: the subject's data_stats.pth must lie in --data_root")
@@ -197,7 +205,8 @@ def run(cli) -> Dict[str, object]:
     geometry = FAIRSEQ if "audio_model.feature_extractor.conv_layers.0.2.weight" in state else STUB
     guide = _load_guide(args.resume_trans, device, cli.num_samples) if args.resume_trans is not None else None
     model, diffusion = _setup_model(args, state, guide=guide, audio_frontend="native", audio_geometry=geometry,
-                                    precision=cli.precision, max_batch=cli.num_samples)
+                                    precision=cli.precision,   # ("dual" runs three branches: 3B sequences in a context of 2 * max_batch)
+                                    max_batch=(3 * cli.num_samples + 1) // 2 if cli.pose_guidance == "dual" else cli.num_samples)
     torch.cuda.synchronize(device)
     timing["model_s"] = time.perf_counter() - t0
     t0 = time.perf_counter()

@@ -9,7 +9,7 @@ accelerated path; callers pass `model_kwargs` dir
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, Optional
+from typing import Callable, Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -20,6 +20,50 @@ from .. import _lib
 from ..sample_parallel import derive_seed, per_sample_noise, sample_parallel, shared_base_seed
 
 _CALLS = itertools.count()   # sampling calls of this process: every rank makes the same calls in the same order
+
+
+class PoseGuidance(NamedTuple):
+    """How the body model is guided when audio and keyframes are not moved by one scale (FiLMTransformer._guidance)."""
+    scale: float                      # y["scale"]: the audio's guidance scale
+    mode: str                         # y["guidance"]: "audio" | "dual"
+    keyframe_scale: Optional[float]   # y["scale_keyframes"] of "dual"
+
+
+def pose_guidance_plan(pose_scale: float, pose_guidance: str = "joint", pose_keyframe_scale: Optional[float] = None):
+    """The entry points' `pose_scale`, `pose_guidance`, `pose_keyframe_scale` checked on the host: `pose_scale` itself for "joint"
+    (the body's y is then what it always was), else a PoseGuidance.  A2PError names an unknown mode, "dual" without a keyframe
+    scale, a keyframe scale given to another mode, and a keyframe scale that is no finite number."""
+    if not isinstance(pose_guidance, str) or pose_guidance not in _lib.GUIDANCE_MODES:
+        raise _lib.A2PError(f"pose_guidance = {pose_guidance!r}: expected one of {sorted(_lib.GUIDANCE_MODES)}")
+    if pose_guidance != "dual":
+        if pose_keyframe_scale is not None:
+            raise _lib.A2PError(f"pose_keyframe_scale = {pose_keyframe_scale!r} goes with pose_guidance = 'dual' (got {pose_guidance!r})")
+        return pose_scale if pose_guidance == "joint" else PoseGuidance(float(pose_scale), pose_guidance, None)
+    if pose_keyframe_scale is None:
+        raise _lib.A2PError("pose_guidance = 'dual' needs pose_keyframe_scale: the guidance scale of the keyframes")
+    if isinstance(pose_keyframe_scale, bool) or not isinstance(pose_keyframe_scale, (int, float)) or not np.isfinite(pose_keyframe_scale):
+        raise _lib.A2PError(f"pose_keyframe_scale = {pose_keyframe_scale!r} is not a finite number")
+    return PoseGuidance(float(pose_scale), "dual", float(pose_keyframe_scale))
+
+
+def pose_scale_entries(pose_scale, B: int, device) -> Dict[str, object]:
+    """The guidance entries of the body model's y for B sequences: "scale" alone for a plain number, plus "guidance" (and
+    "scale_keyframes") for a PoseGuidance."""
+    if not isinstance(pose_scale, PoseGuidance):
+        return {"scale": torch.full((B,), float(pose_scale), device=device)}
+    out = {"scale": torch.full((B,), pose_scale.scale, device=device), "guidance": pose_scale.mode}
+    if pose_scale.keyframe_scale is not None:
+        out["scale_keyframes"] = torch.full((B,), pose_scale.keyframe_scale, device=device)
+    return out
+
+
+def check_pose_capacity(pose_scale, pose_denoiser, B: int) -> None:
+    """A2PError when "dual" guidance of B sequences (3B in the denoiser) does not fit the pose model's context (2 * max_batch)."""
+    if isinstance(pose_scale, PoseGuidance) and pose_scale.mode == "dual":
+        cap = max(int(pose_denoiser.max_batch), B)
+        if 3 * B > 2 * cap:
+            raise _lib.A2PError(f"pose_guidance = 'dual' runs 3 x {B} = {3 * B} sequences, the pose model's max_batch={cap} holds {2 * cap}: "
+                                f"construct it with max_batch >= {(3 * B + 1) // 2}")
 
 
 def fixseed(seed: int) -> None:
@@ -190,6 +234,10 @@ def _generate_sequences(args, model_kwargs, diffusion, model, inv_transform: Cal
     for rep_i in range(args.num_repetitions):
         if args.guidance_param != 1:
             model_kwargs["y"]["scale"] = torch.ones(args.batch_size, device=args.device) * args.guidance_param
+            # args.pose_guidance / args.pose_keyframe_scale (sample/dataset.py --pose_guidance, --pose_keyframe_scale): body model only
+            plan = pose_guidance_plan(args.guidance_param, getattr(args, "pose_guidance", "joint"), getattr(args, "pose_keyframe_scale", None))
+            if isinstance(plan, PoseGuidance):
+                model_kwargs["y"].update(pose_scale_entries(plan, args.batch_size, args.device))
         model_kwargs["y"] = {k: v.to(args.device) if torch.is_tensor(v) else v for k, v in model_kwargs["y"].items()}
         sample, curr_audio, keyframes, gt_seq = _run_single_diffusion(args, model_kwargs, diffusion, model, inv_transform, gt,
                                                                       rep_i=rep_i, call_i=call_i)

@@ -18,7 +18,7 @@ import torch
 from .. import _lib
 from ..diffusion.gaussian_diffusion import GaussianDiffusion
 from ..sample_parallel import derive_seed, per_sample_noise
-from .generate import _replace_keyframes
+from .generate import _replace_keyframes, check_pose_capacity, pose_guidance_plan, pose_scale_entries
 from .long_form import KEYFRAME_STEP, recording_frames
 from .recording import (MULTISTEP, SAMPLE_RATE, SAMPLES_PER_FRAME, _audio_stats, _check_sampler, _denoiser, _overlapped, can_share_features,
                         prepare_recording)
@@ -199,6 +199,7 @@ def _inpaint_window(face, pose, audio, R: int, Tw: int, known_face, known_pose, 
     pose_m, pose_d = pose
     fm, pm = _denoiser(face_m), _denoiser(pose_m)
     device = fm.null_cond_embed.device
+    check_pose_capacity(pose_scale, pm, R)
     nk = len(range(Tw)[::KEYFRAME_STEP])
     uni_id, pose_id, face_id = ids
     uniforms = torch.stack([torch.rand(nk * pm.tokenizer.residual_depth, generator=torch.Generator().manual_seed(derive_seed(seed, uni_id, r)))
@@ -209,7 +210,7 @@ def _inpaint_window(face, pose, audio, R: int, Tw: int, known_face, known_pose, 
         guide_cond, body_cond, face_cond = _conditions(face_m, pose_m, fm, pm, audio, share_features)
         y_face = {**face_cond, "scale": torch.full((R,), float(face_scale), device=device)}
         y_body = {**body_cond, "mask": torch.ones(R, 1, 1, Tw, dtype=torch.bool, device=device),
-                  "scale": torch.full((R,), float(pose_scale), device=device)}
+                  **pose_scale_entries(pose_scale, R, device)}   # (pose_scale: a number, or generate.PoseGuidance)
 
         def run_face():
             return inpaint_sample_loop(face_d, face_m, y_face, known_face, mask, noise_face, sampler=sampler)
@@ -238,7 +239,8 @@ def _motion(sample: torch.Tensor, mean, std) -> np.ndarray:
 def continue_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: int, previous: Dict[str, object], context_frames: int = 120,
                        num_repetitions: Optional[int] = None, top_p: float = 0.97, face_scale: float = 10.0, pose_scale: float = 2.0,
                        seed: int = 10, overlap: bool = True, share_features: bool = True,
-                       guide_context: bool = False, sampler: str = "ddim") -> Dict[str, object]:
+                       guide_context: bool = False, sampler: str = "ddim", pose_guidance: str = "joint",
+                       pose_keyframe_scale: Optional[float] = None) -> Dict[str, object]:
     """Continue a clip with new audio: face and body motion for `waveform` that starts from where `previous` ended.
 
     `previous`: a result of generate_from_recording or of an earlier continue_recording (its "face", "pose" and "audio" are read).
@@ -255,6 +257,9 @@ def continue_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: i
     repetition index, so the result does not depend on `overlap`; pass a new seed per chunk for fresh noise.  `sampler`: "ddim" or
     "dpm++2m" (inpaint_sample_loop), over the steps the diffusions were built with.
 
+    `pose_guidance` / `pose_keyframe_scale`: how the body model is guided, as generate_from_recording takes them ("joint", "audio"
+    or "dual" with a keyframe scale; "dual" runs 1.5x the sequences and needs the pose model's max_batch >= ceil(1.5 x batch)).
+
     Returns generate_from_recording's keys for the NEW frames only -- {"face": [R, T_new, 256], "pose": [R, T_new, 104],
     "keyframes": [R, T_new / 30, 104], "audio": float64 [2, T_new * 1600], "T": T_new, "sr": 48000} -- plus "context": P.
     Concatenating `previous` with it along frames gives the continued clip, and it is itself a valid `previous`.
@@ -263,6 +268,7 @@ def continue_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: i
     the models' seq_len, when num_repetitions differs from previous's, when `previous` is not finite, for an unknown sampler and
     for what prepare_recording refuses."""
     _check_sampler(sampler)
+    pose_scale = pose_guidance_plan(pose_scale, pose_guidance, pose_keyframe_scale)
     fm, pm = _check_models(face, pose, guide_context)
     prev_face, prev_pose, prev_audio = _result_arrays(previous, "previous")
     R, T_prev = prev_face.shape[:2]
@@ -326,7 +332,8 @@ def segment_window(T: int, start: int, end: int, seq_len: int):
 def regenerate_segment(face, pose, stats: Dict[str, np.ndarray], result: Dict[str, object], start_frame: int, end_frame: int,
                        parts: Sequence[str] = ("face", "pose"), top_p: float = 0.97, face_scale: float = 10.0, pose_scale: float = 2.0,
                        seed: int = 10, overlap: bool = True, share_features: bool = True,
-                       guide_context: bool = False, sampler: str = "ddim") -> Dict[str, object]:
+                       guide_context: bool = False, sampler: str = "ddim", pose_guidance: str = "joint",
+                       pose_keyframe_scale: Optional[float] = None) -> Dict[str, object]:
     """Re-roll frames [start_frame, end_frame) of a result and keep everything else.
 
     `result`: a dict with "face" [R, T, 256], "pose" [R, T, 104] and "audio" float64 [2, T * 1600] (generate_from_recording,
@@ -340,6 +347,9 @@ def regenerate_segment(face, pose, stats: Dict[str, np.ndarray], result: Dict[st
     body model is conditioned on all of them, the ones after the segment included.  Random draws are functions of `seed` and the repetition index.
     `sampler`: "ddim" or "dpm++2m" (inpaint_sample_loop), over the steps the diffusions were built with.
 
+    `pose_guidance` / `pose_keyframe_scale`: how the body model is guided, as generate_from_recording takes them ("joint", "audio"
+    or "dual" with a keyframe scale; "dual" runs 1.5x the sequences and needs the pose model's max_batch >= ceil(1.5 x batch)).
+
     Returns a copy of `result` in which only the listed parts' frames [start, end) are new: frames outside the segment and parts not
     listed are the input's arrays verbatim.  When the body is regenerated and result["keyframes"] is [R, T / 30, 104], its rows
     [start / 30, end / 30) are the new keyframes; other keyframe layouts are returned unchanged.
@@ -347,6 +357,7 @@ def regenerate_segment(face, pose, stats: Dict[str, np.ndarray], result: Dict[st
     Raises A2PError before any GPU work for bounds that are not multiples of 30 inside the clip with start < end, a segment longer
     than the window, unknown or no parts, an unknown sampler, and a result that is not finite."""
     _check_sampler(sampler)
+    pose_scale = pose_guidance_plan(pose_scale, pose_guidance, pose_keyframe_scale)
     fm, pm = _check_models(face, pose)
     res_face, res_pose, res_audio = _result_arrays(result, "result")
     R, T = res_face.shape[:2]

@@ -232,7 +232,8 @@ def _max_batch(*modules) -> int:
 def generate_from_long_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: int, num_repetitions: int = 1,
                                  top_p: float = 0.97, face_scale: float = 10.0, pose_scale: float = 2.0, seed: int = 10,
                                  min_overlap: int = 120, overlap: bool = True, share_features: bool = True,
-                                 chain_keyframes: bool = False, sampler: str = "ddim") -> Dict[str, object]:
+                                 chain_keyframes: bool = False, sampler: str = "ddim", pose_guidance: str = "joint",
+                                 pose_keyframe_scale: Optional[float] = None) -> Dict[str, object]:
     """`generate_from_recording` for a recording of any length, over the windows of `plan_windows(T_total, seq_len, min_overlap)`.
 
     Per window (batch R*W): the audio front end / lip features, and guide transformer -> VQ keyframes.  The keyframes of two
@@ -252,6 +253,9 @@ def generate_from_long_recording(face, pose, stats: Dict[str, np.ndarray], wavef
     there, those of window w > 0 from `derive_seed(seed, 1, r, w)`.  A recording that fits one window gives exactly
     `generate_from_recording`'s result.
 
+    `pose_guidance` / `pose_keyframe_scale`: how the body model is guided, as generate_from_recording takes them ("joint", "audio"
+    or "dual" with a keyframe scale; "dual" runs 1.5x the sequences and needs the pose model's max_batch >= ceil(1.5 x batch)).
+
     Returns {"face": [R, T_total, 256], "pose": [R, T_total, 104], "keyframes": [R, W, T_w / 30, 104] (un-normalised),
     "audio": float64 [2, Lc], "T": T_total, "sr": 48000, "window_starts": [W] ints}."""
     face_m, face_d = face
@@ -259,6 +263,8 @@ def generate_from_long_recording(face, pose, stats: Dict[str, np.ndarray], wavef
     fm, pm = _denoiser(face_m), _denoiser(pose_m)
     _check_sampler(sampler)
     _check_models(fm, pm)
+    from .generate import pose_guidance_plan
+    pose_scale = pose_guidance_plan(pose_scale, pose_guidance, pose_keyframe_scale)
     device = fm.null_cond_embed.device
     R = int(num_repetitions)
     max_batch = _max_batch(fm, pm, pm.transformer, fm.audio_frontend, pm.audio_frontend)

@@ -8,7 +8,7 @@ features computed once when the models' front ends are identical, and face / bod
 """
 from __future__ import annotations
 
-from typing import Dict, NamedTuple
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -16,7 +16,7 @@ import torch
 from .. import _lib
 from ..audio import _resample_rows, resampled_length, sinc_resample_table
 from ..sample_parallel import derive_seed, per_sample_noise
-from .generate import _replace_keyframes
+from .generate import _replace_keyframes, check_pose_capacity, pose_guidance_plan, pose_scale_entries
 
 SAMPLE_RATE = 48_000                  # the models' audio rate
 BLOCK = 4 * SAMPLE_RATE               # the demo keeps whole 4 s blocks (demo/demo.py:169-171)
@@ -132,7 +132,8 @@ def can_share_features(face_model, pose_model) -> bool:
 
 def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, sr: int, num_repetitions: int = 1, top_p: float = 0.97,
                             face_scale: float = 10.0, pose_scale: float = 2.0, seed: int = 10, overlap: bool = True,
-                            share_features: bool = True, known_keyframes=None, sampler: str = "ddim") -> Dict[str, object]:
+                            share_features: bool = True, known_keyframes=None, sampler: str = "ddim",
+                            pose_guidance: str = "joint", pose_keyframe_scale: Optional[float] = None) -> Dict[str, object]:
     """`generate_results` (demo/demo.py:156-216) for `num_repetitions` samples of one recording.
 
     `face` / `pose`: (ClassifierFreeSampleModel, SpacedDiffusion) pairs as `sample.generate._setup_model` builds them, the pose
@@ -156,6 +157,11 @@ def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, 
     step), for face and body alike.  The number of steps is the one each SpacedDiffusion was built with (e.g.
     timestep_respacing="ddim20"); anything else raises A2PError before any GPU work.
 
+    `pose_guidance` / `pose_keyframe_scale`: how the body model is guided (INTEGRATION.md "Guiding audio and keyframes separately").
+    "joint" (the default, the reference): `pose_scale` moves audio and keyframes together.  "audio": the keyframes are followed as
+    they are and `pose_scale` guides the audio alone.  "dual": `pose_keyframe_scale` guides the keyframes and `pose_scale` the audio
+    on top of them; three branches per step, 1.5x the sequences, and the pose model needs max_batch >= ceil(1.5 x its batch).
+
     Returns {"face": [R, T, 256], "pose": [R, T, 104], "keyframes": [R, T / 30, 104] (un-normalised with the code_* / pose_*
     statistics: * std + mean), "audio": the un-normalised dual audio float64 [2, Lc], "T", "sr": 48000}."""
     face_m, face_d = face
@@ -163,6 +169,7 @@ def generate_from_recording(face, pose, stats: Dict[str, np.ndarray], waveform, 
     fm, pm = _denoiser(face_m), _denoiser(pose_m)
     _check_sampler(sampler)
     _check_models(fm, pm)
+    pose_scale = pose_guidance_plan(pose_scale, pose_guidance, pose_keyframe_scale)
     known = None
     if known_keyframes is not None:
         from .inpaint import require_encoder
@@ -242,10 +249,11 @@ def _face_body_runs(face, pose, audio: torch.Tensor, T: int, nk: int, uniforms, 
     fm, pm = _denoiser(face_m), _denoiser(pose_m)
     device = fm.null_cond_embed.device
     B = audio.shape[0]
+    check_pose_capacity(pose_scale, pm, B)
     guide_cond, body_cond, face_cond = _conditions(face_m, pose_m, audio, share_features)
     y_face = {**face_cond, "scale": torch.full((B,), float(face_scale), device=device)}
     y_body = {**body_cond, "mask": torch.ones(B, 1, 1, T, dtype=torch.bool, device=device),
-              "scale": torch.full((B,), float(pose_scale), device=device)}
+              **pose_scale_entries(pose_scale, B, device)}   # (pose_scale: a number, or generate.PoseGuidance)
 
     if plan is None:
         def loop(d, m, noise, y):

@@ -17,7 +17,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
-_BATCH_KEYS = ("audio", "cond_embed", "keyframes", "mask", "scale", "lengths", "missing", "alengths", "klengths")
+_BATCH_KEYS = ("audio", "cond_embed", "keyframes", "mask", "scale", "scale_keyframes", "lengths", "missing", "alengths", "klengths")
+# (y["guidance"], the mode string of FiLMTransformer._guidance, is no tensor: every shard gets it as it is)
 
 
 def shard_bounds(total: int, world: int, rank: int) -> Tuple[int, int]:

@@ -49,6 +49,20 @@ extern "C" {
 #define A2P_PASS_COND 0
 #define A2P_PASS_UNCOND 1
 #define A2P_PASS_CFG 2
+/* Body model: audio and keyframes dropped separately.  Write e(K, A) for the output with the keyframe tokens kept (K) or replaced
+ * by null_pose_embed, and the audio tokens + pooled hidden kept (A) or replaced by null_cond_embed / null_cond_hidden; a trained
+ * checkpoint has seen all four (both conditions draw their own dropout mask, model/diffusion.py:325-328 and :366-369).
+ *   A2P_PASS_KEYS      B sequences:  e(K, 0)
+ *   A2P_PASS_CFG_AUDIO 2B sequences: e(K, 0) + scale * (e(K, A) - e(K, 0))
+ *   A2P_PASS_CFG_DUAL  3B sequences: e(0, 0) + scale_keyframes * (e(K, 0) - e(0, 0)) + scale * (e(K, A) - e(K, 0));
+ *                      scale_keyframes from a2p_set_guidance; needs 3 B <= 2 * max_batch. */
+#define A2P_PASS_KEYS 3
+#define A2P_PASS_CFG_AUDIO 4
+#define A2P_PASS_CFG_DUAL 5
+/* What the guided entry points (a2p_sample_step and its variants) evaluate: A2P_PASS_CFG, _CFG_AUDIO or _CFG_DUAL. */
+#define A2P_GUIDE_JOINT 0
+#define A2P_GUIDE_AUDIO 1
+#define A2P_GUIDE_DUAL 2
 
 #define A2P_SAMPLER_DDIM 0 /* GaussianDiffusion.ddim_sample (gaussian_diffusion.py:667-718) */
 #define A2P_SAMPLER_DDPM 1 /* GaussianDiffusion.p_sample    (gaussian_diffusion.py:434-477, noise restored) */
@@ -107,6 +121,15 @@ int a2p_prepare_cond(a2p_ctx* ctx, const float* cond_embed, int32_t batch, int32
  * scale fp32 [B] (y["scale"], A2P_PASS_CFG only) ; out [B, T, nfeats]. */
 int a2p_denoise_forward(a2p_ctx* ctx, const float* x, const int64_t* t_orig, const float* scale,
                         int32_t pass, float* out, void* stream);
+
+/* ---- guiding audio and keyframes separately (body model) ----------------------
+ * Selects what every following guided call evaluates (a2p_sample_step and its inpaint / windowed / multistep variants), until
+ * it is called again: mode A2P_GUIDE_JOINT (the default: A2P_PASS_CFG), A2P_GUIDE_AUDIO or A2P_GUIDE_DUAL.  scale_keyframes
+ * fp32 [B] on the device is read by every A2P_PASS_CFG_DUAL evaluation, a2p_denoise_forward's included, and stays owned by the
+ * caller; the other modes ignore it.  The face model takes A2P_GUIDE_JOINT only.  The three-way combine runs as one kernel
+ * behind the forward and leaves the guided output in both sequence blocks the step tails read, so their arithmetic is that of
+ * A2P_GUIDE_JOINT: scale * (g - g) + g. */
+int a2p_set_guidance(a2p_ctx* ctx, int32_t mode, const float* scale_keyframes);
 
 /* ---- fused sampler step: p_mean_variance + ddim_sample / p_sample -------------
  * tables: fp32 [A2P_NTAB, n_steps] rows in the order of a2p_table_id, built by the host
@@ -334,6 +357,7 @@ int a2p_attention(a2p_ctx* ctx, const float* q, const float* k, const float* v, 
 #define A2P_KERNEL_CHAIN_POST 7    /* out_proj -> FiLM -> norm3 -> FFN -> FiLM [-> next layer's PRE work | final_layer] */
 #define A2P_KERNEL_CHAIN_MIDPOST 8 /* body model: MID2 | keyframe attention | POST in one launch */
 #define A2P_KERNEL_POSE_TAIL 9     /* body model: final_layer + 6 dilated convs + final_conv (a sub-class of A2P_KERNEL_GEMM) */
+#define A2P_KERNEL_GUIDE_COMBINE 10 /* body model: the combine behind an A2P_PASS_CFG_AUDIO / _CFG_DUAL forward */
 int a2p_kernel_timing(a2p_ctx* ctx, int32_t kind, int32_t enable);
 int a2p_kernel_time_ms(a2p_ctx* ctx, double* total_ms, int64_t* launches);
 
