@@ -59,6 +59,7 @@ EXPORTS = (
     "a2p_jpeg_coefficients", "a2p_jpeg_entropy", "a2p_jpeg_restarts", "a2p_jpeg_decode_entropy", "a2p_jpeg_pixels",
     "a2p_vq_train_workspace_bytes", "a2p_vq_train_step",
     "a2p_set_guidance",
+    "a2p_render_antialiased_texture", "a2p_render_antialiased_values",
 )
 
 
@@ -168,6 +169,7 @@ DATASET_MAX_BATCH = 64                # A2P_DATASET_MAX_BATCH
 SKIN_MAX_JOINTS, SKIN_MAX_PARAMS, SKIN_MAX_INFLUENCES = 1024, 1024, 16   # A2P_SKIN_MAX_*
 SURFACE_MAX_UV, SURFACE_MAX_CHANNELS = 16384, 16                         # A2P_SURFACE_MAX_* (3 H H fits in int32)
 RENDER_MAX_SIZE, RENDER_MAX_CHANNELS = 8192, 16                          # A2P_RENDER_MAX_*
+RENDER_MAX_SUPERSAMPLE = 4                                               # A2P_RENDER_MAX_SUPERSAMPLE
 CONV_MAX_CHANNELS, CONV_MAX_SIZE = 4096, 16384                           # A2P_CONV_MAX_* (channels per group; plane side)
 CONV_BIAS_NONE, CONV_BIAS_TIED, CONV_BIAS_UNTIED = 0, 1, 2               # A2P_CONV_BIAS_*
 CONV_SKIP_NONE, CONV_SKIP_TENSOR, CONV_SKIP_CONV = 0, 1, 2               # A2P_CONV_SKIP_*
@@ -271,6 +273,10 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_render_rasterize": [vp, i64, i32, vp, i32, vp, i32, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp],
         "a2p_render_interpolate": [vp, i64, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp],
         "a2p_render_texture": [vp, vp, i64, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp],
+        "a2p_render_antialiased_texture": [vp, i64, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, f32, vp, i32, i32, i32, i32,
+                                           i32, vp, i32, vp, vp, vp, vp, vp],
+        "a2p_render_antialiased_values": [vp, i64, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, f32, vp, i32, vp, i32, vp, vp, vp, vp,
+                                          vp, vp],
         "a2p_conv2d_ub": [C.POINTER(A2PConv2dDesc), vp],
         "a2p_seam_impaint": [vp, i64, i32, i32, vp, vp, i32, vp, vp],
         "a2p_seam_resample": [vp, i64, i32, i32, vp, vp, vp, vp],

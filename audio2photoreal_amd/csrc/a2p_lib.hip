@@ -40,6 +40,7 @@
 #include "kernels_misc.h"
 #include "kernels_multistep.h"
 #include "kernels_render.h"
+#include "kernels_render_aa.h"
 #include "kernels_skin.h"
 #include "kernels_small.h"
 #include "kernels_surface.h"

@@ -83,3 +83,65 @@ extern "C" int a2p_render_texture(const int32_t* face, const float* bary, int64_
   HIPCHK(hipGetLastError());
   return 0;
 }
+
+// ---- anti-aliased images (kernels_render_aa.h): project, key fill, cover on the S H x S W grid and the fused resolve, in one call
+static int render_aa_run(const char* who, const float* verts, int64_t N, int32_t V, const int32_t* vi, int32_t F, const float* K,
+                         int32_t k_per_frame, const float* Rt, int32_t rt_per_frame, int32_t H, int32_t W, int32_t S, float near,
+                         bool tex, RenderAASource src, int32_t C, const float* bg, int32_t bg_per_frame, float* proj, uint64_t* key,
+                         float* out, float* alpha, float* depth, void* stream) {
+  ARG(verts && vi && K && Rt && src.data && src.tab && (!tex || src.vt) && proj && key && out && alpha, "%s: null argument", who);
+  ARG(V >= 1 && F >= 1 && (int64_t)F * 3 <= 0x7fffffff, "%s: V=%d, F=%d: need V >= 1, 1 <= 3 F < 2^31", who, V, F);
+  ARG(S >= 1 && S <= A2P_RENDER_MAX_SUPERSAMPLE, "%s: S=%d samples per axis: need 1 <= S <= %d", who, S, A2P_RENDER_MAX_SUPERSAMPLE);
+  ARG(H >= 1 && W >= 1 && (int64_t)S * H <= A2P_RENDER_MAX_SIZE && (int64_t)S * W <= A2P_RENDER_MAX_SIZE,
+      "%s: a %d x %d image at S=%d: need 1 <= H, W and S H, S W <= %d", who, H, W, S, A2P_RENDER_MAX_SIZE);
+  ARG(near > 0.0f && near < __builtin_inff(), "%s: near=%g: need a positive finite distance", who, (double)near);
+  int64_t pblocks;
+  CHK(render_pixel_grid(who, N, C, H, W, &pblocks));
+  const int64_t vtiles = render_tiles(V), fblocks = render_tiles(F), sH = (int64_t)S * H, sW = (int64_t)S * W;
+  ARG(N * vtiles <= 0x7fffffff && N * fblocks <= 0x7fffffff, "%s: N=%lld frames x %lld vertex tiles or %lld face blocks exceed the grid", who,
+      (long long)N, (long long)vtiles, (long long)fblocks);
+  const void* ins[] = {verts, vi, K, Rt, src.data, src.tab, src.vt, bg};
+  const void* outs[] = {proj, key, out, alpha, depth};
+  for (int a = 0; a < 5; ++a) {
+    for (int b = 0; b < 8; ++b) ARG(!outs[a] || outs[a] != ins[b], "%s: a scratch or output array must not alias an input", who);
+    for (int b = 0; b < a; ++b) ARG(!outs[a] || outs[a] != outs[b], "%s: the scratch and output arrays must be distinct", who);
+  }
+  if (N == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  render_project_scaled_kernel<<<(unsigned)(N * vtiles), RENDER_THREADS, 0, s>>>(verts, V, (int)vtiles, K, k_per_frame ? 9 : 0, Rt,
+                                                                                 rt_per_frame ? 12 : 0, (float)S, proj);
+  HIPCHK(hipMemsetAsync(key, 0xff, (size_t)(N * sH * sW) * sizeof(uint64_t), s));
+  render_cover_kernel<<<(unsigned)(N * fblocks), RENDER_THREADS, 0, s>>>(proj, V, vi, F, (int)fblocks, (int)sH, (int)sW, near,
+                                                                         (unsigned long long*)key);
+  const int64_t bg_stride = bg_per_frame ? (int64_t)C * H * W : 0;
+  if (tex)
+    render_aa_kernel<true><<<(unsigned)(N * pblocks), RENDER_THREADS, 0, s>>>(proj, V, vi, (const unsigned long long*)key, H, W, S,
+                                                                              (int)pblocks, src, C, bg, bg_stride, out, alpha, depth);
+  else
+    render_aa_kernel<false><<<(unsigned)(N * pblocks), RENDER_THREADS, 0, s>>>(proj, V, vi, (const unsigned long long*)key, H, W, S,
+                                                                               (int)pblocks, src, C, bg, bg_stride, out, alpha, depth);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int a2p_render_antialiased_texture(const float* verts, int64_t N, int32_t V, const int32_t* vi, int32_t F, const float* vt,
+                                              int32_t T, const int32_t* vti, const float* K, int32_t k_per_frame, const float* Rt,
+                                              int32_t rt_per_frame, int32_t H, int32_t W, int32_t S, float near, const float* tex,
+                                              int32_t tex_per_frame, int32_t C, int32_t Ht, int32_t Wt, int32_t flip_v, const float* bg,
+                                              int32_t bg_per_frame, float* proj, uint64_t* key, float* out, float* alpha, void* stream) {
+  const char* who = "render_antialiased_texture";
+  ARG(T >= 1, "%s: T=%d: need T >= 1", who, T);
+  ARG(Ht >= 1 && Wt >= 1 && (int64_t)Ht * Wt <= 0x7fffffff, "%s: a %d x %d texture: need 1 <= Ht Wt < 2^31", who, Ht, Wt);
+  const RenderAASource src = {tex, tex_per_frame ? (int64_t)C * Ht * Wt : 0, vt, vti, Ht, Wt, flip_v};
+  return render_aa_run(who, verts, N, V, vi, F, K, k_per_frame, Rt, rt_per_frame, H, W, S, near, true, src, C, bg, bg_per_frame, proj,
+                       key, out, alpha, nullptr, stream);
+}
+
+extern "C" int a2p_render_antialiased_values(const float* verts, int64_t N, int32_t V, const int32_t* vi, int32_t F, const float* K,
+                                             int32_t k_per_frame, const float* Rt, int32_t rt_per_frame, int32_t H, int32_t W, int32_t S,
+                                             float near, const float* values, int32_t C, const float* bg, int32_t bg_per_frame,
+                                             float* proj, uint64_t* key, float* out, float* alpha, float* depth, void* stream) {
+  const RenderAASource src = {values, (int64_t)V * C, nullptr, vi, 0, 0, 0};
+  return render_aa_run("render_antialiased_values", verts, N, V, vi, F, K, k_per_frame, Rt, rt_per_frame, H, W, S, near, false, src, C,
+                       bg, bg_per_frame, proj, key, out, alpha, depth, stream);
+}

@@ -18,24 +18,28 @@
 // Pass 0.  Grid tiles * N (tiles = ceil(V / RENDER_THREADS)): one thread per vertex and frame.  p = R x + t with Rt [., 3, 4];
 // u = fx (x / z) + skew (y / z) + cx, v = fy (y / z) + cy with K [., 3, 3] (K[0][0], K[0][1], K[0][2], K[1][1], K[1][2]); proj
 // [N, V, 3] keeps (u, v, z).  A vertex at z <= 0 gives values no later pass reads: its faces fail the near test first.
-__global__ __launch_bounds__(RENDER_THREADS) void render_project_kernel(
-    const float* __restrict__ verts, int V, int tiles, const float* __restrict__ K, int64_t k_stride,
-    const float* __restrict__ Rt, int64_t rt_stride, float* __restrict__ proj) {
+// One vertex through Rt (m, 12 floats) and the five entries of K that are read.
+__device__ __forceinline__ void render_project_vertex(const float* __restrict__ verts, const float* __restrict__ m, float k0, float k1,
+                                                      float k2, float k4, float k5, int64_t o, float* __restrict__ proj) {
 #pragma clang fp contract(off)      // sums left to right as written: which pixels a face covers hangs on these coordinates
-  const int64_t n = blockIdx.x / tiles;
-  const int v = (blockIdx.x % tiles) * RENDER_THREADS + threadIdx.x;
-  if (v >= V) return;
-  const float* k = K + n * k_stride;
-  const float* m = Rt + n * rt_stride;
-  const int64_t o = 3 * (n * V + v);
   const float x = verts[o], y = verts[o + 1], z = verts[o + 2];
   const float xc = m[0] * x + m[1] * y + m[2] * z + m[3];
   const float yc = m[4] * x + m[5] * y + m[6] * z + m[7];
   const float zc = m[8] * x + m[9] * y + m[10] * z + m[11];
   const float xn = xc / zc, yn = yc / zc;
-  proj[o] = k[0] * xn + k[1] * yn + k[2];
-  proj[o + 1] = k[4] * yn + k[5];
+  proj[o] = k0 * xn + k1 * yn + k2;
+  proj[o + 1] = k4 * yn + k5;
   proj[o + 2] = zc;
+}
+
+__global__ __launch_bounds__(RENDER_THREADS) void render_project_kernel(
+    const float* __restrict__ verts, int V, int tiles, const float* __restrict__ K, int64_t k_stride,
+    const float* __restrict__ Rt, int64_t rt_stride, float* __restrict__ proj) {
+  const int64_t n = blockIdx.x / tiles;
+  const int v = (blockIdx.x % tiles) * RENDER_THREADS + threadIdx.x;
+  if (v >= V) return;
+  const float* k = K + n * k_stride;
+  render_project_vertex(verts, Rt + n * rt_stride, k[0], k[1], k[2], k[4], k[5], 3 * (n * V + v), proj);
 }
 
 // One projected face: corners (u, v, z) and twice its signed screen area.

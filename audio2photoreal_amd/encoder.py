@@ -502,16 +502,21 @@ def encode_motion(face_decoder: FaceDecoder, face_encoder: FaceEncoder, body_enc
 
 
 def render_codes_motion(face_decoder: FaceDecoder, face_encoder: FaceEncoder, body_encoder: BodyEncoder, decoder, texture, skeleton,
-                        rasterizer, poses, face_codes, K, Rt, camera_pos=None, body_embs: str = "per_frame", max_bytes: int = 1 << 30):
+                        rasterizer, poses, face_codes, K, Rt, camera_pos=None, body_embs: str = "per_frame", max_bytes: int = 1 << 30,
+                        supersample: int = 1, background=None):
     """uint8 frames [B, T, H, C W, 3] (or [N, H, C W, 3] for flat frames) on the GPU of sampler output -- un-normalised body poses
     and face codes on the same leading axes -- seen by C cameras side by side: BodyRenderer._render_loop of visualize/
     render_codes.py, which uses 2.  K [C, 3, 3], Rt [C, 3, 4]; camera_pos [C, 3] defaults to render.camera_centre(Rt).  Per chunk
     of frames the embeddings are encoded (encode_motion with geom=None) and the body decoded and posed once; the texture, the
     rasterisation and texture.linear_to_display run per camera; the images are concatenated along the width, clipped to [0, 255]
     and truncated to uint8.  A chunk's activations stay under max_bytes, at least one frame; a frame's result does not depend on
-    the chunking."""
+    the chunking.  supersample and background as in texture.render_rgb_motion: s x s samples per pixel, and one display-space
+    colour or [H, W, 3] / [3, H, W] panel in [0, 255] behind the avatar, the same for every camera; a pixel no sample covers holds
+    the background's bytes exactly."""
     from .render import camera_centre
-    from .texture import linear_to_display
+    from .texture import display_background, display_frames
+    supersample = rasterizer._supersample(supersample)
+    background = display_background(background, rasterizer.height, rasterizer.width)
     if body_embs not in ("per_frame", "rest"):
         raise A2PError(f"body_embs={body_embs!r}: need 'per_frame' or 'rest'")
     if skeleton.P_pos != 6 + decoder.n_pose_dims:
@@ -532,6 +537,7 @@ def render_codes_motion(face_decoder: FaceDecoder, face_encoder: FaceEncoder, bo
     per_frame = activation_bytes_per_frame(face_decoder, face_encoder, body_encoder, skeleton)
     chunk = max(1, int(max_bytes) // (per_frame + decoder.activation_bytes_per_frame() + texture.activation_bytes_per_frame()))
     H, W = rasterizer.height, rasterizer.width
+    background = tuple(None if x is None else x.to(dev) for x in background)
     out = torch.empty(N, H, C * W, 3, dtype=torch.uint8, device=dev)
     rest = _rest_embs(body_encoder, skeleton, dev) if body_embs == "rest" and N else None
     for a in range(0, N, chunk):
@@ -541,8 +547,8 @@ def render_codes_motion(face_decoder: FaceDecoder, face_encoder: FaceEncoder, bo
         verts = skeleton.pose_vertices(frames[a:b], verts_unposed=preds["geom_delta_rec"])
         for c in range(C):
             tex = texture.forward(verts, preds["tex_mean_rec"], camera_pos[c:c + 1], motion=frames[a:b] if texture.pose_shadow is not None else None)
-            image = rasterizer.render(verts, tex["tex_rec"], K[c:c + 1], Rt[c:c + 1])["render"]
-            out[a:b, :, c * W:(c + 1) * W] = linear_to_display(image).permute(0, 2, 3, 1).clip(0, 255).to(torch.uint8)
+            image = display_frames(rasterizer, verts, tex["tex_rec"], K[c:c + 1], Rt[c:c + 1], supersample, background)
+            out[a:b, :, c * W:(c + 1) * W] = image.permute(0, 2, 3, 1).clip(0, 255).to(torch.uint8)
     return out.reshape(*lead, H, C * W, 3)
 
 
@@ -578,6 +584,9 @@ def main(argv=None) -> int:
     ap.add_argument("--fps", type=float, default=30.0, help="with --video: frames per second")
     ap.add_argument("--body-embs", choices=("per_frame", "rest"), default="per_frame", help="rest: encode the template once (not the reference's loop)")
     ap.add_argument("--max-bytes", type=int, default=1 << 30, help="activation budget of one chunk of frames")
+    ap.add_argument("--supersample", type=int, default=1, metavar="S", choices=range(1, 5), help="anti-aliasing: S x S samples per pixel")
+    ap.add_argument("--background", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
+                    help="display colour in [0, 255] behind the avatar, in every panel (default: black)")
     ap.add_argument("--uv-size", type=int, default=1024)
     ap.add_argument("--encoder-uv-size", type=int, default=512)
     ap.add_argument("--n-init-ftrs", type=int, default=8)
@@ -635,7 +644,8 @@ def main(argv=None) -> int:
         rest = skeleton.pose_vertices(poses.reshape(-1, poses.shape[-1])[:1]).cpu().numpy()  # frames the default camera
         K, Rt = R._camera_from_args(args, rest, H, W)
     on_gpu = render_codes_motion(face_decoder, face_encoder, body_encoder, decoder, texture, skeleton, R.BodyRasterizer(surface, H, W), poses,
-                                 face, K, Rt, camera_pos, body_embs=args.body_embs, max_bytes=args.max_bytes)
+                                 face, K, Rt, camera_pos, body_embs=args.body_embs, max_bytes=args.max_bytes, supersample=args.supersample,
+                                 background=args.background)
     frames = on_gpu.cpu().numpy()
     np.save(args.out, frames)
     print(f"{args.out}: frames {list(frames.shape)} uint8")

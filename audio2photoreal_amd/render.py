@@ -1,10 +1,11 @@
 """Rendered images of the posed body mesh on the MI355X: z-buffer rasterisation, perspective-correct attribute images and UV
 texture sampling -- the third stage of the reference's renderer (visualize/ca_body/utils/render.py: RenderLayer, which gets them
-from pytorch3d's MeshRasterizer and TexturesUV.sample_textures), as HIP launches for all frames (csrc/kernels_render.h).
+from pytorch3d's MeshRasterizer and TexturesUV.sample_textures), as HIP launches for all frames (csrc/kernels_render.h), and
+anti-aliased images over a background, which the reference does not have (csrc/kernels_render_aa.h).
 
     python -m audio2photoreal_amd.render --geometry geometry.npy --assets static_assets.pt --out frames.npy [--size H W]
                                          [--camera-json FILE | --eye x y z --target x y z --fov deg] [--outputs depth normals ...]
-                                         [--frames A:B] [--png-dir DIR]
+                                         [--frames A:B] [--png-dir DIR] [--supersample S]
 
 `BodyRasterizer` is built once from a `BodySurface` (whose validated topology tables it shares), from arrays (`from_arrays`) or
 from the topology the reference reads (`from_static_assets`).  Cameras are OpenCV pinholes: K [N or 1, 3, 3], Rt [N or 1, 3, 4],
@@ -213,6 +214,103 @@ class BodyRasterizer:
             raise A2PError("render: background and output_filters must be None (the reference asserts the same)")
         return {"render": self.sample_texture(self.rasterize(verts, K, Rt), tex)}
 
+    # -------------------------------------------------------------------------------------------- anti-aliased images
+    def _supersample(self, supersample) -> int:
+        s = int(supersample)
+        if s != supersample or not 1 <= s <= _lib.RENDER_MAX_SUPERSAMPLE:
+            raise ValueError(f"supersample={supersample} is outside [1, {_lib.RENDER_MAX_SUPERSAMPLE}] samples per axis")
+        for name, size in (("height", self.height), ("width", self.width)):
+            if s * size > _lib.RENDER_MAX_SIZE:
+                raise ValueError(f"supersample={s} x {name}={size} exceeds {_lib.RENDER_MAX_SIZE} samples per axis")
+        return s
+
+    def _background(self, background, C, verts):
+        """A background as (contiguous [n, C, H, W] tensor or None, per-frame flag): None, a colour [C] or [N or 1, C, H, W] on the
+        device of verts.  Checked before anything is asked of the GPU."""
+        if background is None or C is None:                                   # C is None: tex is malformed and is refused next
+            return None, 0
+        H, W = self.height, self.width
+        N = verts.shape[0] if torch.is_tensor(verts) and verts.dim() else 1
+        if not torch.is_tensor(background):
+            raise A2PError(f"background must be None or a tensor on the MI355X (got {type(background).__name__})")
+        shape = tuple(background.shape)
+        if background.dtype != torch.float32 or not (shape == (C,) or (len(shape) == 4 and shape[1:] == (C, H, W) and shape[0] in (1, N))):
+            raise A2PError(f"background must be float32 [{C}] or [{N} or 1, {C}, {H}, {W}] (got {background.dtype} {list(shape)})")
+        if torch.is_tensor(verts) and background.device != verts.device:
+            raise A2PError(f"background is on {background.device}, verts on {verts.device}")
+        bg = background.reshape(1, C, 1, 1).expand(1, C, H, W) if background.dim() == 1 else background
+        return bg.contiguous(), int(bg.shape[0] == N and N != 1)
+
+    def _antialiased(self, verts, K, Rt, s: int, max_bytes, C: int, background, source, want_depth: bool):
+        """The chunk loop both anti-aliased methods share; source(tables, a, b) -> (export name, its arguments before the cameras,
+        its arguments after `near`) for frames a..b-1.  background: what _background returned."""
+        if int(max_bytes) < 1:
+            raise A2PError(f"max_bytes={max_bytes}: need a positive byte budget")
+        N, dev, H, W = verts.shape[0], verts.device, self.height, self.width
+        K, k_per = self._camera(K, "K", 3, N, dev)
+        Rt, rt_per = self._camera(Rt, "Rt", 4, N, dev)
+        bg, bg_per = background
+        new = lambda c: torch.empty(N, c, H, W, dtype=torch.float32, device=dev)
+        out, alpha, depth = new(C), new(1), new(1) if want_depth else None
+        if N == 0:
+            return out, alpha, depth
+        t = self._tables(dev)
+        step = min(N, max(1, int(max_bytes) // (12 * self.V + 8 * s * s * H * W)))          # proj and key of one frame
+        proj = torch.empty(step, self.V, 3, dtype=torch.float32, device=dev)
+        key = torch.empty(step, s * H, s * W, dtype=torch.int64, device=dev)
+        lib = _lib.load()
+        with _lib.on_device_of(verts):
+            for a in range(0, N, step):
+                b = min(N, a + step)
+                part = lambda x, per: x[a:b] if per else x
+                name, before, after = source(t, a, b)
+                _lib.check(getattr(lib, name)(
+                    _lib.ptr(verts[a:b]), b - a, self.V, _lib.ptr(t["vi"]), self.F, *before, _lib.ptr(part(K, k_per)), k_per,
+                    _lib.ptr(part(Rt, rt_per)), rt_per, H, W, s, self.near, *after, _lib.ptr(None if bg is None else part(bg, bg_per)),
+                    bg_per, _lib.ptr(proj), _lib.ptr(key), _lib.ptr(out[a:b]), _lib.ptr(alpha[a:b]),
+                    *(() if name.endswith("texture") else (_lib.ptr(None if depth is None else depth[a:b]),)),
+                    _lib.current_stream(dev)), name)
+        return out, alpha, depth
+
+    def render_antialiased(self, verts, tex, K, Rt, supersample: int = 2, background=None, max_bytes: int = 1 << 30) -> dict:
+        """{"render": [N, C, H, W], "alpha": [N, 1, H, W]}: the texture seen through the camera with supersample x supersample
+        samples per pixel (1 to 4 per axis; INTEGRATION.md "Rendered images" states where they are).  alpha is the covered fraction
+        of the pixel's samples, and render is premultiplied by it: the mean over all samples, an uncovered one counting 0.
+        background (None, a colour [C] or [N or 1, C, H, W], in the texture's own linear units) is composited under it: a fully
+        covered pixel does not read it, an uncovered one holds its value itself, the others render + (1 - alpha) background.
+        Frames are processed in chunks whose scratch stays below max_bytes; a frame's bits do not depend on the chunking."""
+        s = self._supersample(supersample)
+        background = self._background(background, tex.shape[1] if torch.is_tensor(tex) and tex.dim() == 4 else None, verts)
+        verts = self._tensor(verts, "verts", f"[N, {self.V}, 3]", lambda s: len(s) == 3 and s[1:] == (self.V, 3))
+        N, dev = verts.shape[0], verts.device
+        C_max = _lib.RENDER_MAX_CHANNELS
+        tex = self._tensor(tex, "tex", f"[{N} or 1, C, Ht, Wt] with 1 <= C <= {C_max}",
+                           lambda s: len(s) == 4 and s[0] in (1, N) and 1 <= s[1] <= C_max and min(s[2:]) >= 1)
+        if tex.device != dev:
+            raise A2PError(f"tex is on {tex.device}, verts on {dev}")
+        C, Ht, Wt = tex.shape[1:]
+        tex_per = int(tex.shape[0] == N and N != 1)
+        source = lambda t, a, b: ("a2p_render_antialiased_texture", (_lib.ptr(t["vt"]), self.T, _lib.ptr(t["vti"])),
+                                  (_lib.ptr(tex[a:b] if tex_per else tex), tex_per, C, Ht, Wt, int(self.flip_uv)))
+        out, alpha, _ = self._antialiased(verts, K, Rt, s, max_bytes, C, background, source, False)
+        return {"render": out, "alpha": alpha}
+
+    def interpolate_antialiased(self, verts, values, K, Rt, supersample: int = 2, max_bytes: int = 1 << 30) -> dict:
+        """{"values": [N, C, H, W], "alpha": [N, 1, H, W], "depth": [N, 1, H, W]}: values [N, V, C] (1 <= C <= 16) interpolated at
+        every sample and averaged like render_antialiased (premultiplied by alpha); depth is the same mean of the samples' depths."""
+        s = self._supersample(supersample)
+        verts = self._tensor(verts, "verts", f"[N, {self.V}, 3]", lambda s: len(s) == 3 and s[1:] == (self.V, 3))
+        N, dev = verts.shape[0], verts.device
+        C_max = _lib.RENDER_MAX_CHANNELS
+        values = self._tensor(values, "values", f"[{N}, {self.V}, C] with 1 <= C <= {C_max}",
+                              lambda s: len(s) == 3 and s[0] == N and s[1] == self.V and 1 <= s[2] <= C_max)
+        if values.device != dev:
+            raise A2PError(f"values are on {values.device}, verts on {dev}")
+        C = values.shape[2]
+        source = lambda t, a, b: ("a2p_render_antialiased_values", (), (_lib.ptr(values[a:b]), C))
+        out, alpha, depth = self._antialiased(verts, K, Rt, s, max_bytes, C, (None, 0), source, True)
+        return {"values": out, "alpha": alpha, "depth": depth}
+
     def mask(self, fragments: dict):
         """float32 [N, 1, H, W]: 1 where a face is visible, 0 on background."""
         face, _ = self._fragments(fragments)
@@ -227,14 +325,20 @@ def camera_centre(Rt):
 
 
 def render_motion(rasterizer: BodyRasterizer, surface: BodySurface, vertices, K, Rt, outputs=("depth", "normals", "view_cos"),
-                  camera_pos=None, max_bytes: int = 1 << 30) -> dict:
+                  camera_pos=None, max_bytes: int = 1 << 30, supersample: int = 1) -> dict:
     """Images of posed vertices in the layouts skinning.pose_motion returns, [B, T, V, 3] or [N, V, 3] (float32 on the GPU):
     {name: [B, T, C, H, W] or [N, C, H, W]} for each name in `outputs` -- "depth" (1 channel), "normals" (3, the interpolated
     vertex normals), "view_cos" (1), "positions" (3, world coordinates) and "mask" (1).  K / Rt are [N or 1, 3, .] with N = B T;
     camera_pos ([N or 1, 3], for the view cosine) defaults to the camera centre -R^T t.
 
     The frames are processed in chunks whose scratch and intermediate arrays stay below max_bytes (at least one frame per chunk);
-    the returned images themselves take N C H W 4 bytes per output.  A frame's result does not depend on the chunking."""
+    the returned images themselves take N C H W 4 bytes per output.  A frame's result does not depend on the chunking.
+
+    supersample = s > 1 (at most 4) anti-aliases: every output is the mean over the pixel's s x s samples of the single-sample
+    image (BodyRasterizer.interpolate_antialiased), an uncovered sample counting 0.  "mask" is then the coverage, the covered
+    fraction of the pixel's samples, and every other output is premultiplied by it: divide by "mask" where it is not 0 for the
+    mean over the covered samples alone.  (Averaged normals are no longer unit vectors.)"""
+    s = rasterizer._supersample(supersample)
     if not torch.is_tensor(vertices):
         raise A2PError(f"vertices must be a tensor on the MI355X (got {type(vertices).__name__})")
     V, H, W = rasterizer.V, rasterizer.height, rasterizer.width
@@ -259,13 +363,16 @@ def render_motion(rasterizer: BodyRasterizer, surface: BodySurface, vertices, K,
         camera_pos = camera_centre(Rt) if camera_pos is None else camera_pos
         camera_pos = BodyRasterizer._tensor(camera_pos, "camera_pos", f"[{N} or 1, 3]", lambda s: len(s) == 2 and s[1] == 3 and s[0] in (1, N))
     channels = (3 if want_normals else 0) + (1 if want_cos else 0) + (3 if "positions" in outputs else 0)
-    per_frame = 4 * (3 * V + 7 * H * W + 4 * V + channels * (V + H * W))     # proj, key + face + bary + depth, normals + cos, values + image
+    if s == 1:
+        per_frame = 4 * (3 * V + 7 * H * W + 4 * V + channels * (V + H * W))     # proj, key + face + bary + depth, normals + cos, values + image
+    else:                                                                     # proj, the s x s keys, alpha + depth, normals + cos, values + image
+        per_frame = 4 * (3 * V + 2 * s * s * H * W + 2 * H * W + 4 * V + max(channels, 3) * (V + H * W))
     step = max(1, int(max_bytes) // per_frame)
     out = {o: torch.empty(N, OUTPUTS[o], H, W, dtype=torch.float32, device=dev) for o in outputs}
     for a in range(0, N, step):
         b = min(N, a + step)
         part = lambda x, per: x[a:b] if per else x
-        frag = rasterizer.rasterize(verts[a:b], part(K, k_per), part(Rt, rt_per))
+        frag = rasterizer.rasterize(verts[a:b], part(K, k_per), part(Rt, rt_per)) if s == 1 else None
         values = {"positions": verts[a:b]}
         if want_cos:
             values["normals"], cos = surface.normals_and_view_cos(verts[a:b], part(camera_pos, camera_pos.shape[0] == N and N != 1))
@@ -273,8 +380,14 @@ def render_motion(rasterizer: BodyRasterizer, surface: BodySurface, vertices, K,
         elif want_normals:
             values["normals"] = surface.normals(verts[a:b])
         names = [o for o in ("normals", "view_cos", "positions") if o in outputs]
-        if names:                                                             # one interpolate launch over the concatenated channels
+        if s > 1:                                                             # one fused launch: the positions stand in when only depth / mask are wanted
+            aa = rasterizer.interpolate_antialiased(verts[a:b], torch.cat([values[o] for o in names or ["positions"]], dim=2),
+                                                    part(K, k_per), part(Rt, rt_per), s, max_bytes)
+            image = aa["values"]
+            frag = {"depth": aa["depth"][:, 0]}
+        elif names:                                                           # one interpolate launch over the concatenated channels
             image = rasterizer.interpolate(frag, torch.cat([values[o] for o in names], dim=2))
+        if names:
             c = 0
             for o in names:
                 out[o][a:b] = image[:, c:c + OUTPUTS[o]]
@@ -282,7 +395,7 @@ def render_motion(rasterizer: BodyRasterizer, surface: BodySurface, vertices, K,
         if "depth" in outputs:
             out["depth"][a:b] = frag["depth"][:, None]
         if "mask" in outputs:
-            out["mask"][a:b] = rasterizer.mask(frag)
+            out["mask"][a:b] = rasterizer.mask(frag) if s == 1 else aa["alpha"]
     return {o: x.reshape(*lead, OUTPUTS[o], H, W) for o, x in out.items()}
 
 
@@ -305,6 +418,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--frames", default=None, metavar="A:B", help="frames A..B-1 of the time axis only")
     ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write <output>_<sequence>_<frame>.png per frame")
     ap.add_argument("--max-bytes", type=int, default=1 << 30, help="byte budget of one chunk of frames")
+    ap.add_argument("--supersample", type=int, default=1, metavar="S", choices=range(1, _lib.RENDER_MAX_SUPERSAMPLE + 1),
+                    help="anti-aliasing: S x S samples per pixel; the mask is then the coverage and the other images are premultiplied by it")
     return ap
 
 
@@ -376,7 +491,7 @@ def main(argv=None) -> int:
     rasterizer = BodyRasterizer(surface, H, W)
     K, Rt = _camera_from_args(args, verts, H, W)
     out = render_motion(rasterizer, surface, torch.from_numpy(np.ascontiguousarray(verts)).to("cuda"), K.to("cuda"), Rt.to("cuda"),
-                        outputs=args.outputs, max_bytes=args.max_bytes)
+                        outputs=args.outputs, max_bytes=args.max_bytes, supersample=args.supersample)
     images = {k: v.cpu().numpy() for k, v in out.items()}
     np.save(args.out, images)
     print(f"{args.out}: " + ", ".join(f"{k} {list(v.shape)}" for k, v in images.items()))

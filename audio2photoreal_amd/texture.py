@@ -476,17 +476,73 @@ def linear_to_display(rgb):
     return torch.clamp(torch.where(v <= 0.0031308, v * 12.92, curve), 0, 1) * 255.0
 
 
+def display_to_linear(rgb):
+    """The inverse of linear_to_display on display values in [0, 255], [.., 3, H, W]: the inverse of the sRGB-type curve with gamma
+    1.5 (its linear piece below 12.92 x 0.0031308), plus black, divided by the white balance, times 255.  linear_to_display of
+    the result gives rgb back to float32 rounding.  Torch ops, not a hot path: a background is converted once."""
+    if not torch.is_tensor(rgb) or rgb.dim() < 3 or rgb.shape[-3] != 3:
+        raise A2PError("rgb must be a tensor [.., 3, H, W]")
+    wb = torch.tensor(WB_SCALE, dtype=torch.float32, device=rgb.device)[:, None, None]
+    y = rgb.float() / 255.0
+    curve = torch.pow((torch.clamp(y, min=0.0) + 0.055) / 1.055, DISPLAY_GAMMA)
+    v = torch.where(y <= 12.92 * 0.0031308, y / 12.92, curve)
+    return (v + DISPLAY_BLACK) / wb * 255.0
+
+
+def display_background(background, height: int, width: int, device=None):
+    """A display-space background -- three numbers, [3, H, W] or [H, W, 3], in [0, 255] -- as (display [3, 1, 1] or [3, H, W],
+    linear [3] or [1, 3, H, W]) float32 tensors on `device`: the second is display_to_linear of the first, what
+    BodyRasterizer.render_antialiased composites under the linear image.  None gives (None, None)."""
+    if background is None:
+        return None, None
+    try:
+        x = torch.as_tensor(np.asarray(background.detach().cpu() if torch.is_tensor(background) else background, np.float32))
+    except (TypeError, ValueError):
+        raise ValueError(f"background must be three numbers or an image in [0, 255] (got {type(background).__name__})") from None
+    H, W = int(height), int(width)
+    if tuple(x.shape) == (3,):
+        x = x.reshape(3, 1, 1)
+    elif tuple(x.shape) == (H, W, 3) and tuple(x.shape) != (3, H, W):
+        x = x.permute(2, 0, 1)
+    elif tuple(x.shape) != (3, H, W):
+        raise ValueError(f"background must be three numbers, [3, {H}, {W}] or [{H}, {W}, 3] (got {list(x.shape)})")
+    if not bool(((x >= 0) & (x <= 255)).all()):
+        raise ValueError("background must hold display values in [0, 255]")
+    x = x.contiguous().to(device or "cpu")
+    linear = display_to_linear(x)
+    return x, (linear.reshape(3) if x.shape[1:] == (1, 1) else linear[None].contiguous())
+
+
+def display_frames(rasterizer, verts, tex, K, Rt, supersample: int = 1, background=(None, None)):
+    """Display RGB [N, 3, H, W] of one camera: rasterizer.render and linear_to_display; with supersample > 1 or a background (the
+    pair display_background returns) render_antialiased, composited in linear light, then linear_to_display, and finally every
+    pixel no sample covers is set to the given display value itself."""
+    shown, linear = background
+    if supersample == 1 and shown is None:
+        return linear_to_display(rasterizer.render(verts, tex, K, Rt)["render"])
+    got = rasterizer.render_antialiased(verts, tex, K, Rt, supersample, linear)
+    image = linear_to_display(got["render"])
+    return image if shown is None else torch.where(got["alpha"] == 0, shown, image)
+
+
 def render_rgb_motion(decoder, texture: BodyTexture, skeleton, rasterizer, poses, embs, face_embs, K, Rt, camera_pos=None,
-                      max_bytes: int = 1 << 30):
+                      max_bytes: int = 1 << 30, supersample: int = 1, background=None):
     """Display RGB frames [B, T, 3, H, W] (or [N, 3, H, W] for flat frames; float32 in [0, 255] on the GPU) of un-normalised body
     motion in the layouts decoder.decode_motion takes, with embs and face_embs on the same leading axes: per chunk of frames
     BodyDecoder.forward, skeleton.pose_vertices, BodyTexture.forward (motion = the chunk's poses when the texture has PoseToShadow
     weights), rasterizer.render and linear_to_display.  K / Rt are [N or 1, 3, .]; camera_pos [N or 1, 3] defaults to
     render.camera_centre(Rt).  Only the images are kept (a 2048 x 2048 texture is 50 MB a frame); a chunk's activations
     (activation_bytes_per_frame of decoder and texture) stay under max_bytes, at least one frame; a frame's result does not depend
-    on the chunking."""
+    on the chunking.
+
+    supersample = s > 1 anti-aliases with s x s samples per pixel (rasterizer.render_antialiased).  background: a display-space
+    colour (three numbers) or image ([H, W, 3] or [3, H, W]) in [0, 255]; it is converted once by display_to_linear, composited
+    under the avatar in linear light, where coverage is a fraction of light, and passed through linear_to_display with it; a
+    pixel no sample covers holds the given value itself.  With the defaults the calls are those made without the two keywords."""
     from .render import camera_centre
     from .skinning import motion_frames
+    supersample = rasterizer._supersample(supersample)
+    background = display_background(background, rasterizer.height, rasterizer.width)
     if skeleton.P_pos != 6 + decoder.n_pose_dims:
         raise A2PError(f"the skeleton takes {skeleton.P_pos} pose parameters; the decoder 6 + n_pose_dims = {6 + decoder.n_pose_dims}")
     frames, lead = motion_frames(poses, skeleton.P_pos)
@@ -513,6 +569,7 @@ def render_rgb_motion(decoder, texture: BodyTexture, skeleton, rasterizer, poses
     cam_per = camera_pos.shape[0] == N and N != 1
     chunk = max(1, int(max_bytes) // (decoder.activation_bytes_per_frame() + texture.activation_bytes_per_frame()))
     H, W = rasterizer.height, rasterizer.width
+    background = tuple(None if x is None else x.to(dev) for x in background)
     out = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
     for a in range(0, N, chunk):
         b = min(N, a + chunk)
@@ -521,8 +578,7 @@ def render_rgb_motion(decoder, texture: BodyTexture, skeleton, rasterizer, poses
         verts = skeleton.pose_vertices(frames[a:b], verts_unposed=preds["geom_delta_rec"])
         tex = texture.forward(verts, preds["tex_mean_rec"], part(camera_pos, cam_per),
                               motion=frames[a:b] if texture.pose_shadow is not None else None)
-        image = rasterizer.render(verts, tex["tex_rec"], part(K, k_per), part(Rt, rt_per))["render"]
-        out[a:b] = linear_to_display(image)
+        out[a:b] = display_frames(rasterizer, verts, tex["tex_rec"], part(K, k_per), part(Rt, rt_per), supersample, background)
     return out.reshape(*lead, 3, H, W)
 
 
@@ -542,6 +598,10 @@ def main(argv=None) -> int:
     ap.add_argument("--frames", default=None, metavar="A:B", help="frames A..B-1 of the time axis only")
     ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write rgb_<sequence>_<frame>.png per frame")
     ap.add_argument("--max-bytes", type=int, default=1 << 30, help="activation budget of one chunk of frames")
+    ap.add_argument("--supersample", type=int, default=1, metavar="S", choices=range(1, _lib.RENDER_MAX_SUPERSAMPLE + 1),
+                    help="anti-aliasing: S x S samples per pixel")
+    ap.add_argument("--background", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
+                    help="display colour in [0, 255] behind the avatar (default: black, the linear image's 0)")
     ap.add_argument("--results", required=True, help="results.npy of sample.generate (key `motions` [B, P, 1, T], un-normalised)")
     ap.add_argument("--embeddings", required=True, help=".npz with `embs` [B, T, n_embs] and `face_embs` [B, T, n_face_embs]")
     ap.add_argument("--checkpoint", required=True, help="the body model's state dict (decoder.*, decoder_view.*, upscale_net.*, ...)")
@@ -589,7 +649,7 @@ def main(argv=None) -> int:
     rest = skeleton.pose_vertices(poses.reshape(-1, poses.shape[-1])[:1]).cpu().numpy()  # frames the default camera
     K, Rt = R._camera_from_args(args, rest, H, W)
     rgb = render_rgb_motion(decoder, texture, skeleton, R.BodyRasterizer(surface, H, W), poses, embs, face_embs, K.to("cuda"),
-                            Rt.to("cuda"), max_bytes=args.max_bytes).cpu().numpy()
+                            Rt.to("cuda"), max_bytes=args.max_bytes, supersample=args.supersample, background=args.background).cpu().numpy()
     np.save(args.out, rgb)
     print(f"{args.out}: rgb {list(rgb.shape)}")
     if args.png_dir is not None:

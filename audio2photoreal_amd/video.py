@@ -968,11 +968,13 @@ def read_video_frames(path, start: int = 0, count=None, slice_frames: int = 64, 
 
 # ------------------------------------------------------------------------------------------------ rendering into a file
 def render_codes_video(face_decoder, face_encoder, body_encoder, decoder, texture, skeleton, rasterizer, poses, face_codes, K, Rt, path,
-                       audio=None, audio_rate=None, fps=30, quality: int = 90, subsampling: str = "420", slice_frames: int = 32, **kw) -> int:
+                       audio=None, audio_rate=None, fps=30, quality: int = 90, subsampling: str = "420", slice_frames: int = 32,
+                       supersample: int = 1, background=None, **kw) -> int:
     """encoder.render_codes_motion over slices of slice_frames frames of the time axis, every slice encoded and appended to the AVI
     file `path` before the next is rendered: BodyRenderer.render_full_video.  poses [T, P] (or [1, T, P]) and face_codes with the
     same leading axes: one sequence per file; **kw goes to render_codes_motion (camera_pos, body_embs, max_bytes).  A frame's bytes
-    do not depend on the slicing.  Returns the number of frames."""
+    do not depend on the slicing.  supersample and background (anti-aliasing; a display-space colour or panel behind the avatar)
+    are render_codes_motion's.  Returns the number of frames."""
     from .encoder import render_codes_motion
     poses, face_codes = torch.as_tensor(poses), torch.as_tensor(face_codes)
     if poses.dim() == 3 and poses.shape[0] == 1 and face_codes.dim() == 3 and face_codes.shape[0] == 1:
@@ -985,7 +987,7 @@ def render_codes_video(face_decoder, face_encoder, body_encoder, decoder, textur
     with MJPEGWriter(path, rasterizer.height, C * rasterizer.width, fps, quality, subsampling, audio, audio_rate) as w:
         for a in range(0, poses.shape[0], step):
             w.write(render_codes_motion(face_decoder, face_encoder, body_encoder, decoder, texture, skeleton, rasterizer, poses[a:a + step],
-                                        face_codes[a:a + step], K, Rt, **kw))
+                                        face_codes[a:a + step], K, Rt, supersample=supersample, background=background, **kw))
     return int(poses.shape[0])
 
 

@@ -707,6 +707,27 @@ int a2p_render_texture(const int32_t* face, const float* bary, int64_t N, int32_
                        const int32_t* vti, int32_t F, const float* tex, int32_t tex_per_frame, int32_t C, int32_t Ht, int32_t Wt,
                        int32_t flip_v, float* out, void* stream);
 
+/* Anti-aliased images: S x S samples per pixel (1 <= S <= 4, S H and S W <= A2P_RENDER_MAX_SIZE).  Sample (a, b) of pixel (i, j) is
+ * pixel (S i + a, S j + b) of the S H x S W image seen through K' = K with its first two rows times S in float32 (in the image's
+ * own units its centre is (j + (b + 0.5) / S, i + (a + 0.5) / S)); its face is what a2p_render_rasterize gives at (S H, S W, K'),
+ * its value what a2p_render_texture / a2p_render_interpolate give at its barycentrics.  Each call runs projection, key fill, cover
+ * pass and one fused resolve: the samples of a pixel are summed a outer, b inner into fp32 accumulators from 0, n counts the
+ * covered ones; alpha [N, 1, H, W] = (float)n / (float)(S S), mean = acc / (float)(S S) (premultiplied: an uncovered sample adds 0).
+ * bg ([N, C, H, W] when bg_per_frame, else [1, C, H, W]; NULL: none): n == S S gives mean and bg is not read, n == 0 gives bg
+ * itself, otherwise mean + (1 - alpha) bg; without bg, mean.  Every element of out [N, C, H, W] and alpha (and of depth [N, 1, H, W],
+ * optional: the mean of the samples' depths, premultiplied like out) is written.  proj [N, V, 3] floats and key [N, S H, S W] 64-bit
+ * words are scratch; no face index comes from the caller.  No float atomics: a frame's bits depend on neither N nor its index. */
+#define A2P_RENDER_MAX_SUPERSAMPLE 4
+int a2p_render_antialiased_texture(const float* verts, int64_t N, int32_t V, const int32_t* vi, int32_t F, const float* vt, int32_t T,
+                                   const int32_t* vti, const float* K, int32_t k_per_frame, const float* Rt, int32_t rt_per_frame,
+                                   int32_t H, int32_t W, int32_t S, float near, const float* tex, int32_t tex_per_frame, int32_t C,
+                                   int32_t Ht, int32_t Wt, int32_t flip_v, const float* bg, int32_t bg_per_frame, float* proj,
+                                   uint64_t* key, float* out, float* alpha, void* stream);
+int a2p_render_antialiased_values(const float* verts, int64_t N, int32_t V, const int32_t* vi, int32_t F, const float* K,
+                                  int32_t k_per_frame, const float* Rt, int32_t rt_per_frame, int32_t H, int32_t W, int32_t S, float near,
+                                  const float* values, int32_t C, const float* bg, int32_t bg_per_frame, float* proj, uint64_t* key,
+                                  float* out, float* alpha, float* depth, void* stream);
+
 /* ---- decoder layers (reference visualize/ca_body/nn/layers.py, nn/blocks.py, utils/seams.py; audio2photoreal_amd/decoder.py) --
  * The layer family of the body renderer's networks, fp32 like the reference, on the caller's stream.  Context-free: weights
  * (already folded, w = v g / ||v||), biases, masks and seam tables are device arrays the caller prepared once.  No atomics and a
