@@ -60,6 +60,7 @@ EXPORTS = (
     "a2p_vq_train_workspace_bytes", "a2p_vq_train_step",
     "a2p_set_guidance",
     "a2p_render_antialiased_texture", "a2p_render_antialiased_values",
+    "a2p_scene_render",
 )
 
 
@@ -137,6 +138,12 @@ class A2PDown3Desc(C.Structure):
                 + [("N", C.c_int64), ("C_out", C.c_int32), ("slope", C.c_float)])
 
 
+class A2PSceneBody(C.Structure):
+    """a2p_scene_body (include/a2p_hip.h "scenes of several bodies"): one body of an a2p_scene_render call."""
+    _fields_ = ([(n, C.c_void_p) for n in ("verts", "placement", "tex", "vt", "vti")]
+                + [(n, C.c_int32) for n in ("V", "F", "T", "Ht", "Wt", "flip_v", "placement_per_frame", "tex_per_frame")])
+
+
 EPI_STORE, EPI_STORE_T, EPI_FILM_RES, EPI_CONV = 0, 1, 2, 3                          # csrc/kernels_gemm.h
 ACT_NONE, ACT_GELU, ACT_MISH, ACT_SILU, ACT_LRELU, ACT_RELU = 0, 1, 2, 3, 4, 5       # csrc/a2p_common.h
 
@@ -170,6 +177,7 @@ SKIN_MAX_JOINTS, SKIN_MAX_PARAMS, SKIN_MAX_INFLUENCES = 1024, 1024, 16   # A2P_S
 SURFACE_MAX_UV, SURFACE_MAX_CHANNELS = 16384, 16                         # A2P_SURFACE_MAX_* (3 H H fits in int32)
 RENDER_MAX_SIZE, RENDER_MAX_CHANNELS = 8192, 16                          # A2P_RENDER_MAX_*
 RENDER_MAX_SUPERSAMPLE = 4                                               # A2P_RENDER_MAX_SUPERSAMPLE
+SCENE_MAX_BODIES = 4                                                     # A2P_SCENE_MAX_BODIES
 CONV_MAX_CHANNELS, CONV_MAX_SIZE = 4096, 16384                           # A2P_CONV_MAX_* (channels per group; plane side)
 CONV_BIAS_NONE, CONV_BIAS_TIED, CONV_BIAS_UNTIED = 0, 1, 2               # A2P_CONV_BIAS_*
 CONV_SKIP_NONE, CONV_SKIP_TENSOR, CONV_SKIP_CONV = 0, 1, 2               # A2P_CONV_SKIP_*
@@ -277,6 +285,8 @@ def load(half: bool = False) -> C.CDLL:
                                            i32, vp, i32, vp, vp, vp, vp, vp],
         "a2p_render_antialiased_values": [vp, i64, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, f32, vp, i32, vp, i32, vp, vp, vp, vp,
                                           vp, vp],
+        "a2p_scene_render": [C.POINTER(A2PSceneBody), i32, vp, i64, vp, i32, vp, i32, i32, i32, i32, f32, i32, vp, i32, vp, vp, vp, vp, vp,
+                             vp, vp],
         "a2p_conv2d_ub": [C.POINTER(A2PConv2dDesc), vp],
         "a2p_seam_impaint": [vp, i64, i32, i32, vp, vp, i32, vp, vp],
         "a2p_seam_resample": [vp, i64, i32, i32, vp, vp, vp, vp],

@@ -41,6 +41,7 @@
 #include "kernels_multistep.h"
 #include "kernels_render.h"
 #include "kernels_render_aa.h"
+#include "kernels_scene.h"
 #include "kernels_skin.h"
 #include "kernels_small.h"
 #include "kernels_surface.h"
@@ -1052,6 +1053,7 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_skin.h"
 #include "a2p_surface.h"
 #include "a2p_render.h"
+#include "a2p_scene.h"
 #include "a2p_conv.h"
 #include "a2p_texture.h"
 #include "a2p_encode.h"

@@ -728,6 +728,40 @@ int a2p_render_antialiased_values(const float* verts, int64_t N, int32_t V, cons
                                   const float* values, int32_t C, const float* bg, int32_t bg_per_frame, float* proj, uint64_t* key,
                                   float* out, float* alpha, float* depth, void* stream);
 
+/* Scenes of several bodies (audio2photoreal_amd/scene.py): P meshes, 1 <= P <= A2P_SCENE_MAX_BODIES, in one image with one shared
+ * z-buffer per sample.  Body p: verts [N, V, 3]; vt [T, 2] and vti [F, 3] (its own face numbering, entries in [0, T)); tex [N, C, Ht,
+ * Wt] when tex_per_frame, else [1, C, Ht, Wt] (C is the call's, the sizes are the body's); flip_v; placement NULL, or [N, 3, 4] when
+ * placement_per_frame, else [1, 3, 4]: x_world = R x + t with M = [R | t].  faces [sum F, 3] is the merged face table the caller
+ * built once: body p's vi with the sum of the earlier bodies' V added, bodies in order (entries in [0, sum V)).
+ *
+ * One launch projects every body into proj [N, sum V, 3] through K' = K with its first two rows times S in float32, as the
+ * anti-aliased images above.  A body without a placement is projected exactly as a2p_render_rasterize projects it.  A placed vertex is
+ * first moved, per coordinate r, by w_r = ((M[r][0] x + M[r][1] y) + M[r][2] z) + M[r][3] in float32, every product and sum rounded
+ * (no fused multiply-add), and w is projected in its place.  Key fill and cover pass then run on the merged mesh at (S H, S W): the
+ * key is depth bits << 32 | global face index, so at exactly equal depth the earlier body wins, then the lower face.  One fused resolve
+ * walks a pixel's samples a outer, b inner, finds each sample's body from its global face index and shades it from that body's vt,
+ * vti, tex and flip_v by a2p_render_texture's expression, into fp32 accumulators from 0; n counts the covered samples, n_p those body
+ * p wins.  alpha [N, 1, H, W] = (float)n / (float)(S S); out [N, C, H, W] = acc / (float)(S S) (premultiplied), over bg ([N, C, H, W]
+ * when bg_per_frame, else [1, C, H, W]; NULL: none) by the rule above: n == S S does not read bg, n == 0 gives bg itself, otherwise
+ * mean + (1 - alpha) bg; depth [N, 1, H, W] = the sum of the covered samples' camera-space depths / (float)(S S); body_alpha [N, P, H,
+ * W] = (float)n_p / (float)(S S).  Every element of the four outputs is written; all four are required.  proj [N, sum V, 3] floats and
+ * key [N, S H, S W] 64-bit words are scratch.  Limits: 3 sum V and 3 sum F < 2^31; the image and channel limits above; a face with a
+ * corner at z < near is dropped whole (one near plane for all bodies).  No float atomics: a frame's bits depend on neither N nor its
+ * index.  No scratch or output array may alias an input or another. */
+#define A2P_SCENE_MAX_BODIES 4
+typedef struct a2p_scene_body {
+  const float* verts;
+  const float* placement;
+  const float* tex;
+  const float* vt;
+  const int32_t* vti;
+  int32_t V, F, T, Ht, Wt, flip_v, placement_per_frame, tex_per_frame;
+} a2p_scene_body;
+int a2p_scene_render(const a2p_scene_body* bodies, int32_t P, const int32_t* faces, int64_t N, const float* K, int32_t k_per_frame,
+                     const float* Rt, int32_t rt_per_frame, int32_t H, int32_t W, int32_t S, float near, int32_t C, const float* bg,
+                     int32_t bg_per_frame, float* proj, uint64_t* key, float* out, float* alpha, float* depth, float* body_alpha,
+                     void* stream);
+
 /* ---- decoder layers (reference visualize/ca_body/nn/layers.py, nn/blocks.py, utils/seams.py; audio2photoreal_amd/decoder.py) --
  * The layer family of the body renderer's networks, fp32 like the reference, on the caller's stream.  Context-free: weights
  * (already folded, w = v g / ||v||), biases, masks and seam tables are device arrays the caller prepared once.  No atomics and a
