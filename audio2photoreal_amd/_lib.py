@@ -49,7 +49,7 @@ EXPORTS = (
     "a2p_sample_step_multistep", "a2p_sample_step_windowed_multistep", "a2p_multistep_update",
     "a2p_eval_moments", "a2p_eval_pair_dist", "a2p_eval_gemm_f64", "a2p_eval_eigh",
     "a2p_resample_channels", "a2p_conversation_audio", "a2p_dataset_batch",
-    "a2p_gemm_ex", "a2p_skinny_gemm_ex",
+    "a2p_gemm_ex", "a2p_skinny_gemm_ex", "a2p_attention_ex",
     "a2p_skin_states", "a2p_skin_vertices",
     "a2p_surface_normals", "a2p_surface_to_uv", "a2p_surface_from_uv", "a2p_surface_uv_index",
     "a2p_render_rasterize", "a2p_render_interpolate", "a2p_render_texture",
@@ -104,6 +104,17 @@ class A2PSkinnyCase(C.Structure):
     """a2p_skinny_case (include/a2p_hip.h), test-only."""
     _fields_ = ([(n, C.c_void_p) for n in ("A", "W", "bias", "out")] + [(n, C.c_int64) for n in ("lda", "ldw", "ldo")]
                 + [(n, C.c_int32) for n in ("M", "N", "K", "act")])
+
+
+class A2PAttentionCase(C.Structure):
+    """a2p_attention_case (include/a2p_hip.h): one launch of the attention dispatcher, test-only."""
+    _fields_ = ([(n, C.c_void_p) for n in ("qbuf", "kbuf", "vt", "out", "ktail", "vtail")]
+                + [("kv_slot_host", C.POINTER(C.c_int32)), ("ran_host", C.POINTER(C.c_int32))]
+                + [(n, C.c_int64) for n in ("q_elems", "k_elems", "vt_elems", "out_elems", "tail_elems", "q_off", "k_off", "vt_off", "out_off",
+                                            "q_seq_stride", "ldq", "k_slot_stride", "ldk", "vt_slot_stride", "ldvt", "o_seq_stride", "ldo",
+                                            "tail_sample_stride", "tail_row_stride")]
+                + [(n, C.c_int32) for n in ("nseq", "Tq", "S_main", "S_tail", "nslots", "slot_rule", "slot_b", "tail_mod", "kv_stream", "ksplit",
+                                            "nseq_rule", "reserved")])
 
 
 class A2PConvSource(C.Structure):
@@ -270,6 +281,7 @@ def load(half: bool = False) -> C.CDLL:
         "a2p_conversation_audio": [vp, i64, i64, i32, vp, i32, C.POINTER(C.c_double), i32, vp, vp],
         "a2p_gemm_ex": [vp, C.POINTER(A2PGemmCase), vp],
         "a2p_skinny_gemm_ex": [vp, C.POINTER(A2PSkinnyCase), i32, vp],
+        "a2p_attention_ex": [vp, C.POINTER(A2PAttentionCase), vp],
         "a2p_dataset_batch": [C.POINTER(A2PDatasetTake), i32, i32, i32, C.POINTER(i32), C.POINTER(i64), i32, i32, i32, i32, vp, vp,
                               f32, f32, f32, i32, vp, vp, vp, vp, vp],
         "a2p_skin_states": [vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],

@@ -462,62 +462,46 @@ static int launch_ln_rope(a2p_ctx* c, bool as_f32, const float* x, int64_t ldx, 
   return 0;
 }
 
+// Which attention kernel a launch takes and how its grid is laid out -- the whole decision of launch_attn, launching nothing
+// (gemm_pick's counterpart; a2p_attention_ex reports it).  kernel: ATTN_K_*; bits: operand bits; waves per workgroup; qt: 16-query
+// tiles per wave (attn2_kernel: 3 | 2, reported as 3); nq: query blocks per (sequence, head) pair; grid: workgroups.
+enum { ATTN_K_ATTN = 0, ATTN_K_KSPLIT = 1, ATTN_K_ATTN2 = 2, ATTN_K_ATTN3 = 3 };
+struct AttnPick {
+  int kernel, bits, dh, waves, qt, nq, grid, xcd_remap;
+};
 // nseq_rule: the sequence count the size rule below decides attn3_kernel vs attn_kernel from (0: nseq).  Denoiser forwards pass
 // the count of the UNSHARDED batch (hinted_nseq, a2p_set_batch_hint): the two kernels differ in rounding, and a shard must take
 // the kernel of the single-process run.  Grids and p.nseq stay local.
-static int launch_attn(a2p_ctx* c, const AttnP& p0, int nseq, int kind, hipStream_t s, bool ksplit = false, int nseq_rule = 0) {
-  AttnP p = p0;
+static AttnPick attn_pick(const a2p_ctx* c, const AttnP& p, int nseq, bool ksplit, int nseq_rule) {
   if (nseq_rule <= 0) nseq_rule = nseq;
+  const int bits = c->bf16 ? 16 : 32;
+  const bool b16 = c->bf16 && (c->DH == 64 || c->DH == 32) && p.ldvt % 8 == 0;   // what every 16-bit-only kernel asks for
   // small forwards (decoder_layer_small): the waves of a workgroup split the keys instead of the queries (kernels_attn.h)
-  if ((ksplit || c->opt.force_ksplit) && c->bf16 && !c->opt.no_ksplit && (c->DH == 64 || c->DH == 32) && p.ldvt % 8 == 0 && p.S_tail <= 2) {
+  if ((ksplit || c->opt.force_ksplit) && b16 && !c->opt.no_ksplit && p.S_tail <= 2) {
     // waves x query tiles per wave: A2P_KSPLIT_NW / A2P_KSPLIT_QT (experiment switches)
     const int ntiles = (p.S_main + p.S_tail + 63) / 64;
     // measured at 2 x 240 frames (profiles/r03_ksplit_ab.txt): 16 queries per wave beat 32 (the tile arithmetic of a lone wave per
     // SIMD is serial), 8 waves beat 4 once a 4-wave workgroup would walk more than two tiles per wave (800 keys = 13 tiles)
     const bool w8 = c->opt.ksplit_nw == 8 || (c->opt.ksplit_nw == 0 && ntiles > 8);
     const int qt = c->opt.ksplit_qt == 2 ? 2 : 1;
-    p.nq = (p.Tq + 16 * qt - 1) / (16 * qt); p.nheads = c->H; p.nseq = nseq; p.xcd_remap = 0;
-    p.stat_max = c->nonfinite.p ? reinterpret_cast<int*>(c->nonfinite.p) + 1 : nullptr;   // the envelope check covers the small forwards too
-    dim3 grid(p.nq * c->H * nseq);
-    KernelTimer kt(c, kind);
-#define A2P_KS(DH_) \
-    do { \
-      if (w8 && qt == 1) A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 8, 1>), grid, 512, s, p); \
-      else if (w8) A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 8, 2>), grid, 512, s, p); \
-      else if (qt == 1) A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 4, 1>), grid, 256, s, p); \
-      else A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 4, 2>), grid, 256, s, p); \
-    } while (0)
-    if (c->DH == 64) A2P_KS(64);
-    else A2P_KS(32);
-#undef A2P_KS
-    HIPCHK(hipGetLastError());
-    return 0;
+    const int nq = (p.Tq + 16 * qt - 1) / (16 * qt);
+    return {ATTN_K_KSPLIT, 16, c->DH, w8 ? 8 : 4, qt, nq, nq * c->H * nseq, 0};
   }
   // A2P_ATTN_WAVES=2 (16-bit modes): 2-wave workgroups of 64 queries -- a perfectly even 5 workgroups per CU at B=8, but every K/V
   // tile then feeds half as many queries: measured 97 vs 70 us for the cross attention (experiment switch, kernels_attn.h NWV)
-  p.stat_max = (c->DH != 128 && c->nonfinite.p) ? reinterpret_cast<int*>(c->nonfinite.p) + 1 : nullptr;   // denoiser attentions only
   static const bool two = getenv("A2P_ATTN_WAVES") && atoi(getenv("A2P_ATTN_WAVES")) == 2;
   const int nwv = (c->bf16 && two) ? 2 : 4;
-  p.nq = (p.Tq + 32 * nwv - 1) / (32 * nwv); p.nheads = c->H; p.nseq = nseq;
+  const int nq = (p.Tq + 32 * nwv - 1) / (32 * nwv);
   static const bool no_remap = getenv("A2P_ATTN_NO_REMAP") != nullptr;   // A/B switch
-  p.xcd_remap = (!no_remap && (c->H * nseq) % 8 == 0) ? 1 : 0;
-  if (c->bf16 && c->opt.attn2 && (c->DH == 64 || c->DH == 32) && p.ldvt % 8 == 0) {   // round 5: balanced 8-wave pipeline kernel
-    p.nq = (p.Tq + 319) / 320;
-    dim3 grid2(p.nq * c->H * nseq);
-    KernelTimer kt2(c, kind);
-    if (c->DH == 64) A2P_LAUNCH(kt2, (attn2_kernel<64, 3, 2>), grid2, 512, s, p);
-    else A2P_LAUNCH(kt2, (attn2_kernel<32, 3, 2>), grid2, 512, s, p);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
+  const int remap = (!no_remap && (c->H * nseq) % 8 == 0) ? 1 : 0;
+  const int nq3 = (p.Tq + 319) / 320;   // the 320-query workgroups of attn2_kernel and attn3_kernel
+  if (b16 && c->opt.attn2) return {ATTN_K_ATTN2, 16, c->DH, 8, 3, nq3, nq3 * c->H * nseq, remap};   // round 5: balanced 8-wave pipeline kernel
   // Round 6: attn3_kernel (kernels_attn3.h) -- one wave per SIMD, 80 queries per wave, ISA-level tile body with a lazy softmax
   // reference.  Measured stand-alone against attn_kernel (scratch/attn3_bench.hip, profiles/r06_attn3_bench.txt): x1.35 on the B=8
   // cross attention (2000 keys, 256 workgroups = one per CU), x1.12 on its self attention, x1.07 on the B=32 cross attention, but
   // x0.85 on short key ranges once the launch is several rounds of workgroups (its per-workgroup prologue is longer), and slower on
   // the body model's short key ranges -- hence the rule.
-  if (c->bf16 && c->opt.attn3 && !c->opt.attn2 && (c->DH == 64 || c->DH == 32) && p.ldvt % 8 == 0) {
-    const int nq3 = (p.Tq + 319) / 320;
-    const int64_t wgs = (int64_t)nq3 * c->H * nseq;
+  if (b16 && c->opt.attn3) {
     const int64_t wgs_rule = (int64_t)nq3 * c->H * nseq_rule;
     // v5 (row sums on the matrix pipe; profiles/r06_attn3_bench_v5.txt): also x1.19 on the body model's cross attention (head_dim 32, 2000 keys, 512 workgroups:
     // 81 vs 97 us); its self attention (600 keys) and the B=32 face self attention stay x0.9
@@ -525,30 +509,50 @@ static int launch_attn(a2p_ctx* c, const AttnP& p0, int nseq, int kind, hipStrea
     // ... and NOT below one attn_kernel workgroup per CU (profiles/r06_attn3_small_batch.txt: up to 6 sequences of 600 frames attn_kernel's 128-query workgroups
     // are one round of <= 240 and finish in 32-36 us (cross) / 13-14 us (self) where attn3's 320-query workgroups take their fixed 41-44 / 19 us: x0.7-0.8;
     // from 8 sequences on attn_kernel needs a second round and attn3 leads x1.18 / x1.02)
-    const int64_t wgs1_rule = (int64_t)p.nq * c->H * nseq_rule;   // attn_kernel's grid (of the unsharded batch)
+    const int64_t wgs1_rule = (int64_t)nq * c->H * nseq_rule;   // attn_kernel's grid (of the unsharded batch)
     const bool wins = p.Tq >= 160 && wgs1_rule > 256 && ((c->DH == 64 && (S3 >= 1024 || wgs_rule <= 256)) || (c->DH == 32 && S3 >= 1024));
-    if (c->opt.attn3 >= 2 || wins) {
-      p.nq = nq3;
-      dim3 grid3((unsigned)wgs);
-      KernelTimer kt3(c, kind);
-      if (c->DH == 64) A2P_LAUNCH(kt3, (attn3_kernel<64>), grid3, 256, s, p);
-      else A2P_LAUNCH(kt3, (attn3_kernel<32>), grid3, 256, s, p);
-      HIPCHK(hipGetLastError());
-      ++c->attn3_launches;
-      return 0;
-    }
+    if (c->opt.attn3 >= 2 || wins) return {ATTN_K_ATTN3, 16, c->DH, 4, 5, nq3, nq3 * c->H * nseq, remap};
   }
-  dim3 grid(p.nq * c->H * nseq);
+  return {ATTN_K_ATTN, bits, c->DH, nwv, 2, nq, nq * c->H * nseq, remap};
+}
+
+static int launch_attn(a2p_ctx* c, const AttnP& p0, int nseq, int kind, hipStream_t s, bool ksplit = false, int nseq_rule = 0) {
+  AttnP p = p0;
+  const AttnPick k = attn_pick(c, p, nseq, ksplit, nseq_rule);
+  p.nq = k.nq; p.nheads = c->H; p.nseq = nseq; p.xcd_remap = k.xcd_remap;
+  // the envelope check (a2p_attention_logit_max) covers the denoiser's attentions, the small forwards included; not the lip regressor's
+  p.stat_max = (c->DH != 128 && c->nonfinite.p) ? reinterpret_cast<int*>(c->nonfinite.p) + 1 : nullptr;
+  ARG(k.dh != 128 || !c->bf16, "head_dim 128 is instantiated for fp32 only");
+  const dim3 grid((unsigned)k.grid);
   KernelTimer kt(c, kind);
-  if (c->DH == 128) {  // lip regressor of the audio front end (4 heads x 128), fp32 only
-    ARG(!c->bf16, "head_dim 128 is instantiated for fp32 only");
+  if (k.kernel == ATTN_K_KSPLIT) {
+#define A2P_KS(DH_) \
+    do { \
+      if (k.waves == 8 && k.qt == 1) A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 8, 1>), grid, 512, s, p); \
+      else if (k.waves == 8) A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 8, 2>), grid, 512, s, p); \
+      else if (k.qt == 1) A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 4, 1>), grid, 256, s, p); \
+      else A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 4, 2>), grid, 256, s, p); \
+    } while (0)
+    if (k.dh == 64) A2P_KS(64);
+    else A2P_KS(32);
+#undef A2P_KS
+  } else if (k.kernel == ATTN_K_ATTN2) {
+    if (k.dh == 64) A2P_LAUNCH(kt, (attn2_kernel<64, 3, 2>), grid, 512, s, p);
+    else A2P_LAUNCH(kt, (attn2_kernel<32, 3, 2>), grid, 512, s, p);
+  } else if (k.kernel == ATTN_K_ATTN3) {
+    if (k.dh == 64) A2P_LAUNCH(kt, (attn3_kernel<64>), grid, 256, s, p);
+    else A2P_LAUNCH(kt, (attn3_kernel<32>), grid, 256, s, p);
+    HIPCHK(hipGetLastError());
+    ++c->attn3_launches;
+    return 0;
+  } else if (k.dh == 128) {  // lip regressor of the audio front end (4 heads x 128), fp32 only
     A2P_LAUNCH(kt, (attn_kernel<float, 128>), grid, 256, s, p);
-  } else if (c->DH == 64) {
-    if (c->bf16 && nwv == 2) A2P_LAUNCH(kt, (attn_kernel<h16_t, 64, 0, 2>), grid, 128, s, p);
+  } else if (k.dh == 64) {
+    if (c->bf16 && k.waves == 2) A2P_LAUNCH(kt, (attn_kernel<h16_t, 64, 0, 2>), grid, 128, s, p);
     else if (c->bf16) A2P_LAUNCH(kt, (attn_kernel<h16_t, 64>), grid, 256, s, p);
     else A2P_LAUNCH(kt, (attn_kernel<float, 64>), grid, 256, s, p);
   } else {
-    if (c->bf16 && nwv == 2) A2P_LAUNCH(kt, (attn_kernel<h16_t, 32, 0, 2>), grid, 128, s, p);
+    if (c->bf16 && k.waves == 2) A2P_LAUNCH(kt, (attn_kernel<h16_t, 32, 0, 2>), grid, 128, s, p);
     else if (c->bf16) A2P_LAUNCH(kt, (attn_kernel<h16_t, 32>), grid, 256, s, p);
     else A2P_LAUNCH(kt, (attn_kernel<float, 32>), grid, 256, s, p);
   }

@@ -1921,6 +1921,92 @@ extern "C" int a2p_skinny_gemm_ex(a2p_ctx* c, const a2p_skinny_case* q, int32_t 
   return 0;
 }
 
+// Test-only: one launch_attn call with every field of AttnP in the caller's hands (include/a2p_hip.h a2p_attention_case).  The images
+// are narrowed whole in the 16-bit modes (padding included, as a2p_gemm_ex narrows its output image) and O is widened back whole.
+extern "C" int a2p_attention_ex(a2p_ctx* c, const a2p_attention_case* q, void* stream) {
+  ARG(c && q && q->qbuf && q->vt && q->out, "attention_ex: null argument");
+  ARG(c->DH == 64 || c->DH == 32, "attention_ex: head_dim %d (the fp32 head_dim 128 instance belongs to the audio front end's context)", c->DH);
+  ARG(c->nonfinite.p, "attention_ex: the context has no logit-maximum slot");
+  const int64_t d = c->d;
+  const int nseq = q->nseq, Tq = q->Tq, S = q->S_main + q->S_tail, Sp = rup(S, 64);
+  ARG(nseq >= 1 && Tq >= 1 && q->S_main >= 1 && q->S_tail >= 0 && q->S_tail <= 64 && q->nslots >= 1, "attention_ex: bad shape nseq=%d Tq=%d S_main=%d S_tail=%d",
+      nseq, Tq, q->S_main, q->S_tail);
+  ARG(q->slot_rule >= 0 && q->slot_rule <= 3 && q->tail_mod >= 1 && q->nseq_rule >= 0 && (q->kv_stream == 0 || q->kv_stream == 1), "attention_ex: bad rule field");
+  ARG(!q->ksplit || q->S_tail <= 2, "attention_ex: the key-split kernel takes at most two tail rows");
+  const float* kimg = q->kbuf ? q->kbuf : q->qbuf;
+  const int64_t k_elems = q->kbuf ? q->k_elems : q->q_elems;
+  auto al8 = [](int64_t v) { return v >= 0 && v % 8 == 0; };
+  ARG((uintptr_t)q->qbuf % 16 == 0 && (uintptr_t)kimg % 16 == 0 && (uintptr_t)q->vt % 16 == 0 && (uintptr_t)q->out % 16 == 0, "attention_ex: images must be 16-byte aligned");
+  ARG(al8(q->q_off) && al8(q->k_off) && al8(q->vt_off) && al8(q->out_off) && al8(q->q_seq_stride) && al8(q->ldq) && al8(q->k_slot_stride) && al8(q->ldk) &&
+      al8(q->vt_slot_stride) && al8(q->ldvt) && al8(q->o_seq_stride) && al8(q->ldo), "attention_ex: offsets and strides must be multiples of 8 elements (ldvt % 8 == 0 is the kernels' contract)");
+  // reads of Q and writes of O: rows < Tq of every sequence, the d columns of the head block
+  ARG(q->ldq >= d && q->q_off + (int64_t)(nseq - 1) * q->q_seq_stride + (int64_t)(Tq - 1) * q->ldq + d <= q->q_elems, "attention_ex: Q leaves its buffer");
+  ARG(q->ldo >= d && q->out_off + (int64_t)(nseq - 1) * q->o_seq_stride + (int64_t)(Tq - 1) * q->ldo + d <= q->out_elems, "attention_ex: O leaves its buffer");
+  ARG(nseq == 1 || q->o_seq_stride >= (int64_t)(Tq - 1) * q->ldo + d, "attention_ex: output sequences overlap");
+  // K / V^T: whole 64-key tiles of every slot
+  ARG(q->ldk >= d && q->ldvt >= Sp, "attention_ex: ldk < d or ldvt < %d keys", Sp);
+  ARG(q->nslots == 1 || (q->k_slot_stride >= (int64_t)(Sp - 1) * q->ldk + d && q->vt_slot_stride >= (d - 1) * q->ldvt + Sp), "attention_ex: K/V slots overlap");
+  ARG(q->k_off + (int64_t)(q->nslots - 1) * q->k_slot_stride + (int64_t)(Sp - 1) * q->ldk + d <= k_elems, "attention_ex: a K slot does not hold %d keys", Sp);
+  ARG(q->vt_off + (int64_t)(q->nslots - 1) * q->vt_slot_stride + (d - 1) * q->ldvt + Sp <= q->vt_elems, "attention_ex: a V^T slot does not hold %d keys", Sp);
+  for (int seq = 0; seq < nseq; ++seq) {
+    const int slot = q->slot_rule == 1 ? 1 + seq : q->slot_rule == 2 ? 0 : q->slot_rule == 3 ? (seq < q->slot_b ? 1 + seq : 0) : q->kv_slot_host ? q->kv_slot_host[seq] : seq;
+    ARG(slot >= 0 && slot < q->nslots, "attention_ex: sequence %d reads slot %d of %d", seq, slot, q->nslots);
+  }
+  if (q->S_tail > 0) {
+    const int64_t samples = q->tail_mod < nseq ? q->tail_mod : nseq;
+    ARG(q->ktail && q->vtail && (uintptr_t)q->ktail % 16 == 0 && (uintptr_t)q->vtail % 16 == 0, "attention_ex: tail rows missing or misaligned");
+    ARG(q->tail_row_stride >= d && q->tail_row_stride % 4 == 0 && q->tail_sample_stride % 4 == 0 &&
+        (samples == 1 || q->tail_sample_stride >= (int64_t)(q->S_tail - 1) * q->tail_row_stride + d), "attention_ex: bad tail strides");
+    ARG((samples - 1) * q->tail_sample_stride + (int64_t)(q->S_tail - 1) * q->tail_row_stride + d <= q->tail_elems, "attention_ex: the tail leaves its buffer");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  Buf q16, k16, v16, o16, slots;
+  struct Free { Buf *a, *b, *c, *d, *e; ~Free() { buf_free(*a); buf_free(*b); buf_free(*c); buf_free(*d); buf_free(*e); } } fr{&q16, &k16, &v16, &o16, &slots};
+  const void *Qp = q->qbuf, *Kp = kimg, *Vp = q->vt;
+  void* Op = q->out;
+  if (c->bf16) {
+    auto narrow = [&](const float* src, int64_t n, Buf& b) -> int {
+      CHK(buf_alloc_tmp(b, (size_t)n * 2));
+      narrow_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(src, reinterpret_cast<h16_t*>(b.p), n);
+      HIPCHK(hipGetLastError());
+      return 0;
+    };
+    CHK(narrow(q->qbuf, q->q_elems, q16));
+    if (q->kbuf) CHK(narrow(q->kbuf, q->k_elems, k16));
+    CHK(narrow(q->vt, q->vt_elems, v16));
+    CHK(narrow(q->out, q->out_elems, o16));
+    Qp = q16.p; Kp = q->kbuf ? k16.p : q16.p; Vp = v16.p; Op = o16.p;
+  }
+  AttnP a;
+  memset(&a, 0, sizeof(a));
+  if (q->slot_rule == 0 && q->kv_slot_host) {
+    CHK(buf_alloc_tmp(slots, (size_t)nseq * sizeof(int)));
+    HIPCHK(hipMemcpyAsync(slots.p, q->kv_slot_host, (size_t)nseq * sizeof(int), hipMemcpyHostToDevice, s));
+    a.kv_slot = reinterpret_cast<const int*>(slots.p);
+  }
+  a.Q = c->offT(const_cast<void*>(Qp), q->q_off); a.q_seq_stride = q->q_seq_stride; a.ldq = q->ldq;
+  a.K = c->offT(const_cast<void*>(Kp), q->k_off); a.k_slot_stride = q->k_slot_stride; a.ldk = q->ldk;
+  a.VT = c->offT(const_cast<void*>(Vp), q->vt_off); a.vt_slot_stride = q->vt_slot_stride; a.ldvt = q->ldvt;
+  a.O = c->offT(Op, q->out_off); a.o_seq_stride = q->o_seq_stride; a.ldo = q->ldo;
+  if (q->S_tail > 0) { a.ktail = q->ktail; a.vtail = q->vtail; a.tail_sample_stride = q->tail_sample_stride; a.tail_row_stride = q->tail_row_stride; }
+  a.slot_rule = q->slot_rule; a.slot_b = q->slot_b; a.tail_mod = q->tail_mod; a.kv_stream = q->kv_stream;
+  a.Tq = Tq; a.S_main = q->S_main; a.S_tail = q->S_tail;
+  a.scale_log2e = 1.4426950408889634f / sqrtf((float)c->DH);
+  if (q->ran_host) {
+    const AttnPick k = attn_pick(c, a, nseq, q->ksplit != 0, q->nseq_rule);
+    const int r[8] = {k.kernel, k.bits, k.dh, k.waves, k.qt, k.nq, k.grid, k.xcd_remap};
+    for (int i = 0; i < 8; ++i) q->ran_host[i] = r[i];
+  }
+  HIPCHK(hipMemsetAsync(reinterpret_cast<int*>(c->nonfinite.p) + 1, 0x80, sizeof(int), s));   // (a2p_attention_logit_max's reset)
+  int rc = launch_attn(c, a, nseq, A2P_KERNEL_ATTN_SELF, s, q->ksplit != 0, q->nseq_rule);
+  if (rc == 0 && c->bf16) {
+    widen_kernel<<<(int)((q->out_elems + 255) / 256), 256, 0, s>>>(reinterpret_cast<const h16_t*>(o16.p), q->out, q->out_elems);
+    if (hipGetLastError() != hipSuccess) { set_err("attention_ex: widen launch failed"); rc = A2P_ERR_HIP; }
+  }
+  if (hipStreamSynchronize(s) != hipSuccess && rc == 0) { set_err("attention_ex: stream synchronisation failed"); rc = A2P_ERR_HIP; }
+  return rc;
+}
+
 template <typename T>
 __global__ void transpose_cast_kernel(const float* __restrict__ v, T* __restrict__ vt, int S, int d, int Sld) {
   // v [n][S][d] -> vt [n][d][Sld]

@@ -342,6 +342,41 @@ int a2p_skinny_gemm_ex(a2p_ctx* ctx, const a2p_skinny_case* cases, int32_t ncase
 /* softmax(q k^T / sqrt(dh)) v per head; q [N, Tq, d], k/v [N, S, d], out [N, Tq, d]. */
 int a2p_attention(a2p_ctx* ctx, const float* q, const float* k, const float* v, float* out, int32_t nseq,
                   int32_t tq, int32_t s, void* stream);
+/* Test-only (never on the product path): ONE launch of the attention dispatcher with every field of the kernels' parameter block in
+ * the caller's hands, so that each kernel instance can be compared with a float64 restatement on its own
+ * (tests/test_attention_family_hip.py).  d = latent_dim, dh = d / num_heads, S = S_main + S_tail, Sp = S rounded up to 64:
+ *   out[out_off + seq * o_seq_stride + t * ldo + h * dh + c] = sum_j softmax_j(q . k_j / sqrt(dh)) v_j[c]      t < Tq
+ *   q   = qbuf[q_off + seq * q_seq_stride + t * ldq + h * dh ..]
+ *   k_j = kbuf[k_off + slot * k_slot_stride + j * ldk + h * dh ..]                                             j < S_main
+ *   v_j[c] = vt[vt_off + slot * vt_slot_stride + (h * dh + c) * ldvt + j]
+ *   k_j, v_j = ktail / vtail[(seq % tail_mod) * tail_sample_stride + (j - S_main) * tail_row_stride + h * dh ..]   S_main <= j < S
+ *   slot = slot_rule 1: 1 + seq;  2: 0;  3: seq < slot_b ? 1 + seq : 0;  0: kv_slot_host[seq], or seq when that is NULL
+ * qbuf, kbuf (NULL: K lives in qbuf, the self-attention layout [T][Q | K]), vt and out are fp32 device images of the WHOLE buffers
+ * (guard rows, padding rows and columns included; q_elems .. out_elems elements).  In a 16-bit mode every image is narrowed to the
+ * 16-bit type before the launch -- a NaN or sentinel in padding reaches the kernel as it is -- and all of out is widened back after
+ * it.  ktail / vtail stay fp32 (the kernels read them as fp32; tail_elems elements each).  kv_slot_host is a HOST array of nseq
+ * slots.  Every K and V^T slot must hold Sp keys (the kernels move whole 64-key tiles), nslots of them lie in the buffers.
+ * ksplit / nseq_rule: launch_attn's arguments of the same name.  kv_stream: the non-temporal policy of the K/V tile loads.
+ * ran_host (host memory, may be NULL) receives the dispatcher's decision: {kernel (0 attn_kernel, 1 attn_ksplit_kernel, 2 attn2_kernel,
+ * 3 attn3_kernel), operand bits, head_dim, waves per workgroup, 16-query tiles per wave, query blocks per (sequence, head), workgroups,
+ * xcd_remap}.  The context's logit-maximum slot is reset in front of the launch: a2p_attention_logit_max afterwards returns this
+ * launch's maximum.  A case whose reads or writes would leave a buffer, whose slots or output sequences overlap, or which breaks an
+ * alignment the kernels rely on is A2P_ERR_ARG and nothing is launched.  Synchronises `stream`. */
+typedef struct a2p_attention_case {
+  const float* qbuf;
+  const float* kbuf;
+  const float* vt;
+  float* out;
+  const float* ktail;
+  const float* vtail;
+  const int32_t* kv_slot_host;
+  int32_t* ran_host;
+  int64_t q_elems, k_elems, vt_elems, out_elems, tail_elems;
+  int64_t q_off, k_off, vt_off, out_off;
+  int64_t q_seq_stride, ldq, k_slot_stride, ldk, vt_slot_stride, ldvt, o_seq_stride, ldo, tail_sample_stride, tail_row_stride;
+  int32_t nseq, Tq, S_main, S_tail, nslots, slot_rule, slot_b, tail_mod, kv_stream, ksplit, nseq_rule, reserved;
+} a2p_attention_case;
+int a2p_attention_ex(a2p_ctx* ctx, const a2p_attention_case* attention_case, void* stream);
 
 /* ---- measurement (bench.py roofline leg) ----------------------------------------
  * When enabled, every launch of the kernel class `kind` is bracketed by hipEvents on
