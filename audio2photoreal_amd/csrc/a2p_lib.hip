@@ -25,7 +25,6 @@
 
 #include "../../include/a2p_hip.h"
 #include "kernels_attn.h"
-#include "kernels_attn2.h"
 #include "kernels_attn3.h"
 #include "kernels_audio.h"
 #include "kernels_chain.h"
@@ -166,8 +165,7 @@ static inline int rup(int v, int m) { return (v + m - 1) / m * m; }
 struct A2POpts {
   int kv_cached = 0;        // A2P_KV_CACHED=1: default cache policy for the cached audio K/V (A/B)
   int no_chain = 0;         // A2P_NO_CHAIN=1: per-op kernels instead of the chain kernels
-  int chain_nw = 0;         // A2P_CHAIN_NW=4|8: force the generation-1 workgroup shape (0: measured per box)
-  int chain_tune = 0;       // A2P_CHAIN_TUNE=1: measure the 4- vs 8-wave chain workgroup shape in situ (round 3's default); 0: 8 waves
+  int chain_nw = 0;         // A2P_CHAIN_NW=4|8: force the generation-1 workgroup shape (0: 8 waves)
   int chain_mt = 0;         // A2P_CHAIN_MT=n: force the panel height 16*n (also takes the chain path below 960 rows)
   int chain_no_mix = 0;     // A2P_CHAIN_NO_MIX=1: uniform panel heights
   int tune_verbose = 0;     // A2P_TUNE_VERBOSE=1: print the per-box shape decision
@@ -178,22 +176,17 @@ struct A2POpts {
   int no_shared_half = 0;   // A2P_NO_SHARED_HALF=1: layer 0 computed for both guidance halves
   int no_ksplit = 0;        // A2P_NO_KSPLIT=1: small forwards use attn_kernel instead of the key-split attention (A/B)
   int ksplit_nw = 0;        // A2P_KSPLIT_NW=4|8: waves of the key-split attention
-  int ksplit_qt = 0;        // A2P_KSPLIT_QT=1|2: 16-query tiles per wave of the key-split attention
   int force_ksplit = 0;     // A2P_ATTN_KSPLIT=1: every 16-bit attention launch takes the key-split kernel (tests)
   int chain_v = 0;          // A2P_CHAIN_V=4: tall chain kernels (kernels_chain4.h) wherever their contract holds; A2P_CHAIN_V=1: never; 0: the
                             // faster of the two families ON THIS BOX, measured during the first forwards of a size (chain_pick_family)
   int attn3 = 1;            // A2P_ATTN3: 1 (default) = the one-wave-per-SIMD kernel with the ISA-level tile body (kernels_attn3.h) where it wins
                             // (head_dim 64, >= 160 queries, and >= 1024 keys or at most one workgroup per CU: launch_attn); 2 = wherever it is legal
                             // (tests); 0 = never (A/B)
-  int attn2 = 0;            // A2P_ATTN2=1: the query-split 16-bit attention launches take attn2_kernel (kernels_attn2.h: one 8-wave workgroup per CU,
-                            // 48 + 32 queries per SIMD, unit-level software pipeline); 0: attn_kernel
   int no_fused_kf = 0;      // A2P_NO_FUSED_KF=1: body model: MID2 | keyframe attention | POST as three launches instead of one (A/B, tests)
   int time_table = 1000;    // A2P_TIME_TABLE: rows of the time-MLP table (a2p_ctx::tct_table) built at a2p_finalize_weights; 0 = compute the time MLP in every forward
   int no_fused_in = 0;      // A2P_NO_FUSED_IN=1: face model: pack_input_split3 + gemm_kernel + the gen-1 PRE kernel instead of chain4_kernel<MT, CHAIN_IN> (A/B, tests)
   int no_fused_final = 0;   // A2P_NO_FUSED_FINAL=1: face model: final_layer behind the last tall POST kernel as split3_kernel + gemm_kernel instead of inside it (A/B, tests)
   int fused_tail = 1;       // A2P_FUSED_TAIL=0: guided DDPM step: step_tail_kernel behind the last tall POST kernel instead of inside it (chain4_kernel<3, POST, 3>; A/B, tests)
-  int graph = 0;            // A2P_GRAPH=1: non-chain forwards replay a captured graph instead of stream launches (measured: same GPU
-                            // time per step -- the launches are not host-bound -- at a tenth of the host time; off by default)
   int no_small = 0;         // A2P_NO_SMALL=1: per-op kernels for forwards below 960 rows instead of kernels_small.h
   int chain_rows = 1100;    // A2P_CHAIN_ROWS=n: forwards of at least n rows take the chain kernels.  Measured against the small-forward kernels
                             // (profiles/r03_ksplit_ab.txt): 960 rows (2 x 2 x 240) small 1192 vs chain 1002 steps/s; 1200 rows (2 x 600 frames, 2000
@@ -204,12 +197,11 @@ static void load_opts(A2POpts& o) {
   auto num = [](const char* n, int dflt) { const char* v = getenv(n); return v ? atoi(v) : dflt; };
   o.kv_cached = flag("A2P_KV_CACHED"); o.no_chain = flag("A2P_NO_CHAIN");
   o.chain_nw = num("A2P_CHAIN_NW", 0); o.chain_mt = num("A2P_CHAIN_MT", 0);
-  o.chain_no_mix = flag("A2P_CHAIN_NO_MIX"); o.chain_tune = flag("A2P_CHAIN_TUNE"); o.tune_verbose = flag("A2P_TUNE_VERBOSE"); o.side_join = num("A2P_SIDE_JOIN", 3);
+  o.chain_no_mix = flag("A2P_CHAIN_NO_MIX"); o.tune_verbose = flag("A2P_TUNE_VERBOSE"); o.side_join = num("A2P_SIDE_JOIN", 3);
   o.x_rowmajor = flag("A2P_CHAIN_X_ROWMAJOR"); o.no_side_stream = flag("A2P_NO_SIDE_STREAM");
   o.side_early_join = flag("A2P_SIDE_EARLY_JOIN"); o.no_shared_half = flag("A2P_NO_SHARED_HALF");
-  o.graph = flag("A2P_GRAPH");
-  o.no_ksplit = flag("A2P_NO_KSPLIT"); o.force_ksplit = flag("A2P_ATTN_KSPLIT"); o.ksplit_nw = num("A2P_KSPLIT_NW", 0); o.ksplit_qt = num("A2P_KSPLIT_QT", 0);
-  o.no_fused_kf = flag("A2P_NO_FUSED_KF"); o.no_fused_final = flag("A2P_NO_FUSED_FINAL"); o.no_fused_in = flag("A2P_NO_FUSED_IN"); o.fused_tail = num("A2P_FUSED_TAIL", 1); o.time_table = num("A2P_TIME_TABLE", 1000); o.attn2 = num("A2P_ATTN2", 0); o.attn3 = num("A2P_ATTN3", 1); o.chain_v = num("A2P_CHAIN_V", 0);
+  o.no_ksplit = flag("A2P_NO_KSPLIT"); o.force_ksplit = flag("A2P_ATTN_KSPLIT"); o.ksplit_nw = num("A2P_KSPLIT_NW", 0);
+  o.no_fused_kf = flag("A2P_NO_FUSED_KF"); o.no_fused_final = flag("A2P_NO_FUSED_FINAL"); o.no_fused_in = flag("A2P_NO_FUSED_IN"); o.fused_tail = num("A2P_FUSED_TAIL", 1); o.time_table = num("A2P_TIME_TABLE", 1000); o.attn3 = num("A2P_ATTN3", 1); o.chain_v = num("A2P_CHAIN_V", 0);
   o.no_small = flag("A2P_NO_SMALL"); o.chain_rows = num("A2P_CHAIN_ROWS", 1100);
 }
 
@@ -256,12 +248,11 @@ struct a2p_ctx {
   std::vector<Buf> ch_stream4;         // kernels_chain4.h: half-stage streams [layer*5 + kind] (CH_MID, CH_POST of the face model; empty Buf otherwise)
   std::vector<Buf> ch_stream, ch_aux;  // packed weight streams [layout * L*5 + layer*5 + kind] (layout 0: 4-wave LDS slices, 1: 8-wave; kinds: a2p_lib_run.h CH_*) / bias blocks [layer*5 + kind]
   int ch_nw = 4;                       // waves per chain workgroup of the forward being enqueued (4 or 8; chain_pick_nw)
-  struct ChainTune {                   // per forward size (rows): which workgroup shape is faster ON THIS BOX, measured in situ
+  struct ChainTune {                   // per forward size (rows): which chain kernel family is faster ON THIS BOX, measured in situ
     int choice = 0, calls = 0;
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> samples;
   };
-  std::map<int64_t, ChainTune> ch_tune;
-  std::map<int64_t, ChainTune> ch_tune4;   // per forward size: kernels_chain.h (1) or kernels_chain4.h (4), measured in situ (chain_pick_family)
+  std::map<int64_t, ChainTune> ch_tune4;   // kernels_chain.h (1) or kernels_chain4.h (4) (chain_pick_family)
   int ch_fam_mid = 4, ch_fam_post = 4;     // chain kernel families of the forward being enqueued (MID kernels, POST kernels)
   Buf hidden, kc, vtc, k2c, vt2c, slot_cond, slot_unc, slot_cfg;
   // separate guidance of audio and keyframes (a2p_set_guidance; body model): per-sequence slot tables of the 2B / 3B sequence passes,
@@ -281,12 +272,6 @@ struct a2p_ctx {
   Buf ce_pack, pooled, tmpa, tmpb, kf_pack, kf_tok;
   // timing
   int time_kind = -1;
-  // captured forwards (a2p_lib_run.h run_forward)
-  struct GraphKey { int pass, B, T, S0, K, small, epoch; };
-  struct GraphEnt { GraphKey key; hipGraphExec_t exec; int rows; };
-  std::vector<GraphEnt> graphs;
-  hipStream_t gstream = nullptr;
-  int graph_epoch = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
   std::vector<hipEvent_t> ev_pool;
   // side stream: the per-step time path (t -> FiLM scale/shift, time-token K/V) overlaps the first projections / self attention
@@ -379,15 +364,12 @@ static GemmPick gemm_pick(const a2p_ctx* c, const GemmP& p) {
   const int64_t blocks128 = (int64_t)((p.N + 127) / 128) * ((p.M + 127) / 128);
   const bool small = c->bf16 || blocks128 < 512;
   // 16-bit launches of at most one 64x128 workgroup per CU (config 0: 480 rows) are K/64 serial memory round trips with the
-  // 2-deep ring; they take the 4-deep one (A2P_GEMM_RING2=1 keeps the 2-deep ring for A/B runs)
-  static const bool ring2 = getenv("A2P_GEMM_RING2") != nullptr;
+  // 2-deep ring; they take the 4-deep one
   const int64_t blocks64 = (int64_t)((p.N + 127) / 128) * ((p.M + 63) / 64);
   // narrow tap-accumulating launches (the body model's dilated conv tail: N <= 128, i.e. one column tile; 312 workgroups of 64 rows
-  // at B=16 = 1.2 per CU, each a chain of 18 k-tile round trips): 32-row tiles double the workgroups per CU (A2P_GEMM_MT1=0|1)
-  static const int mt1 = getenv("A2P_GEMM_MT1") ? atoi(getenv("A2P_GEMM_MT1")) : 1;
-  static const int ring4_blocks = getenv("A2P_GEMM_RING4_BLOCKS") ? atoi(getenv("A2P_GEMM_RING4_BLOCKS")) : 256;   // (A/B: the 4-deep ring up to this many 64-row workgroups)
-  if (c->bf16 && mt1 && p.ntaps > 1 && p.N <= 128 && blocks64 <= 3 * 256) return {16, 1, 2};
-  if (c->bf16 && small && blocks64 <= ring4_blocks && p.ntaps == 1 && !ring2) return {16, 2, 4};
+  // at B=16 = 1.2 per CU, each a chain of 18 k-tile round trips): 32-row tiles double the workgroups per CU
+  if (c->bf16 && p.ntaps > 1 && p.N <= 128 && blocks64 <= 3 * 256) return {16, 1, 2};
+  if (c->bf16 && small && blocks64 <= 256 && p.ntaps == 1) return {16, 2, 4};
   if (c->bf16) return {16, small ? 2 : 4, 2};
   return {32, small ? 2 : 4, 2};
 }
@@ -464,8 +446,8 @@ static int launch_ln_rope(a2p_ctx* c, bool as_f32, const float* x, int64_t ldx, 
 
 // Which attention kernel a launch takes and how its grid is laid out -- the whole decision of launch_attn, launching nothing
 // (gemm_pick's counterpart; a2p_attention_ex reports it).  kernel: ATTN_K_*; bits: operand bits; waves per workgroup; qt: 16-query
-// tiles per wave (attn2_kernel: 3 | 2, reported as 3); nq: query blocks per (sequence, head) pair; grid: workgroups.
-enum { ATTN_K_ATTN = 0, ATTN_K_KSPLIT = 1, ATTN_K_ATTN2 = 2, ATTN_K_ATTN3 = 3 };
+// tiles per wave; nq: query blocks per (sequence, head) pair; grid: workgroups.
+enum { ATTN_K_ATTN = 0, ATTN_K_KSPLIT = 1, ATTN_K_ATTN3 = 3 };   // 2 was attn2_kernel (removed; the reported numbers do not shift)
 struct AttnPick {
   int kernel, bits, dh, waves, qt, nq, grid, xcd_remap;
 };
@@ -478,24 +460,19 @@ static AttnPick attn_pick(const a2p_ctx* c, const AttnP& p, int nseq, bool kspli
   const bool b16 = c->bf16 && (c->DH == 64 || c->DH == 32) && p.ldvt % 8 == 0;   // what every 16-bit-only kernel asks for
   // small forwards (decoder_layer_small): the waves of a workgroup split the keys instead of the queries (kernels_attn.h)
   if ((ksplit || c->opt.force_ksplit) && b16 && !c->opt.no_ksplit && p.S_tail <= 2) {
-    // waves x query tiles per wave: A2P_KSPLIT_NW / A2P_KSPLIT_QT (experiment switches)
     const int ntiles = (p.S_main + p.S_tail + 63) / 64;
     // measured at 2 x 240 frames (profiles/r03_ksplit_ab.txt): 16 queries per wave beat 32 (the tile arithmetic of a lone wave per
     // SIMD is serial), 8 waves beat 4 once a 4-wave workgroup would walk more than two tiles per wave (800 keys = 13 tiles)
-    const bool w8 = c->opt.ksplit_nw == 8 || (c->opt.ksplit_nw == 0 && ntiles > 8);
-    const int qt = c->opt.ksplit_qt == 2 ? 2 : 1;
-    const int nq = (p.Tq + 16 * qt - 1) / (16 * qt);
-    return {ATTN_K_KSPLIT, 16, c->DH, w8 ? 8 : 4, qt, nq, nq * c->H * nseq, 0};
+    const bool w8 = c->opt.ksplit_nw == 8 || (c->opt.ksplit_nw == 0 && ntiles > 8);   // A2P_KSPLIT_NW: tests reach both at small shapes
+    const int nq = (p.Tq + 15) / 16;
+    return {ATTN_K_KSPLIT, 16, c->DH, w8 ? 8 : 4, 1, nq, nq * c->H * nseq, 0};
   }
-  // A2P_ATTN_WAVES=2 (16-bit modes): 2-wave workgroups of 64 queries -- a perfectly even 5 workgroups per CU at B=8, but every K/V
-  // tile then feeds half as many queries: measured 97 vs 70 us for the cross attention (experiment switch, kernels_attn.h NWV)
-  static const bool two = getenv("A2P_ATTN_WAVES") && atoi(getenv("A2P_ATTN_WAVES")) == 2;
-  const int nwv = (c->bf16 && two) ? 2 : 4;
+  // attn_kernel: 4-wave workgroups of 128 queries (2-wave workgroups of 64 were rejected, 97 vs 70 us for the cross attention:
+  // every K/V tile then feeds half as many queries; profiles/r02_attn_ablation.txt)
+  const int nwv = 4;
   const int nq = (p.Tq + 32 * nwv - 1) / (32 * nwv);
-  static const bool no_remap = getenv("A2P_ATTN_NO_REMAP") != nullptr;   // A/B switch
-  const int remap = (!no_remap && (c->H * nseq) % 8 == 0) ? 1 : 0;
-  const int nq3 = (p.Tq + 319) / 320;   // the 320-query workgroups of attn2_kernel and attn3_kernel
-  if (b16 && c->opt.attn2) return {ATTN_K_ATTN2, 16, c->DH, 8, 3, nq3, nq3 * c->H * nseq, remap};   // round 5: balanced 8-wave pipeline kernel
+  const int remap = (c->H * nseq) % 8 == 0 ? 1 : 0;
+  const int nq3 = (p.Tq + 319) / 320;   // the 320-query workgroups of attn3_kernel
   // Round 6: attn3_kernel (kernels_attn3.h) -- one wave per SIMD, 80 queries per wave, ISA-level tile body with a lazy softmax
   // reference.  Measured stand-alone against attn_kernel (scratch/attn3_bench.hip, profiles/r06_attn3_bench.txt): x1.35 on the B=8
   // cross attention (2000 keys, 256 workgroups = one per CU), x1.12 on its self attention, x1.07 on the B=32 cross attention, but
@@ -528,17 +505,12 @@ static int launch_attn(a2p_ctx* c, const AttnP& p0, int nseq, int kind, hipStrea
   if (k.kernel == ATTN_K_KSPLIT) {
 #define A2P_KS(DH_) \
     do { \
-      if (k.waves == 8 && k.qt == 1) A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 8, 1>), grid, 512, s, p); \
-      else if (k.waves == 8) A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 8, 2>), grid, 512, s, p); \
-      else if (k.qt == 1) A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 4, 1>), grid, 256, s, p); \
-      else A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 4, 2>), grid, 256, s, p); \
+      if (k.waves == 8) A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 8, 1>), grid, 512, s, p); \
+      else A2P_LAUNCH(kt, (attn_ksplit_kernel<DH_, 4, 1>), grid, 256, s, p); \
     } while (0)
     if (k.dh == 64) A2P_KS(64);
     else A2P_KS(32);
 #undef A2P_KS
-  } else if (k.kernel == ATTN_K_ATTN2) {
-    if (k.dh == 64) A2P_LAUNCH(kt, (attn2_kernel<64, 3, 2>), grid, 512, s, p);
-    else A2P_LAUNCH(kt, (attn2_kernel<32, 3, 2>), grid, 512, s, p);
   } else if (k.kernel == ATTN_K_ATTN3) {
     if (k.dh == 64) A2P_LAUNCH(kt, (attn3_kernel<64>), grid, 256, s, p);
     else A2P_LAUNCH(kt, (attn3_kernel<32>), grid, 256, s, p);
@@ -548,12 +520,10 @@ static int launch_attn(a2p_ctx* c, const AttnP& p0, int nseq, int kind, hipStrea
   } else if (k.dh == 128) {  // lip regressor of the audio front end (4 heads x 128), fp32 only
     A2P_LAUNCH(kt, (attn_kernel<float, 128>), grid, 256, s, p);
   } else if (k.dh == 64) {
-    if (c->bf16 && k.waves == 2) A2P_LAUNCH(kt, (attn_kernel<h16_t, 64, 0, 2>), grid, 128, s, p);
-    else if (c->bf16) A2P_LAUNCH(kt, (attn_kernel<h16_t, 64>), grid, 256, s, p);
+    if (c->bf16) A2P_LAUNCH(kt, (attn_kernel<h16_t, 64>), grid, 256, s, p);
     else A2P_LAUNCH(kt, (attn_kernel<float, 64>), grid, 256, s, p);
   } else {
-    if (c->bf16 && k.waves == 2) A2P_LAUNCH(kt, (attn_kernel<h16_t, 32, 0, 2>), grid, 128, s, p);
-    else if (c->bf16) A2P_LAUNCH(kt, (attn_kernel<h16_t, 32>), grid, 256, s, p);
+    if (c->bf16) A2P_LAUNCH(kt, (attn_kernel<h16_t, 32>), grid, 256, s, p);
     else A2P_LAUNCH(kt, (attn_kernel<float, 32>), grid, 256, s, p);
   }
   HIPCHK(hipGetLastError());
@@ -744,7 +714,6 @@ extern "C" int a2p_ctx_create(const a2p_config* cfg, a2p_ctx** out) {
 
 extern "C" int a2p_set_batch_hint(a2p_ctx* c, int32_t global_batch) {
   ARG(c && global_batch >= 0, "bad arguments");
-  if (global_batch != c->batch_hint) ++c->graph_epoch;   // a captured forward (A2P_GRAPH) carries the attention kernels of the hint it was captured under
   c->batch_hint = global_batch;
   return 0;
 }
@@ -759,22 +728,15 @@ extern "C" int a2p_set_guidance(a2p_ctx* c, int32_t mode, const float* scale_key
   return 0;
 }
 
-static void graphs_drop(a2p_ctx* c);   // a2p_lib_run.h: waits for the device, then destroys every captured forward
-
 extern "C" int a2p_reload_env(a2p_ctx* c) {
   ARG(c, "null ctx");
   load_opts(c->opt);
-  ++c->graph_epoch;   // captured forwards carry the kernel choices of the switches they were captured under:
-  graphs_drop(c);     // evicted here, not left to pile up behind a key no forward will ask for again
   return 0;
 }
 
 extern "C" int a2p_ctx_destroy(a2p_ctx* c) {
   if (!c) return 0;
   hipDeviceSynchronize();
-  for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
-  c->graphs.clear();
-  if (c->gstream) (void)hipStreamDestroy(c->gstream);
   for (auto& kv : c->w) buf_free(kv.second);
   for (auto& kv : c->wt) buf_free(kv.second);
   Buf* all[] = {&c->rope_cs, &c->rope_cst, &c->time_freq, &c->film_w, &c->film_b, &c->tct_w, &c->tct_b, &c->tct_table, &c->cak_w32, &c->cak_b, &c->cav_w32,
@@ -789,9 +751,8 @@ extern "C" int a2p_ctx_destroy(a2p_ctx* c) {
   for (auto& b : c->ch_stream4) buf_free(b);
   for (auto& b : c->ch_stream4w) buf_free(b);
   buf_free(c->ch_stream4_in); buf_free(c->ch_aux_in);
-  for (auto* m : {&c->ch_tune, &c->ch_tune4})
-    for (auto& kv : *m)
-      for (auto& sm : kv.second.samples) { (void)hipEventDestroy(std::get<1>(sm)); (void)hipEventDestroy(std::get<2>(sm)); }
+  for (auto& kv : c->ch_tune4)
+    for (auto& sm : kv.second.samples) { (void)hipEventDestroy(std::get<1>(sm)); (void)hipEventDestroy(std::get<2>(sm)); }
   for (auto& b : c->ch_aux) buf_free(b);
   for (void* slab : c->arena.slabs) (void)hipFree(slab);
   for (int i = 0; i < 8; ++i) {
@@ -855,8 +816,6 @@ static int chain_build_streams(a2p_ctx* c, hipStream_t s);
 
 extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
   ARG(c, "null ctx");
-  ++c->graph_epoch;   // the compute-dtype weight copies are rebuilt: captured forwards hold the old pointers
-  graphs_drop(c);
   ArenaScope scope(c->use_arena ? &c->arena : nullptr);
   hipStream_t s = (hipStream_t)stream;
   std::map<std::string, int64_t> e;

@@ -134,7 +134,7 @@ static int chain_pack(a2p_ctx* c, int idx, const std::vector<ChainPackDesc>& des
   Buf dd;
   CHK(buf_alloc_tmp(dd, descs.size() * sizeof(ChainPackDesc)));
   HIPCHK(hipMemcpyAsync(dd.p, descs.data(), descs.size() * sizeof(ChainPackDesc), hipMemcpyHostToDevice, s));
-  for (int w8 = 0; w8 < 2; ++w8) {  // both slice layouts: 4 waves x 32 out-cols and 8 waves x 16 (chain_pick_nw chooses per box)
+  for (int w8 = 0; w8 < 2; ++w8) {  // both slice layouts: 4 waves x 32 out-cols and 8 waves x 16 (chain_pick_nw chooses)
     Buf& st = c->ch_stream[(size_t)w8 * c->L * CH_KINDS + idx];
     CHK(buf_alloc(st, (descs.size() + pad) * CHAIN_STAGE_ELEMS * 2));
     chain_pack_kernel<<<(int)descs.size(), 256, 0, s>>>(reinterpret_cast<const ChainPackDesc*>(dd.p), reinterpret_cast<h16_t*>(st.p), w8 ? 8 : 4);
@@ -343,51 +343,15 @@ static void chain_set_out_proj(a2p_ctx* c, ChainP& p, const std::string& attn, c
 // (kernels_chain.h: one shared LayerNorm reduction tree, no floating-point contraction; tests/test_hip_round2.py).
 // Which one is faster depends on the BOX, not on the code: on most MI355X boxes NW=4 leads by 3-5 % at B=8, on a sizeable
 // minority the 512-register kernels run 35 % slower inside the step (not in isolation) and NW=8 leads by 19 % (docs/lab_notebook_r1_r4.md
-// section 6).  So it is measured in situ: forwards 1..4 of a given size alternate the two shapes with an event pair around
-// the decoder stack (forward 0 is warm-up), forward 5 picks the faster average and the choice sticks.  A2P_CHAIN_NW=4|8 forces.
-// Round 4: the in-situ measurement is OPT-IN (A2P_CHAIN_TUNE=1).  The default is the 8-wave shape everywhere: deterministic per
-// process and per rank (round 3's tuner timed 4 forwards per size and box: run-to-run noise decided close calls, and the ranks of
-// one job could disagree), immune to the slow-box regime, and the only shape with mixed panel heights at B=32; what it gives up is
-// the 4-wave shape's 3-5 % at B=8 on the boxes where that shape runs well.
-static const int kTuneForwards = 5;
-static int chain_pick_nw(a2p_ctx* c, int64_t rows, hipEvent_t* e0, hipEvent_t* e1) {
-  *e0 = *e1 = nullptr;
+// section 6).  The rule is the 8-wave shape everywhere: deterministic per process and per rank, immune to the slow-box regime, and
+// the only shape with mixed panel heights at B=32; what it gives up is the 4-wave shape's 3-5 % at B=8 on the boxes where that
+// shape runs well.  (Round 3 measured the two shapes in situ instead: four timed forwards per size and box let run-to-run noise
+// decide close calls, and the ranks of one job could disagree -- removed.)  A2P_CHAIN_NW=4|8 forces.
+static int chain_pick_nw(const a2p_ctx* c) {
   if (c->opt.chain_nw) return c->opt.chain_nw == 8 ? 8 : 4;
-  if (!c->opt.chain_tune) {
-    const int mt = c->opt.chain_mt;
-    if (mt == 5 && c->d == 512 && c->opt.chain_v != 1 && !c->ch_stream4.empty() && c->ch_stream4[ch_index(0, CH_MID)].p) return 8;   // 80 rows: the tall kernels (8 waves) have it
-    return (mt && ((mt > 4 && c->d == 512) || mt > 5)) ? 4 : 8;   // forced panel heights the 8-wave kernels do not have
-  }
-  if (c->opt.chain_mt) {  // a forced panel height the 8-wave kernels do not have
-    const int mt = c->opt.chain_mt;
-    if ((mt > 4 && c->d == 512) || mt > 5) return 4;
-  }
-  auto& t = c->ch_tune[rows];
-  if (t.choice) return t.choice;
-  const int call = t.calls++;
-  if (call < kTuneForwards) {
-    const int nw = (call & 1) ? 8 : 4;
-    if (call >= 1 && hipEventCreate(e0) == hipSuccess && hipEventCreate(e1) == hipSuccess) t.samples.emplace_back(nw, *e0, *e1);
-    else *e0 = *e1 = nullptr;
-    return nw;
-  }
-  double sum[2] = {0, 0};
-  int cnt[2] = {0, 0};
-  for (auto& sm : t.samples) {
-    float ms = 0.f;
-    if (hipEventSynchronize(std::get<2>(sm)) == hipSuccess && hipEventElapsedTime(&ms, std::get<1>(sm), std::get<2>(sm)) == hipSuccess) {
-      sum[std::get<0>(sm) == 8] += ms;
-      ++cnt[std::get<0>(sm) == 8];
-    }
-    (void)hipEventDestroy(std::get<1>(sm));
-    (void)hipEventDestroy(std::get<2>(sm));
-  }
-  t.samples.clear();
-  t.choice = (cnt[0] && cnt[1] && sum[1] / cnt[1] < sum[0] / cnt[0]) ? 8 : 4;
-  if (c->opt.tune_verbose)
-    fprintf(stderr, "[a2p] chain workgroup shape for %lld rows: NW=4 %.3f ms, NW=8 %.3f ms -> %d\n", (long long)rows,
-            cnt[0] ? sum[0] / cnt[0] : -1.0, cnt[1] ? sum[1] / cnt[1] : -1.0, t.choice);
-  return t.choice;
+  const int mt = c->opt.chain_mt;
+  if (mt == 5 && c->d == 512 && c->opt.chain_v != 1 && !c->ch_stream4.empty() && c->ch_stream4[ch_index(0, CH_MID)].p) return 8;   // 80 rows: the tall kernels (8 waves) have it
+  return (mt && ((mt > 4 && c->d == 512) || mt > 5)) ? 4 : 8;   // forced panel heights the 8-wave kernels do not have
 }
 
 // Chain kernel FAMILY of a forward, per chain: kernels_chain.h (1) or kernels_chain4.h (4) for the MID kernels and for the POST
@@ -968,13 +932,13 @@ extern "C" int a2p_prepare_cond(a2p_ctx* c, const float* cond_embed, int32_t B, 
 // ------------------------------------------------------------------------------------------------
 // per-step time path (a15, a20, time-token K/V)
 // ------------------------------------------------------------------------------------------------
-static int time_path(a2p_ctx* c, const int64_t* t_orig, int N, const int* slots, hipStream_t s, bool embed = true) {
+static int time_path(a2p_ctx* c, const int64_t* t_orig, int N, const int* slots, hipStream_t s) {
   const int d = c->d, B = c->pB, L = c->L, F = c->F;
   // time_embed -> time_mlp -> [to_time_cond ; to_time_tokens] depend on the timestep VALUE alone: a row of the table built at a2p_finalize_weights (same kernels, same bits)
-  // where there is one and this call may read the caller's timestep tensor (not under graph replay); three launches otherwise
-  const bool table = embed && c->tct_rows > 0 && c->opt.time_table > 0;
+  // where there is one; three launches otherwise
+  const bool table = c->tct_rows > 0 && c->opt.time_table > 0;
   if (!table) {
-    if (embed) time_embed_kernel<<<(B * (d / 2) + 255) / 256, 256, 0, s>>>(t_orig, c->time_freq.f(), c->emb.f(), B, d / 2);
+    time_embed_kernel<<<(B * (d / 2) + 255) / 256, 256, 0, s>>>(t_orig, c->time_freq.f(), c->emb.f(), B, d / 2);
     CHK(launch_skinny(c->emb.f(), d, W32(c, "time_mlp.1.weight"), d, W32(c, "time_mlp.1.bias"), c->th.f(), 4 * d, B, 4 * d, d, ACT_MISH, s));
     CHK(launch_skinny(c->th.f(), 4 * d, c->tct_w.f(), 4 * d, c->tct_b.f(), c->tct.f(), 3 * d, B, 3 * d, 4 * d, ACT_NONE, s));
   }
@@ -1030,23 +994,9 @@ static int pose_conv_tail(a2p_ctx* c, int N, int T, hipStream_t s) {
   return launch_gemm(c, pf, s);
 }
 
-// The two launches of a forward that read CALLER memory (the timestep tensor, the noisy input): time embedding and input pack.
-// They are the first launch of the time path and of the main path; forward_body(ext = false) leaves them out, so that what it
-// launches touches context-owned buffers only and can be replayed as a captured graph (run_forward).
-static int forward_ext(a2p_ctx* c, const float* x_in, const int64_t* t_orig, hipStream_t s) {
-  const int d = c->d, B = c->pB, T = c->pT;
-  time_embed_kernel<<<(B * (d / 2) + 255) / 256, 256, 0, s>>>(t_orig, c->time_freq.f(), c->emb.f(), B, d / 2);
-  dim3 grid((T + 31) / 32, (c->Cpad + 31) / 32, B);
-  if (c->tail_x3) pack_input_split3_kernel<<<grid, 256, 0, s>>>(x_in, (h16_t*)c->inpack.p, B, c->C, T, c->Cpad);
-  else if (c->bf16 && !c->tail32) pack_input_kernel<h16_t><<<grid, 256, 0, s>>>(x_in, (h16_t*)c->inpack.p, B, c->C, T, c->Cpad);
-  else pack_input_kernel<float><<<grid, 256, 0, s>>>(x_in, (float*)c->inpack.p, B, c->C, T, c->Cpad);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 // FiLMTransformer.forward for N sequences; result rows in c->mo ([N][mo_rows][C] fp32)
-static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, int pass, int* mo_seq_rows, hipStream_t s, bool ext,
-                        bool use_chain, bool use_small) {
+static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, int pass, int* mo_seq_rows, hipStream_t s, bool use_chain,
+                        bool use_small) {
   const int d = c->d, B = c->pB, T = c->pT, L = c->L, F = c->F;
   const int N = pass_nseq(pass, B);
   c->clk_turn = 0;
@@ -1070,28 +1020,26 @@ static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, in
     ++c->ev_turn;
     HIPCHK(hipEventRecord(c->ev_fork, s));  // orders the side stream behind t_orig AND behind the previous step's readers
     HIPCHK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    CHK(time_path(c, t_orig, N, slots, c->side, ext));
+    CHK(time_path(c, t_orig, N, slots, c->side));
     HIPCHK(hipEventRecord(c->ev_join, c->side));
     if (c->opt.side_early_join) HIPCHK(hipStreamWaitEvent(s, c->ev_join, 0));  // diagnostic: side stream without overlap
   } else {
-    CHK(time_path(c, t_orig, N, slots, s, ext));
+    CHK(time_path(c, t_orig, N, slots, s));
   }
   hipEvent_t tune0 = nullptr, tune1 = nullptr;
   if (use_chain) {   // (in front of the input projection: chain_in_wanted needs the workgroup shape; the calibration's timed region now includes the projection)
-    c->ch_nw = chain_pick_nw(c, (int64_t)N * T, &tune0, &tune1);
-    if (!tune0) chain_pick_family(c, (int64_t)N * T, &tune0, &tune1);   // (one calibration at a time)
-    else c->ch_fam_mid = c->ch_fam_post = 1;
+    c->ch_nw = chain_pick_nw(c);
+    chain_pick_family(c, (int64_t)N * T, &tune0, &tune1);
     if (tune0) HIPCHK(hipEventRecord(tune0, s));
   }
   // input permute + projection (model/diffusion.py:345-346,364); exact fp32 in every mode (a2p_ctx::tail32).
   // Chain forwards of the face model: inside the first chain kernel (chain4_kernel<MT, CHAIN_IN>: decoder_layer_chain), nothing to launch here.
-  const bool fuse_in = use_chain && ext && chain_in_wanted(c, T, N == B || (N == 2 * B && !c->opt.no_shared_half));
+  const bool fuse_in = use_chain && chain_in_wanted(c, T, N == B || (N == 2 * B && !c->opt.no_shared_half));
   if (!fuse_in) {
     Fp32Scope f32(c, c->tail32 && !c->tail_x3);
     dim3 grid((T + 31) / 32, (c->Cpad + 31) / 32, B);
     const int X = c->tail_x3 ? 3 : 1;
-    if (!ext) {   // forward_ext launched it
-    } else if (c->tail_x3) pack_input_split3_kernel<<<grid, 256, 0, s>>>(x_in, (h16_t*)c->inpack.p, B, c->C, T, c->Cpad);
+    if (c->tail_x3) pack_input_split3_kernel<<<grid, 256, 0, s>>>(x_in, (h16_t*)c->inpack.p, B, c->C, T, c->Cpad);
     else if (c->bf16) pack_input_kernel<h16_t><<<grid, 256, 0, s>>>(x_in, (h16_t*)c->inpack.p, B, c->C, T, c->Cpad);
     else pack_input_kernel<float><<<grid, 256, 0, s>>>(x_in, (float*)c->inpack.p, B, c->C, T, c->Cpad);
     const bool shared_half = use_chain && N == 2 * B && !c->opt.no_shared_half;
@@ -1190,24 +1138,6 @@ static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, in
   return 0;
 }
 
-
-// Opt-in (A2P_GRAPH=1): forwards that are not chain-kernel forwards (config 0: 76 launches of 4-12 us) replayed as a captured graph.
-// Everything behind the two launches that read caller memory is captured ONCE per (pass, prepared geometry, kernel family) on a
-// context-owned stream and replayed with hipGraphLaunch on the caller's stream; replays are bit-identical to stream launches
-// (tests/test_hip_round3.py).  Measured (profiles/r03_ksplit_ab.txt): a dependent stream launch of an EMPTY kernel costs 2.8 us and is
-// host-bound, a graph node 1.6 us (scratch/launch_floor.hip) -- but the step's kernels are longer than the host's enqueue time, the
-// host runs ahead either way, and the step takes the same time (1742 vs 1757 steps/s); what the graph saves is ~200 us of host time per
-// step.  Graphs die with the state they captured: a2p_finalize_weights / a2p_reload_env bump graph_epoch.  Never while a kernel class
-// is being timed (dispatch-packet events are not capturable).
-// Destroying an executable that a caller's stream may still be replaying is not something HIP promises to defer: a drop waits for the
-// device first (rare: the 17th geometry of a long-lived context, a weight update, a2p_reload_env, a2p_ctx_destroy).
-static void graphs_drop(a2p_ctx* c) {
-  if (c->graphs.empty()) return;
-  (void)hipDeviceSynchronize();
-  for (auto& g : c->graphs) (void)hipGraphExecDestroy(g.exec);
-  c->graphs.clear();
-}
-
 static int run_forward(a2p_ctx* c, const float* x_in, const int64_t* t_orig, int pass, int* mo_seq_rows, hipStream_t s) {
   if (!c->prepared) {
     set_err("denoise before a2p_prepare_cond");
@@ -1221,7 +1151,7 @@ static int run_forward(a2p_ctx* c, const float* x_in, const int64_t* t_orig, int
     ARG(c->pose, "pass %d drops audio and keyframes separately: the face model has no keyframes", pass);
     ARG(N <= c->Nmax, "three guidance branches of batch %d are %d sequences, the context holds %d: construct the model with max_batch >= %d",
         B, N, c->Nmax, (N + 1) / 2);
-    if (pass != A2P_PASS_KEYS && c->slot3_B != B) {   // (outside any capture: forward_body's launches only read the tables)
+    if (pass != A2P_PASS_KEYS && c->slot3_B != B) {
       slot_tables3_kernel<<<1, 256, 0, s>>>((int*)c->slot_a3.p, (int*)c->slot_kf3.p, B, c->Nmax);
       HIPCHK(hipGetLastError());
       c->slot3_B = B;
@@ -1238,38 +1168,7 @@ static int run_forward(a2p_ctx* c, const float* x_in, const int64_t* t_orig, int
   const int64_t chain_thr = small_supported(c) ? c->opt.chain_rows : (c->opt.chain_rows < 960 ? c->opt.chain_rows : 960);
   const bool use_chain = chain_supported(c) && (rows_eff >= chain_thr || c->opt.chain_mt);
   const bool use_small = !use_chain && small_supported(c);
-  if (use_chain || !c->opt.graph || c->time_kind >= 0) return forward_body(c, x_in, t_orig, pass, mo_seq_rows, s, true, use_chain, use_small);
-  CHK(forward_ext(c, x_in, t_orig, s));
-  const a2p_ctx::GraphKey key = {pass, B, T, c->pS0, c->pK, use_small ? 1 : 0, c->graph_epoch};
-  for (auto& g : c->graphs)
-    if (memcmp(&g.key, &key, sizeof(key)) == 0) {
-      HIPCHK(hipGraphLaunch(g.exec, s));
-      *mo_seq_rows = g.rows;
-      return 0;
-    }
-  if (c->graphs.size() >= 16) graphs_drop(c);   // a long-lived context walking through many geometries
-  if (!c->gstream) HIPCHK(hipStreamCreateWithFlags(&c->gstream, hipStreamNonBlocking));
-  HIPCHK(hipStreamBeginCapture(c->gstream, hipStreamCaptureModeThreadLocal));
-  int rows = 0;
-  const int rc = forward_body(c, x_in, t_orig, pass, &rows, c->gstream, false, use_chain, use_small);
-  hipGraph_t graph = nullptr;
-  const hipError_t ce = hipStreamEndCapture(c->gstream, &graph);
-  if (rc != 0 || ce != hipSuccess || !graph) {
-    if (graph) (void)hipGraphDestroy(graph);
-    if (rc == 0) set_err("graph capture of the forward failed: %s", hipGetErrorString(ce));
-    return rc != 0 ? rc : A2P_ERR_HIP;
-  }
-  hipGraphExec_t exec = nullptr;
-  const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  if (ie != hipSuccess) {
-    set_err("hipGraphInstantiate: %s", hipGetErrorString(ie));
-    return A2P_ERR_HIP;
-  }
-  c->graphs.push_back({key, exec, rows});
-  HIPCHK(hipGraphLaunch(exec, s));
-  *mo_seq_rows = rows;
-  return 0;
+  return forward_body(c, x_in, t_orig, pass, mo_seq_rows, s, use_chain, use_small);
 }
 
 static int launch_step_tail(a2p_ctx* c, StepP& sp, hipStream_t s) {

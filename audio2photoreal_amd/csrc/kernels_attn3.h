@@ -1,6 +1,6 @@
 // Third attention kernel of the 16-bit modes (round 6): ONE wave per SIMD, 80 queries per wave, and a tile body written at ISA level.
 //
-// What rounds 2-5 measured about attn_kernel / attn2_kernel (docs/lab_notebook_r1_r4.md 4.2, docs/lab_notebook_r5.md 4): per 64-key
+// What rounds 2-5 measured about attn_kernel and round 5's since-removed 8-wave kernel (docs/lab_notebook_r1_r4.md 4.2, docs/lab_notebook_r5.md 4): per 64-key
 // tile a 32-query wave issues 32 MFMAs against ~220 VALU instructions (6.8 per MFMA), the loop is instruction-ISSUE bound, and every
 // term of the ablation adds.  Round 6 measured the issue model itself (scratch/ubench/mfma_fill.hip, profiles/r06_mfma_fill.txt): in
 // one wave's in-order stream a v_mfma_f32_16x16x32 (18 cycles back to back) hides TWO single-issue instructions; every further one
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(A3_OWN))) vo
   const h16_t* Kb = reinterpret_cast<const h16_t*>(p.K) + (int64_t)slot * p.k_slot_stride + head * DH;
   const h16_t* Vb = reinterpret_cast<const h16_t*>(p.VT) + (int64_t)slot * p.vt_slot_stride + (int64_t)head * DH * p.ldvt;
 
-  // ---- tile DMA (attn2_kernel's: inline asm so that hipcc neither waits for it nor orders LDS reads behind it) ----
+  // ---- tile DMA (inline asm so that hipcc neither waits for it nor orders LDS reads behind it) ----
   // piece pi of a tile = K piece pi (pi < NPK) or V^T piece pi - NPK; wave w owns pieces w, w + NW, ...: its first NPK / NW are K pieces
   constexpr int CPR = DH / 8, KRPI = 64 / CPR, KPW = G::NPK / NW;
   int64_t src_off[PW];
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(A3_OWN))) vo
       attn3_static_for<0, KC>([&](auto k_c) __attribute__((always_inline)) {
         constexpr int q = decltype(q_c)::value, kc = decltype(k_c)::value;
         (void)&qf;
-        asm volatile("" : "+v"(qf[q][kc]));   // hipcc's own vmcnt(0) for the Q loads lands here, not inside the loop (attn2_kernel)
+        asm volatile("" : "+v"(qf[q][kc]));   // hipcc's own vmcnt(0) for the Q loads lands here, not inside the loop
 #pragma unroll
         for (int e = 0; e < 8; ++e) qf[q][kc][e] = (h16_t)((float)qf[q][kc][e] * p.scale_log2e);
         const u32x4 w = __builtin_bit_cast(u32x4, qf[q][kc]);

@@ -357,7 +357,7 @@ int a2p_attention(a2p_ctx* ctx, const float* q, const float* k, const float* v, 
  * it.  ktail / vtail stay fp32 (the kernels read them as fp32; tail_elems elements each).  kv_slot_host is a HOST array of nseq
  * slots.  Every K and V^T slot must hold Sp keys (the kernels move whole 64-key tiles), nslots of them lie in the buffers.
  * ksplit / nseq_rule: launch_attn's arguments of the same name.  kv_stream: the non-temporal policy of the K/V tile loads.
- * ran_host (host memory, may be NULL) receives the dispatcher's decision: {kernel (0 attn_kernel, 1 attn_ksplit_kernel, 2 attn2_kernel,
+ * ran_host (host memory, may be NULL) receives the dispatcher's decision: {kernel (0 attn_kernel, 1 attn_ksplit_kernel, 2 unused,
  * 3 attn3_kernel), operand bits, head_dim, waves per workgroup, 16-query tiles per wave, query blocks per (sequence, head), workgroups,
  * xcd_remap}.  The context's logit-maximum slot is reset in front of the launch: a2p_attention_logit_max afterwards returns this
  * launch's maximum.  A case whose reads or writes would leave a buffer, whose slots or output sequences overlap, or which breaks an

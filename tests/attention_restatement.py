@@ -1,5 +1,5 @@
 """Cases, inputs, a float64 torch restatement, the dispatcher's rule and the derived per-element error bound of the attention family
-(csrc/kernels_attn.h attn_kernel / attn_ksplit_kernel, kernels_attn2.h attn2_kernel, kernels_attn3.h attn3_kernel, all behind
+(csrc/kernels_attn.h attn_kernel / attn_ksplit_kernel, kernels_attn3.h attn3_kernel, all behind
 launch_attn / attn_pick of csrc/a2p_lib.hip).  Test infrastructure: shared by tests/test_attention_family_cpu.py and
 tests/test_attention_family_hip.py.
 
@@ -25,23 +25,20 @@ D_MODEL = 256
 U32 = 2.0 ** -24
 THR3 = 8.0                  # attn3_kernel: log2 units a score may exceed the lazy reference by (A2P_ATTN3_THR)
 ENVELOPE_16BIT = 20.0       # A2P_LOGIT_ENVELOPE_16BIT (include/a2p_hip.h; INTEGRATION.md "validity envelope")
-K_ATTN, K_KSPLIT, K_ATTN2, K_ATTN3 = 0, 1, 2, 3
-KERNEL_NAMES = ("attn", "ksplit", "attn2", "attn3")
+K_ATTN, K_KSPLIT, K_ATTN3 = 0, 1, 3                     # ATTN_K_* of csrc/a2p_lib.hip; 2 is unused
+KERNEL_NAMES = ("attn", "ksplit", None, "attn3")
 PAD_BIG_K, PAD_BIG_V = 12.0, 28672.0   # "big" padding: finite, exact in all three types; a K row of +-12 is what a 6x spike looks like
 
 # The instances a case runs as: name -> (environment switches, modes).  "default" leaves every switch alone.
 INSTANCES = {
     "attn": ({"A2P_ATTN3": "0"}, MODES),
-    "attn2": ({"A2P_ATTN2": "1"}, B16),
     "attn3": ({"A2P_ATTN3": "2"}, B16),
-    "ks4q1": ({"A2P_ATTN_KSPLIT": "1", "A2P_KSPLIT_NW": "4", "A2P_KSPLIT_QT": "1"}, B16),
-    "ks4q2": ({"A2P_ATTN_KSPLIT": "1", "A2P_KSPLIT_NW": "4", "A2P_KSPLIT_QT": "2"}, B16),
-    "ks8q1": ({"A2P_ATTN_KSPLIT": "1", "A2P_KSPLIT_NW": "8", "A2P_KSPLIT_QT": "1"}, B16),
-    "ks8q2": ({"A2P_ATTN_KSPLIT": "1", "A2P_KSPLIT_NW": "8", "A2P_KSPLIT_QT": "2"}, B16),
+    "ks4q1": ({"A2P_ATTN_KSPLIT": "1", "A2P_KSPLIT_NW": "4"}, B16),
+    "ks8q1": ({"A2P_ATTN_KSPLIT": "1", "A2P_KSPLIT_NW": "8"}, B16),
     "default": ({}, MODES),
 }
-ENV_NAMES = ("A2P_ATTN3", "A2P_ATTN2", "A2P_ATTN_KSPLIT", "A2P_KSPLIT_NW", "A2P_KSPLIT_QT", "A2P_NO_KSPLIT")
-FORCED = ("attn", "attn2", "attn3", "ks4q1", "ks4q2", "ks8q1", "ks8q2")
+ENV_NAMES = ("A2P_ATTN3", "A2P_ATTN_KSPLIT", "A2P_KSPLIT_NW", "A2P_NO_KSPLIT")
+FORCED = ("attn", "attn3", "ks4q1", "ks8q1")
 
 
 @dataclass(frozen=True)
@@ -256,7 +253,7 @@ def restate(case, ops):
 # ----------------------------------------------------------------------------- the dispatcher's rule
 def pick(mode, case, env=None):
     """attn_pick of csrc/a2p_lib.hip restated from launch_attn's rule: (kernel, operand bits, head_dim, waves, 16-query tiles per wave,
-    query blocks per (sequence, head), workgroups, xcd_remap).  env: the A2P_* switches (A2P_ATTN_WAVES / A2P_ATTN_NO_REMAP unset)."""
+    query blocks per (sequence, head), workgroups, xcd_remap).  env: the A2P_* switches."""
     env = env or {}
     num = lambda n, dflt: int(env.get(n, dflt))
     b16, H, dh, Tq, S = mode != "fp32", case.H, case.dh, case.Tq, case.S
@@ -267,13 +264,10 @@ def pick(mode, case, env=None):
     if (case.ksplit or "A2P_ATTN_KSPLIT" in env) and b16 and "A2P_NO_KSPLIT" not in env and case.S_tail <= 2:
         nw = num("A2P_KSPLIT_NW", 0)
         w8 = nw == 8 or (nw == 0 and ceil(S, 64) > 8)          # 8 waves once 4 would walk more than two tiles each
-        qt = 2 if num("A2P_KSPLIT_QT", 0) == 2 else 1
-        nq = ceil(Tq, 16 * qt)
-        return (K_KSPLIT, 16, dh, 8 if w8 else 4, qt, nq, nq * pairs, 0)
+        nq = ceil(Tq, 16)
+        return (K_KSPLIT, 16, dh, 8 if w8 else 4, 1, nq, nq * pairs, 0)
     remap = 1 if pairs % 8 == 0 else 0
     nq, nq3 = ceil(Tq, 128), ceil(Tq, 320)
-    if b16 and num("A2P_ATTN2", 0):
-        return (K_ATTN2, 16, dh, 8, 3, nq3, nq3 * pairs, remap)
     a3 = num("A2P_ATTN3", 1)
     if b16 and a3:
         # where it wins: >= 160 queries, more than one attn_kernel workgroup per CU (256) in the rule's batch, and long key ranges
@@ -400,7 +394,7 @@ def bound(case, mode, kernel, r, exp2_rel=0.0):
                   renormalisation: |d out| <= expm1(2 delta) Dv, delta from `logit_delta` (fp32 accumulation over dh; attn3: the rounded
                   pre-scaled Q).  exp2_rel, the relative error of the hardware exp2, enters the same way (not derivable: the caller's
                   measured constant, 0.0 until measured).
-      P operand   16-bit modes: P_j (1 + rho_j), |rho_j| <= u, in the numerator.  attn_kernel / ksplit / attn2 keep the UNROUNDED fp32 P
+      P operand   16-bit modes: P_j (1 + rho_j), |rho_j| <= u, in the numerator.  attn_kernel / ksplit keep the UNROUNDED fp32 P
                   in the row sum: d out = sum_j w_j rho_j v_j = (P rounding against the weighted mean, <= u Dv) + (mismatch of the row
                   sum, <= u |out|), bounded together by u Mv.  attn3 sums the rounded P (its row sums are MFMAs on the P operand), so
                   the rounding renormalises: expm1(2 u) Dv; its P reaches 2^8 relative to the lazy reference -- the same relative
@@ -456,7 +450,7 @@ def _padded_kv(case, ops, seq, fault):
 
 def emulate(case, mode, family, ops, fault=None, nw=4):
     """The kernel families in plain fp32 torch, [nseq, Tq, d] rounded to the stored type.
-    "online": attn_kernel / attn2_kernel -- online softmax per 64-key tile, 16-bit P operand, fp32 row sum of the unrounded P;
+    "online": attn_kernel -- online softmax per 64-key tile, 16-bit P operand, fp32 row sum of the unrounded P;
     "ksplit": attn_ksplit_kernel -- wave w of nw walks tiles w, w + nw, ..; partial (m, l, O) states merged by log-sum-exp;
     "lazy":   attn3_kernel -- Q pre-scaled by log2(e) / sqrt(dh) and rounded, a reference that moves (for the 80 queries of a wave at
               once) only when a score exceeds it by more than 8, row sums of the ROUNDED P.
@@ -553,4 +547,4 @@ def emulate(case, mode, family, ops, fault=None, nw=4):
     return rp(out)
 
 
-FAMILY_OF = {K_ATTN: "online", K_ATTN2: "online", K_KSPLIT: "ksplit", K_ATTN3: "lazy"}
+FAMILY_OF = {K_ATTN: "online", K_KSPLIT: "ksplit", K_ATTN3: "lazy"}

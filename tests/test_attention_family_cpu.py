@@ -103,10 +103,10 @@ def _case(**k):
 
 
 def test_pick_restates_the_documented_rule():
-    A, KS, A2, A3 = R.K_ATTN, R.K_KSPLIT, R.K_ATTN2, R.K_ATTN3
+    A, KS, A3 = R.K_ATTN, R.K_KSPLIT, R.K_ATTN3
     kern = lambda mode, env=None, **k: R.pick(mode, _case(**k), env)[0]
     # fp32 never leaves attn_kernel, whatever is forced
-    for env in ({}, {"A2P_ATTN3": "2"}, {"A2P_ATTN2": "1"}, {"A2P_ATTN_KSPLIT": "1"}):
+    for env in ({}, {"A2P_ATTN3": "2"}, {"A2P_ATTN_KSPLIT": "1"}):
         assert R.pick("fp32", _case(nseq=16, ksplit=1), env)[:5] == (A, 32, 64, 4, 2)
     # attn3 by size: head_dim 64, >= 160 queries, more than 256 attn_kernel workgroups of the RULE's batch, and at most 256 of its own
     assert kern("bf16", nseq=16) == A3                        # 5 * 4 * 16 = 320 > 256; 2 * 4 * 16 = 128 <= 256
@@ -117,27 +117,25 @@ def test_pick_restates_the_documented_rule():
     assert kern("bf16", nseq=64, S_main=1022, S_tail=2) == A3 and kern("bf16", nseq=64, S_main=1021, S_tail=2) == A   # the key count rule
     assert kern("bf16", H=8, nseq=8) == A and kern("bf16", H=8, nseq=8, S_main=1024) == A3       # head_dim 32: long key ranges only
     assert kern("bf16", {"A2P_ATTN3": "0"}, nseq=16) == A and kern("fp16", {"A2P_ATTN3": "2"}, Tq=1, S_main=1) == A3
-    assert kern("bf16", {"A2P_ATTN2": "1"}, nseq=16) == A2    # attn2 goes before attn3
-    # geometry: query blocks of 128 (attn_kernel), 320 (attn2 / attn3), 16 or 32 (key split); the remap needs pairs % 8 == 0
+    # geometry: query blocks of 128 (attn_kernel), 320 (attn3), 16 (key split); the remap needs pairs % 8 == 0
     assert R.pick("bf16", _case(nseq=2, Tq=321), {"A2P_ATTN3": "0"}) == (A, 16, 64, 4, 2, 3, 24, 1)
     assert R.pick("bf16", _case(nseq=3, Tq=321), {"A2P_ATTN3": "2"}) == (A3, 16, 64, 4, 5, 2, 24, 0)
-    assert R.pick("fp16", _case(H=8, nseq=1, Tq=320), {"A2P_ATTN2": "1"}) == (A2, 16, 32, 8, 3, 1, 8, 1)
     # key split: on request or forced; 8 waves above 8 tiles unless the switch says otherwise; never remapped; at most two tail rows
     assert R.pick("bf16", _case(nseq=2, Tq=33, S_main=510, S_tail=2, ksplit=1)) == (KS, 16, 64, 4, 1, 3, 24, 0)
     assert R.pick("bf16", _case(nseq=2, Tq=33, S_main=511, S_tail=2, ksplit=1)) == (KS, 16, 64, 8, 1, 3, 24, 0)
-    assert R.pick("bf16", _case(nseq=2, Tq=33, S_main=65), {"A2P_ATTN_KSPLIT": "1", "A2P_KSPLIT_NW": "8", "A2P_KSPLIT_QT": "2"}) == (KS, 16, 64, 8, 2, 2, 16, 0)
+    assert R.pick("bf16", _case(nseq=2, Tq=33, S_main=65), {"A2P_ATTN_KSPLIT": "1", "A2P_KSPLIT_NW": "8"}) == (KS, 16, 64, 8, 1, 3, 24, 0)
     assert R.pick("bf16", _case(nseq=2, Tq=33, S_main=900), {"A2P_ATTN_KSPLIT": "1", "A2P_KSPLIT_NW": "4"})[3] == 4
     assert kern("bf16", Tq=33, S_main=65, S_tail=3, ksplit=1) == A and kern("bf16", {"A2P_NO_KSPLIT": "1"}, Tq=33, S_main=65, ksplit=1) == A
 
 
 def test_the_case_list_reaches_every_instance():
-    """attn_kernel<float | h16, 32 | 64>, the eight key-split instances, attn2 / attn3 at 64 and 32 -- each in the modes that have it."""
+    """attn_kernel<float | h16, 32 | 64>, the four key-split instances, attn3 at 64 and 32 -- each in the modes that have it."""
     for mode in R.MODES:
         seen = {R.pick(mode, c, R.INSTANCES[i][0])[:5] for c in R.CASES for i in R.instances_of(c, mode)}
         want = {(R.K_ATTN, 32 if mode == "fp32" else 16, dh, 4, 2) for dh in (32, 64)}
         if mode != "fp32":
-            want |= {(R.K_KSPLIT, 16, dh, nw, qt) for dh in (32, 64) for nw in (4, 8) for qt in (1, 2)}
-            want |= {(R.K_ATTN2, 16, dh, 8, 3) for dh in (32, 64)} | {(R.K_ATTN3, 16, dh, 4, 5) for dh in (32, 64)}
+            want |= {(R.K_KSPLIT, 16, dh, nw, 1) for dh in (32, 64) for nw in (4, 8)}
+            want |= {(R.K_ATTN3, 16, dh, 4, 5) for dh in (32, 64)}
         assert seen == want, seen ^ want
     # ... and the default rule reaches attn3, attn_kernel and the requested key split (4 and 8 waves) with no switch set
     by_rule = {c.name: R.pick("bf16", c)[:4] for c in R.CASES if c.instances == ("default",)}

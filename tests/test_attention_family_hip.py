@@ -1,5 +1,5 @@
 """Every attention kernel instance against float64, element by element (csrc/kernels_attn.h attn_kernel / attn_ksplit_kernel,
-kernels_attn2.h attn2_kernel, kernels_attn3.h attn3_kernel, through launch_attn of csrc/a2p_lib.hip and the test-only entry point
+kernels_attn3.h attn3_kernel, through launch_attn of csrc/a2p_lib.hip and the test-only entry point
 a2p_attention_ex, which puts every field of the kernels' parameter block in the caller's hands).
 
 Per case (tests/attention_restatement.py) and instance:
@@ -10,9 +10,8 @@ Per case (tests/attention_restatement.py) and instance:
   4. a second launch returns the same bits;
   5. the logit maximum the launch reports is the float64 maximum over the VALID keys, to the derived logit bound: K pad rows (NaN
      bit patterns in half of the cases, +-12 -- a 6x spike -- in the other half) must not leak into it.
-Instances reached: attn_kernel<float, 32 | 64>, attn_kernel<h16_t, 32 | 64>, attn_ksplit_kernel<32 | 64, 4 | 8, 1 | 2>, attn2_kernel<32 | 64>,
-attn3_kernel<32 | 64>, the 16-bit ones in the IEEE-half and the bfloat16 build.  Deliberately not reached: the 2-wave experiment
-instances attn_kernel<h16_t, DH, 0, 2> (A2P_ATTN_WAVES is read once per process), and attn_kernel<float, 128>, which exists only on
+Instances reached: attn_kernel<float, 32 | 64>, attn_kernel<h16_t, 32 | 64>, attn_ksplit_kernel<32 | 64, 4 | 8, 1>,
+attn3_kernel<32 | 64>, the 16-bit ones in the IEEE-half and the bfloat16 build.  Deliberately not reached: attn_kernel<float, 128>, which exists only on
 the audio front end's own context (a2p_ctx_create refuses head_dim 128; tests/test_frontend_hip.py covers it through the lip
 regressor).  The keyframe attention fused into the chain kernel is not an AttnP kernel."""
 import ctypes as C

@@ -459,58 +459,3 @@ def test_16bit_sampling_call_outside_the_envelope_escalates_to_fp32(dev, name, k
     assert wo["forward_rel_l2"] > 1e-3 and wo["rel_l2"] > e["rel_l2"], (wo, e)   # the 16-bit forward IS outside the bar here
     if name == "qk_x3":
         assert cond < 1e-4 and gate == 1e-3, cond
-
-
-# ----------------------------------------------------------------------------- round 5: the 8-wave anti-phase attention kernel (opt-in experiment)
-@pytest.mark.parametrize("precision", ["fp16", "bf16"])
-@pytest.mark.parametrize("fmt", ["face", "pose"])
-def test_attn2_kernel_is_bit_identical_to_attn_kernel(dev, fmt, precision, monkeypatch):
-    """csrc/kernels_attn2.h (A2P_ATTN2=1): one 8-wave workgroup per CU, 48 + 32 queries per SIMD, the two waves of a SIMD alternating
-    between a matrix segment (PV + next tile's QK^T) and a vector segment (softmax) in anti-phase, 8-slot K/V ring behind counted
-    vmcnt waits.  Same arithmetic per (query, key tile) as attn_kernel, so the outputs must be IDENTICAL -- through a2p_attention
-    (one tile, ragged tiles, many tiles, a spiked key) and through a whole guided forward (cached K/V slots, the time-token tail
-    patched into the last tile, the shared unconditional slot)."""
-    from audio2photoreal_amd.spec import face_spec as fs, pose_spec as ps
-    monkeypatch.setenv("A2P_ATTN3", "0")   # the reference side is attn_kernel, not round 6's attn3_kernel (which is not bit-identical to either)
-    spec = fs() if fmt == "face" else ps()
-    model, _ = create_model_and_diffusion(default_args(fmt), "test", precision=precision, max_batch=2)
-    load_model(model, synthetic_state_dict(spec, SEED))
-    model = model.to(dev).eval()
-    model._ensure_ctx(dev, 2)
-    lib = model._lib()
-    d = spec.latent_dim
-    g = torch.Generator().manual_seed(7)
-
-    def both(fn):
-        outs = []
-        for val in (None, "1"):
-            if val is None:
-                monkeypatch.delenv("A2P_ATTN2", raising=False)
-            else:
-                monkeypatch.setenv("A2P_ATTN2", val)
-            _lib.check(lib.a2p_reload_env(model._ctx), "a2p_reload_env")
-            outs.append(fn())
-        monkeypatch.delenv("A2P_ATTN2", raising=False)
-        _lib.check(lib.a2p_reload_env(model._ctx), "a2p_reload_env")
-        return outs
-    for (N, Tq, S) in [(2, 100, 77), (1, 600, 800), (3, 33, 20), (2, 321, 640), (1, 150, 150)]:
-        q, k, v = (torch.randn(N, L, d, generator=g) for L in (Tq, S, S))
-        k[0, S // 3] *= 6.0
-        qd, kd, vd = q.to(dev), k.to(dev), v.to(dev)
-
-        def run():
-            out = torch.empty(N, Tq, d, device=dev)
-            _lib.check(lib.a2p_attention(model._ctx, _lib.ptr(qd), _lib.ptr(kd), _lib.ptr(vd), _lib.ptr(out), N, Tq, S, _lib.current_stream()), "a2p_attention")
-            return out.cpu()
-        a, b = both(run)
-        assert torch.isfinite(b).all() and torch.equal(a, b), (N, Tq, S, float((a - b).abs().max()))
-    B, T = 2, 600
-    inp = synthetic_inputs(spec, B, T, SEED)
-    y = {"cond_embed": inp["cond_embed"].to(dev), "scale": torch.full((B,), 10.0 if fmt == "face" else 2.0, device=dev)}
-    if spec.is_pose:
-        y["keyframes"], y["mask"] = inp["keyframes"].to(dev), inp["mask"].to(dev)
-    cfg = ClassifierFreeSampleModel(model)
-    t = torch.tensor([901, 33], device=dev)
-    a, b = both(lambda: cfg(inp["x_T"].to(dev), t, y).cpu())
-    model.release()
-    assert torch.isfinite(b).all() and torch.equal(a, b), float((a - b).abs().max())

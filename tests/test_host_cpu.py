@@ -42,6 +42,32 @@ def test_header_symbols_are_exported_and_bound():
     assert lib.a2p_version().decode().startswith("a2p_hip")
 
 
+# Environment reads of csrc/ outside load_opts: read once per context or per process, so a2p_reload_env cannot see them and no test
+# may toggle them on a live context.  A new name here needs a reason; a switch meant to be toggled belongs in load_opts.
+STATIC_ENV_READS = {"A2P_TAIL16", "A2P_TAIL_F32", "A2P_NO_FUSED_TAIL", "A2P_NO_ARENA", "A2P_CHAIN_CLK", "A2P_STAMP_LAUNCH"}
+
+
+def test_env_switch_inventory_matches_the_library():
+    """Python calls a2p_reload_env only when a name of _lib.ENV_SWITCHES changes: a switch load_opts reads but the tuple lacks would
+    make every test that toggles it compare a path with itself.  So: the names load_opts reads (csrc/a2p_lib.hip) are exactly
+    _lib.ENV_SWITCHES, every other getenv("A2P_...") of csrc/ is in the short list above, and INTEGRATION.md names them all."""
+    csrc = os.path.join(ROOT, "audio2photoreal_amd", "csrc")
+    lib_src = open(os.path.join(csrc, "a2p_lib.hip")).read()
+    body = re.search(r"static void load_opts\(A2POpts& o\) \{(.*?)\n\}", lib_src, flags=re.S).group(1)
+    loaded = re.findall(r"\b(?:flag|num)\(\"(A2P_[A-Z0-9_]+)\"", body)
+    assert len(loaded) == len(set(loaded)) and len(_lib.ENV_SWITCHES) == len(set(_lib.ENV_SWITCHES))
+    assert set(loaded) == set(_lib.ENV_SWITCHES), set(loaded) ^ set(_lib.ENV_SWITCHES)
+    assert "getenv(\"" not in body, "load_opts reads through flag / num only"
+    static = set()
+    for name in sorted(os.listdir(csrc)):
+        static |= set(re.findall(r"getenv\(\"(A2P_[A-Z0-9_]+)\"\)", open(os.path.join(csrc, name)).read()))
+    assert static == STATIC_ENV_READS, static ^ STATIC_ENV_READS
+    assert not static & set(loaded)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    missing = [n for n in sorted(static | set(loaded)) if not re.search(r"\b" + n + r"\b", doc)]
+    assert not missing, f"not in INTEGRATION.md: {missing}"
+
+
 def test_abi_rejects_bad_config_without_touching_the_gpu():
     lib = _lib.load()
     import ctypes as C
