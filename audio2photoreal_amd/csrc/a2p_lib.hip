@@ -247,13 +247,15 @@ struct a2p_ctx {
   bool step_tail_done = false;         // ... and whether it did (then no step_tail_kernel launch follows)
   std::vector<Buf> ch_stream4;         // kernels_chain4.h: half-stage streams [layer*5 + kind] (CH_MID, CH_POST of the face model; empty Buf otherwise)
   std::vector<Buf> ch_stream, ch_aux;  // packed weight streams [layout * L*5 + layer*5 + kind] (layout 0: 4-wave LDS slices, 1: 8-wave; kinds: a2p_lib_run.h CH_*) / bias blocks [layer*5 + kind]
-  int ch_nw = 4;                       // waves per chain workgroup of the forward being enqueued (4 or 8; chain_pick_nw)
+  int ch_nw = 8;                       // waves per chain workgroup of the last chain forward's plan (4 or 8; chain_pick_nw): a record for a2p_debug_read
+  int32_t ch_picks[64][10];            // the ChainPick of each chain launch of the last forward, in launch order (launch_chain; a2p_debug_read "chain_picks")
+  int ch_npicks = 0;
   struct ChainTune {                   // per forward size (rows): which chain kernel family is faster ON THIS BOX, measured in situ
     int choice = 0, calls = 0;
     std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> samples;
   };
   std::map<int64_t, ChainTune> ch_tune4;   // kernels_chain.h (1) or kernels_chain4.h (4) (chain_pick_family)
-  int ch_fam_mid = 4, ch_fam_post = 4;     // chain kernel families of the forward being enqueued (MID kernels, POST kernels)
+  int ch_fam_mid = 4, ch_fam_post = 4;     // chain kernel families of the last chain forward's plan (MID kernels, POST kernels): a record for a2p_debug_read
   Buf hidden, kc, vtc, k2c, vt2c, slot_cond, slot_unc, slot_cfg;
   // separate guidance of audio and keyframes (a2p_set_guidance; body model): per-sequence slot tables of the 2B / 3B sequence passes,
   // audio + hidden [1+b | 0 | 0] and keyframes [1+b | 1+b | 0], filled for slot3_B samples by the first forward that needs them

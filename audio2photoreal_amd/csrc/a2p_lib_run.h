@@ -302,11 +302,11 @@ static int chain_build_streams(a2p_ctx* c, hipStream_t s) {
   return 0;
 }
 
-static void chain_base(a2p_ctx* c, ChainP& p, int N, int T, int idx, int aux_floats) {
+static void chain_base(a2p_ctx* c, ChainP& p, int nw, int N, int T, int idx, int aux_floats) {
   memset(&p, 0, sizeof(p));
   p.M = N * T; p.rows_per_seq = T; p.x = c->x.f(); p.cst = reinterpret_cast<const f32x4*>(c->rope_cst.p); p.cs_npos = c->rope_npos;
   p.ain = reinterpret_cast<const h16_t*>(c->ao.p); p.ld_ain = c->d;
-  p.stream = reinterpret_cast<const h16_t*>(c->ch_stream[(size_t)(c->ch_nw == 8) * c->L * CH_KINDS + idx].p);
+  p.stream = reinterpret_cast<const h16_t*>(c->ch_stream[(size_t)(nw == 8) * c->L * CH_KINDS + idx].p);
   p.stream4 = c->ch_stream4.empty() ? nullptr : reinterpret_cast<const h16_t*>(c->ch_stream4[idx].p);
   p.stream4w = (c->ch_stream4w.empty() || idx % CH_KINDS != CH_POST) ? nullptr : reinterpret_cast<const h16_t*>(c->ch_stream4w[idx / CH_KINDS].p);
   p.aux = c->ch_aux[idx].f(); p.aux_kb = (aux_floats + 255) / 256;
@@ -365,27 +365,32 @@ static int chain_pick_nw(const a2p_ctx* c) {
 // (untimed), forwards 2..9 alternate them with an event pair around the decoder stack (four samples each), forward 10 compares the
 // MINIMA (interference from other streams only ever adds time) and keeps gen 1 only if it leads by more than 1.5 %.
 // A2P_CHAIN_V=1 | 4 forces one family for both chains, 41 the mixed choice (tall MID, gen-1 POST).
-static const int kFamConfigs[2][2] = {{4, 4}, {4, 1}};
+// This is the only stateful piece of the dispatch; the pair it returns goes into the forward's plan (FwdPlan::fam).
+struct ChainFam { int mid, post; };
+static const ChainFam kFamConfigs[3] = {{4, 4}, {4, 1}, {1, 1}};
 static const int kTuneForwards4 = 10;
-static void chain_pick_family(a2p_ctx* c, int64_t rows, hipEvent_t* e0, hipEvent_t* e1) {
+// the part of the rule that needs no measurement: the pair where the switch forces it or the tall kernels cannot run, else NULL
+static const ChainFam* chain_family_fixed(const a2p_ctx* c, int nw) {
+  if (c->opt.chain_v == 1 || c->ch_stream4.empty() || c->d != 512 || nw != 8) return &kFamConfigs[2];
+  // (41: tests, A/B: what the calibration picks on the slow GPU type -- tall MID, gen-1 POST)
+  return c->opt.chain_v == 4 ? &kFamConfigs[0] : c->opt.chain_v == 41 ? &kFamConfigs[1] : nullptr;
+}
+static ChainFam chain_pick_family(a2p_ctx* c, int nw, int64_t rows, hipEvent_t* e0, hipEvent_t* e1) {
   *e0 = *e1 = nullptr;
-  auto set = [&](int cfg) { c->ch_fam_mid = kFamConfigs[cfg][0]; c->ch_fam_post = kFamConfigs[cfg][1]; };
-  if (c->opt.chain_v == 1 || c->ch_stream4.empty() || c->d != 512 || c->ch_nw != 8) { c->ch_fam_mid = c->ch_fam_post = 1; return; }
-  if (c->opt.chain_v == 4) return set(0);
-  if (c->opt.chain_v == 41) return set(1);   // (tests, A/B: what the calibration picks on the slow GPU type -- tall MID, gen-1 POST)
+  if (const ChainFam* fixed = chain_family_fixed(c, nw)) return *fixed;
   if (c->ch_tune4.size() > 64 && !c->ch_tune4.count(rows)) {   // (variable-length clips: the table stays bounded; pending event pairs are released)
     for (auto& kv : c->ch_tune4)
       for (auto& sm : kv.second.samples) { (void)hipEventDestroy(std::get<1>(sm)); (void)hipEventDestroy(std::get<2>(sm)); }
     c->ch_tune4.clear();
   }
   auto& t = c->ch_tune4[rows];
-  if (t.choice) return set(t.choice - 1);
+  if (t.choice) return kFamConfigs[t.choice - 1];
   const int call = t.calls++;
   if (call < kTuneForwards4) {
     const int cfg = call & 1;
     if (call >= 2 && hipEventCreate(e0) == hipSuccess && hipEventCreate(e1) == hipSuccess) t.samples.emplace_back(cfg, *e0, *e1);
     else *e0 = *e1 = nullptr;
-    return set(cfg);
+    return kFamConfigs[cfg];
   }
   double best_ms[2] = {1e30, 1e30};
   for (auto& sm : t.samples) {
@@ -400,207 +405,159 @@ static void chain_pick_family(a2p_ctx* c, int64_t rows, hipEvent_t* e0, hipEvent
   t.choice = best + 1;
   if (c->opt.tune_verbose)
     fprintf(stderr, "[a2p] chain kernel family of the POST chain for %lld rows (MID is tall by rule), fastest decoder stack of 4, ms: tall %.3f  gen 1 %.3f -> (%d,%d)\n",
-            (long long)rows, best_ms[0], best_ms[1], kFamConfigs[best][0], kFamConfigs[best][1]);
-  set(best);
+            (long long)rows, best_ms[0], best_ms[1], kFamConfigs[best].mid, kFamConfigs[best].post);
+  return kFamConfigs[best];
 }
 
-// Tall chain kernels (kernels_chain4.h): 64 / 80-row panels, weights straight into registers, epilogue operands from LDS.
-// Contract: face model (d = 512), MID or POST-with-successor, FiLM present, frame count a multiple of 8 and >= the panel height.
-// Rule: forwards of >= 16 sequences (B >= 8 under guidance is 16 sequences of 600 frames = 37.5 rows per CU: the 48-row panels of
-// kernels_chain.h are one round there; from 75 rows per CU on -- B = 16 -- an 80-row panel is one round where 48-row panels are two).
-// final_layer inside the last layer's POST kernel (chain4_kernel<MT, CHAIN_POST, 2>) asked for and possible: split-operand islands (the default), 256 output features.
-// The diagnostic build keeps its stamps in ChainP::fin_out.
-static bool chain4_final_ok(const a2p_ctx* c, int mode, const ChainP& p) {
+// What a forward launches is decided in two pure steps: forward_plan (below, once per forward; the family pair above is its one measured input) and chain_pick (once
+// per chain launch).  launch_chain launches exactly the pick, from one instance table, and logs it (a2p_debug_read "chain_picks").
+enum { FWD_CHAIN = 0, FWD_SMALL = 1, FWD_PER_OP = 2 };
+struct FwdPlan {
+  int path = FWD_PER_OP;
+  int N = 0, T = 0;             // sequences and frames per sequence
+  int nw = 8;                   // waves per chain workgroup (chain_pick_nw)
+  ChainFam fam = {1, 1};        // chain kernel families of the MID and POST kernels (chain_pick_family)
+  bool shared_half = false;     // classifier-free guidance: layer 0's PRE work and self attention on the first N/2 sequences only (decoder_layer_chain)
+  bool fuse_in = false;         // input_projection inside the first chain kernel (CHAIN_IN)
+  bool fuse_final16 = false;    // A2P_TAIL16: final_layer with 16-bit operands inside the last gen-1 POST kernel (ChainP::has_next == 2)
+  bool overlap_tpath = false;   // the time path on the side stream
+  bool want_output = false;     // the caller wants the MODEL OUTPUT (c->mo), not the residual stream of the last layer
+  bool single_layer = false;    // a2p_decoder_layer_forward: one layer, its own PRE kernel, no successor
+  int rule_B = 0;               // the batch the N sequences belong to, for the attention kernels' size rule (hinted_nseq; 0: N alone)
+};
+
+enum { CV_UNIFORM = 0, CV_MIX = 1,                                    // generation 1: one panel height | mixed panel heights (chain_kernel_mix)
+       CV_NEXT = 2, CV_LAST = 3, CV_LAST_FINAL = 4, CV_PAIRED_TAIL = 5 };   // tall: a kernel follows in the chain | last layer | + final_layer | + paired panels and the step tail
+enum { CS_GEN1 = 0, CS_TALL = 1, CS_TALL_WIDE = 2, CS_IN = 3 };       // weight stream: ChainP::stream as chain_base set it | stream4 | stream4w | a2p_ctx::ch_stream4_in
+struct ChainPick { int32_t family, d, mt, nw, mode, variant, grid, block, n_tall, stream; };   // one "chain_picks" record, in this order
+
+static ChainPick chain_pick(const a2p_ctx* c, const FwdPlan& f, int mode, const ChainP& p) {
+  ChainPick k = {1, c->d, c->opt.chain_mt, f.nw, mode, CV_UNIFORM, 0, 64 * f.nw, 0, CS_GEN1};
+  // Tall chain kernels (kernels_chain4.h): 64 / 80-row panels, weights straight into registers, epilogue operands from LDS.
+  // Contract: face model (d = 512), MID or POST-with-successor, FiLM present, frame count a multiple of 8 and >= the panel height.
+  // Rule: forwards of >= 16 sequences (B >= 8 under guidance is 16 sequences of 600 frames = 37.5 rows per CU: the 48-row panels of
+  // kernels_chain.h are one round there; from 75 rows per CU on -- B = 16 -- an 80-row panel is one round where 48-row panels are two).
+  // final_layer inside the last layer's POST kernel (chain4_kernel<MT, CHAIN_POST, 2>) asked for and possible: split-operand islands (the default), 256 output features.
+  // The diagnostic build keeps its stamps in ChainP::fin_out.
 #ifdef A2P_STAMPS
-  return false;
+  const bool final_ok = false;
 #else
-  return mode == CHAIN_POST && p.has_next == 0 && p.fin_x3 && c->tail_x3 && !c->pose && c->C == 256 && !c->opt.no_fused_final;
+  const bool final_ok = mode == CHAIN_POST && p.has_next == 0 && f.want_output && !f.fuse_final16 && c->tail_x3 && !c->pose && c->C == 256 && !c->opt.no_fused_final;
 #endif
-}
-static bool chain4_wanted(const a2p_ctx* c, int mode, const ChainP& p) {
-  if (c->opt.chain_v == 1 || p.stream4 == nullptr || c->d != 512 || c->ch_nw != 8) return false;
-  if (!(mode == CHAIN_MID || (mode == CHAIN_POST && p.has_next <= 1))) return false;   // (has_next == 2: final_layer fused, kernels_chain.h only)
-  if (p.film_o == nullptr || (mode == CHAIN_POST && p.film_f == nullptr)) return false;
-  if ((p.rows_per_seq & 7) || p.rows_per_seq < 80) return false;
-  // The LAST layer's POST kernel is tall whatever the calibration says about the other seven: with final_layer inside it replaces three launches and 49 MB of traffic
-  // (B=8: 53 us against 48 + 12.5 + 29), which no box type's gen-1 lead (at most ~20 % of one POST launch on the slow type) outweighs.  Same bits either way.
-  if (chain4_final_ok(c, mode, p)) return true;
-  return (mode == CHAIN_MID ? c->ch_fam_mid : c->ch_fam_post) == 4;   // the family of this forward's chain (chain_pick_family: forced, or measured on this box)
-}
-static int chain4_pick_mt(const a2p_ctx* c, int M) {
-  int mt = c->opt.chain_mt;
-  if (mt < 3 || mt > 5) {   // fewest rounds over the 256 CUs, then the shorter panel
-    int best = 1 << 30;
-    for (int m = 3; m <= 5; ++m) {
-      const int blocks = (M + 16 * m - 1) / (16 * m);
-      const int cost = ((blocks + 255) / 256) * (16 + 4 * m);
-      if (cost < best) { best = cost; mt = m; }
-    }
+  bool tall = mode == CHAIN_IN;   // (FwdPlan::fuse_in: the contract was checked by forward_plan)
+  if (!tall && c->opt.chain_v != 1 && p.stream4 && c->d == 512 && f.nw == 8 &&
+      (mode == CHAIN_MID || (mode == CHAIN_POST && p.has_next <= 1)) &&   // (has_next == 2: final_layer fused, kernels_chain.h only)
+      p.film_o && (mode != CHAIN_POST || p.film_f) && !(p.rows_per_seq & 7) && p.rows_per_seq >= 80) {
+    // The LAST layer's POST kernel is tall whatever the calibration says about the other seven: with final_layer inside it replaces three launches and 49 MB of traffic
+    // (B=8: 53 us against 48 + 12.5 + 29), which no box type's gen-1 lead (at most ~20 % of one POST launch on the slow type) outweighs.  Same bits either way.
+    tall = final_ok || (mode == CHAIN_MID ? f.fam.mid : f.fam.post) == 4;   // the family of this forward's chain (chain_pick_family: forced, or measured on this box)
   }
-  return mt;
-}
-static bool chain4_final_fused(const a2p_ctx* c, int mode, const ChainP& p) { return chain4_final_ok(c, mode, p) && chain4_wanted(c, mode, p); }
-static int launch_chain4(a2p_ctx* c, int mode, const ChainP& p0, hipStream_t s) {
-  ChainP p = p0;
-  const int mt = chain4_pick_mt(c, p.M);
-  const bool fin = chain4_final_fused(c, mode, p);
-  p.stream = (mode == CHAIN_POST && mt <= 4) ? p.stream4w : p.stream4;   // POST: the stream of the panel height's hidden-chunk width (Chain4Lds::HC)
-  const int grid = (p.M + 16 * mt - 1) / (16 * mt);
-  ++c->ch4_launches;
-  if (fin) ++c->fin_fused_launches;
-  KernelTimer kt(c, A2P_KERNEL_CHAIN, mode == CHAIN_MID ? A2P_KERNEL_CHAIN_MID : A2P_KERNEL_CHAIN_POST);
-#define A2P_CHAIN4(MT)                                                                          \
-  do {                                                                                          \
-    if (mode == CHAIN_MID) A2P_LAUNCH(kt, (chain4_kernel<MT, CHAIN_MID>), grid, 512, s, p);     \
-    else if (p.has_next) A2P_LAUNCH(kt, (chain4_kernel<MT, CHAIN_POST>), grid, 512, s, p);      \
-    else A2P_LAUNCH(kt, (chain4_kernel<MT, CHAIN_POST, 1>), grid, 512, s, p);                   \
-  } while (0)
-  if (fin && p.pair_B) {   // paired panels: one workgroup per 24 frames of a (conditional, unconditional) sequence pair
-    ARG(mt == 3, "paired panels are 48 rows");
-    ++c->tail_fused_launches;
-    A2P_LAUNCH(kt, (chain4_kernel<3, CHAIN_POST, 3>), p.pair_B * ((p.rows_per_seq + 23) / 24), 512, s, p);
-  } else if (fin) {
-    if (mt == 3) A2P_LAUNCH(kt, (chain4_kernel<3, CHAIN_POST, 2>), grid, 512, s, p);
-    else if (mt == 4) A2P_LAUNCH(kt, (chain4_kernel<4, CHAIN_POST, 2>), grid, 512, s, p);
-    else A2P_LAUNCH(kt, (chain4_kernel<5, CHAIN_POST, 2>), grid, 512, s, p);
-  } else if (mt == 3) A2P_CHAIN4(3);
-  else if (mt == 4) A2P_CHAIN4(4);
-  else A2P_CHAIN4(5);
-#undef A2P_CHAIN4
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// input_projection + layer 0's PRE work as ONE tall kernel (chain4_kernel<MT, CHAIN_IN>) instead of pack_input_split3 + gemm_kernel + the gen-1 PRE kernel.
-// Face model with split-operand islands, 256 input features, the 8-wave shape, clips of >= 80 frames (a multiple of 8), and one set of rows for the whole pass
-// (no guidance, or guidance with the shared layer-0 half).  A2P_CHAIN_V=1 keeps the gen-1 launches.
-static bool chain_in_wanted(const a2p_ctx* c, int T, bool rows_shared) {
-#ifdef A2P_STAMPS
-  return false;
-#else
-  return c->ch_stream4_in.p && c->opt.chain_v != 1 && !c->opt.no_fused_in && c->d == 512 && !c->pose && c->tail_x3 && c->C == 256 && c->ch_nw == 8 &&
-         (T & 7) == 0 && T >= 80 && rows_shared;
-#endif
-}
-static int launch_chain_in(a2p_ctx* c, const ChainP& p0, hipStream_t s) {
-  ChainP p = p0;
-  const int mt = chain4_pick_mt(c, p.M);
-  p.stream = reinterpret_cast<const h16_t*>(c->ch_stream4_in.p);
-  const int grid = (p.M + 16 * mt - 1) / (16 * mt);
-  ++c->ch4_launches;
-  ++c->in4_launches;
-  KernelTimer kt(c, A2P_KERNEL_CHAIN, A2P_KERNEL_CHAIN_PRE);
-  if (mt == 3) A2P_LAUNCH(kt, (chain4_kernel<3, CHAIN_IN>), grid, 512, s, p);
-  else if (mt == 4) A2P_LAUNCH(kt, (chain4_kernel<4, CHAIN_IN>), grid, 512, s, p);
-  else A2P_LAUNCH(kt, (chain4_kernel<5, CHAIN_IN>), grid, 512, s, p);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-static int launch_chain(a2p_ctx* c, int mode, const ChainP& p, hipStream_t s) {
-  if (chain4_wanted(c, mode, p)) return launch_chain4(c, mode, p, s);
+  auto cost = [&](int m) { return (((p.M + 16 * m - 1) / (16 * m) + 255) / 256) * (16 + 4 * m); };   // rounds of 16m-row panels over the 256 CUs x a panel's time
+  int best = 1 << 30;
+  if (tall) {
+    if (k.mt < 3 || k.mt > 5)   // fewest rounds over the 256 CUs, then the shorter panel
+      for (int m = 3; m <= 5; ++m)
+        if (cost(m) < best) { best = cost(m); k.mt = m; }
+    k.family = 4;
+    k.grid = (p.M + 16 * k.mt - 1) / (16 * k.mt);
+    k.stream = mode == CHAIN_IN ? CS_IN : (mode == CHAIN_POST && k.mt <= 4) ? CS_TALL_WIDE : CS_TALL;   // POST: the stream of the panel height's hidden-chunk width (Chain4Lds::HC)
+    k.variant = (mode != CHAIN_POST || p.has_next) ? CV_NEXT : final_ok ? CV_LAST_FINAL : CV_LAST;
+    // A guided DDPM step (a2p_sample_step) whose last POST kernel runs 48-row panels: paired panels, one workgroup per 24 frames of a (conditional, unconditional) sequence
+    // pair, the step tail in the kernel's epilogue (chain4_kernel<3, POST, 3>); the model output rows are not written at all.  Same bits as step_tail_kernel behind the
+    // kernel (A2P_FUSED_TAIL=0; tests/test_fused_step_tail_hip.py).
+    const StepP* st = c->step_tail;
+    if (k.variant == CV_LAST_FINAL && st && c->opt.fused_tail && f.N == 2 * st->B && st->Tn == p.rows_per_seq && st->C == 256 && k.mt == 3) {
+      k.variant = CV_PAIRED_TAIL;
+      k.grid = st->B * ((p.rows_per_seq + 23) / 24);
+    }
+    return k;
+  }
   const bool env_mt = c->opt.chain_mt != 0;  // tuning / test override of the panel height (rows = 16 * MT)
-  int mt = c->opt.chain_mt;
   // panel heights instantiated per width (LDS: the [16*MT][d] bf16 panel + hidden chunk + >= 3 ring slots must fit 160 KiB)
   static const int kMt512[] = {4, 3, 2}, kMt256[] = {6, 5, 4, 3, 2};
   static const int kMt512w8[] = {4, 3, 2}, kMt256w8[] = {5, 4, 3, 2};  // 8 waves: 256 registers per wave bound the panel height (d = 256, 96 rows: 46 spilled)
-  const bool w8 = c->ch_nw == 8;
+  const bool w8 = f.nw == 8;
   const int* cands = c->d == 512 ? (w8 ? kMt512w8 : kMt512) : (w8 ? kMt256w8 : kMt256);
   const int ncand = c->d == 512 ? 3 : (w8 ? 4 : 5);
   bool ok = false;
-  for (int i = 0; i < ncand; ++i) ok = ok || cands[i] == mt;
+  for (int i = 0; i < ncand; ++i) ok = ok || cands[i] == k.mt;
   if (!ok) {  // fewest rounds over the 256 CUs, then the cheaper (shorter) panel: every panel streams all weights once.
     // d = 512: the 64-row panels are left to A2P_CHAIN_MT -- their POST kernels spill (20 B / 340 B of scratch per lane with
     // 4 / 8 waves) and measure slower at every size tried (B=32: 133 vs 141 steps/s with 4 waves, 143 vs 148 with 8)
-    int best = 1 << 30;
-    for (int i = 0; i < ncand; ++i) {
-      if (c->d == 512 && cands[i] == 4) continue;
-      const int blocks = (p.M + 16 * cands[i] - 1) / (16 * cands[i]);
-      const int cost = ((blocks + 255) / 256) * (16 + 4 * cands[i]);
-      if (cost < best) { best = cost; mt = cands[i]; }
-    }
+    for (int i = 0; i < ncand; ++i)
+      if (!(c->d == 512 && cands[i] == 4) && cost(cands[i]) < best) { best = cost(cands[i]); k.mt = cands[i]; }
   }
-  const int grid = (p.M + 16 * mt - 1) / (16 * mt);
-  KernelTimer kt(c, A2P_KERNEL_CHAIN, mode == CHAIN_PRE ? A2P_KERNEL_CHAIN_PRE : mode == CHAIN_MID ? A2P_KERNEL_CHAIN_MID
-                                       : mode == CHAIN_POST ? A2P_KERNEL_CHAIN_POST : A2P_KERNEL_CHAIN_MIDPOST);
+  k.grid = (p.M + 16 * k.mt - 1) / (16 * k.mt);
   // d = 512, more than one round of 48-row panels with a mostly empty last round: 64-row panels for the first n_tall
   // workgroups so that the forward fits one round less (chain_kernel_mix; B=32: 96 x 64 + 672 x 48 rows = 3 full rounds
   // instead of 3.125 -> 4).  A2P_CHAIN_NO_MIX=1 keeps the uniform launch for A/B runs.
   // Only for the 8-wave shape: 64-row panels of 512-register waves live half in AGPRs and run 1.6-1.9x the 48-row time
   // (scratch/chain_bench, POST: 143 vs 89 us), with 8 waves 1.26-1.37x (102 vs 75 us) for 1.33x the rows.
-  if (w8 && c->d == 512 && mt == 3 && !env_mt && grid > 256 && grid % 256 != 0 && !c->opt.chain_no_mix) {
-    const int W = 256 * ((grid + 255) / 256 - 1);
+  if (w8 && c->d == 512 && k.mt == 3 && !env_mt && k.grid > 256 && k.grid % 256 != 0 && !c->opt.chain_no_mix) {
+    const int W = 256 * ((k.grid + 255) / 256 - 1);
     const int n_tall = (p.M - 48 * W + 15) / 16;
-    if (n_tall > 0 && n_tall <= W) {
-      ChainP q = p;
-      q.n_tall = n_tall;
-#define A2P_CHAIN_MIX(NW)                                                                                              \
-  do {                                                                                                                 \
-    if (mode == CHAIN_PRE) A2P_LAUNCH(kt, (chain_kernel_mix<512, 4, 3, CHAIN_PRE, NW>), W, 64 * NW, s, q);              \
-    else if (mode == CHAIN_MID) A2P_LAUNCH(kt, (chain_kernel_mix<512, 4, 3, CHAIN_MID, NW>), W, 64 * NW, s, q);         \
-    else A2P_LAUNCH(kt, (chain_kernel_mix<512, 4, 3, CHAIN_POST, NW>), W, 64 * NW, s, q);                               \
-  } while (0)
-      A2P_CHAIN_MIX(8);
-#undef A2P_CHAIN_MIX
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
+    if (n_tall > 0 && n_tall <= W) { k.variant = CV_MIX; k.grid = W; k.n_tall = n_tall; }
   }
+  return k;
+}
+
+// Every chain kernel instance of the library, by the pick that launches it.  (Diagnostic build: the gen-1 kernels carry the stamp ablation argument.)
+using ChainKernel = void (*)(ChainP);
+struct ChainInst { ChainPick key; ChainKernel fn; };   // key: family, d, mt, nw, mode, variant
+template <int FAM, int D, int MT, int NW, int MODE, int VAR>
+static constexpr ChainKernel chain_instance() {
 #ifdef A2P_STAMPS
-#define A2P_CHAIN_ABL 64
+  constexpr int ABL = 64;
 #else
-#define A2P_CHAIN_ABL 0
+  constexpr int ABL = 0;
 #endif
-#define A2P_CHAIN_W(D, MT, NW)                                                                                              \
-  do {                                                                                                                      \
-    if (mode == CHAIN_PRE) A2P_LAUNCH(kt, (chain_kernel<D, MT, CHAIN_PRE, A2P_CHAIN_ABL, NW>), grid, 64 * NW, s, p);        \
-    else if (mode == CHAIN_MID) A2P_LAUNCH(kt, (chain_kernel<D, MT, CHAIN_MID, A2P_CHAIN_ABL, NW>), grid, 64 * NW, s, p);   \
-    else A2P_LAUNCH(kt, (chain_kernel<D, MT, CHAIN_POST, A2P_CHAIN_ABL, NW>), grid, 64 * NW, s, p);                         \
-  } while (0)
-#define A2P_CHAIN(D, MT) A2P_CHAIN_W(D, MT, 4)
-  if (mode == CHAIN_MIDPOST) {   // body model only (d = 256): MID2 | keyframe attention | POST in one kernel
-    ARG(c->d == 256, "CHAIN_MIDPOST is instantiated for d = 256");
-#define A2P_CHAIN_MP(MT, NW) A2P_LAUNCH(kt, (chain_kernel<256, MT, CHAIN_MIDPOST, A2P_CHAIN_ABL, NW>), grid, 64 * NW, s, p)
-    if (w8) {
-      if (mt == 2) A2P_CHAIN_MP(2, 8);
-      else if (mt == 3) A2P_CHAIN_MP(3, 8);
-      else if (mt == 4) A2P_CHAIN_MP(4, 8);
-      else A2P_CHAIN_MP(5, 8);
-    } else {
-      if (mt == 2) A2P_CHAIN_MP(2, 4);
-      else if (mt == 3) A2P_CHAIN_MP(3, 4);
-      else if (mt == 4) A2P_CHAIN_MP(4, 4);
-      else if (mt == 5) A2P_CHAIN_MP(5, 4);
-      else A2P_CHAIN_MP(6, 4);
-    }
-#undef A2P_CHAIN_MP
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if (w8) {
-    if (c->d == 512) {
-      if (mt == 2) A2P_CHAIN_W(512, 2, 8);
-      else if (mt == 3) A2P_CHAIN_W(512, 3, 8);
-      else A2P_CHAIN_W(512, 4, 8);
-    } else {
-      if (mt == 2) A2P_CHAIN_W(256, 2, 8);
-      else if (mt == 3) A2P_CHAIN_W(256, 3, 8);
-      else if (mt == 4) A2P_CHAIN_W(256, 4, 8);
-      else A2P_CHAIN_W(256, 5, 8);
-    }
-  } else if (c->d == 512) {
-    if (mt == 2) A2P_CHAIN(512, 2);
-    else if (mt == 3) A2P_CHAIN(512, 3);
-    else A2P_CHAIN(512, 4);
-  } else {
-    if (mt == 2) A2P_CHAIN(256, 2);
-    else if (mt == 3) A2P_CHAIN(256, 3);
-    else if (mt == 4) A2P_CHAIN(256, 4);
-    else if (mt == 5) A2P_CHAIN(256, 5);
-    else A2P_CHAIN(256, 6);
-  }
-#undef A2P_CHAIN
-#undef A2P_CHAIN_W
+  if constexpr (FAM == 4) return chain4_kernel<MT, MODE, VAR - CV_NEXT>;
+  else if constexpr (VAR == CV_MIX) return chain_kernel_mix<D, 4, MT, MODE, NW>;   // 64-row panels first, then MT
+  else return chain_kernel<D, MT, MODE, ABL, NW>;
+}
+#define CI(FAM, D, MT, NW, MODE, VAR) {{FAM, D, MT, NW, CHAIN_##MODE, CV_##VAR, 0, 0, 0, 0}, chain_instance<FAM, D, MT, NW, CHAIN_##MODE, CV_##VAR>()}
+static const ChainInst kChainInst[] = {
+  // generation 1, 8 waves: d = 512 (with the mixed launch of 64- and 48-row panels), d = 256
+  CI(1, 512, 2, 8, PRE, UNIFORM), CI(1, 512, 2, 8, MID, UNIFORM), CI(1, 512, 2, 8, POST, UNIFORM), CI(1, 512, 3, 8, PRE, UNIFORM), CI(1, 512, 3, 8, MID, UNIFORM),
+  CI(1, 512, 3, 8, POST, UNIFORM), CI(1, 512, 4, 8, PRE, UNIFORM), CI(1, 512, 4, 8, MID, UNIFORM), CI(1, 512, 4, 8, POST, UNIFORM),
+  CI(1, 512, 3, 8, PRE, MIX), CI(1, 512, 3, 8, MID, MIX), CI(1, 512, 3, 8, POST, MIX),
+  CI(1, 256, 2, 8, PRE, UNIFORM), CI(1, 256, 2, 8, MID, UNIFORM), CI(1, 256, 2, 8, POST, UNIFORM), CI(1, 256, 3, 8, PRE, UNIFORM), CI(1, 256, 3, 8, MID, UNIFORM),
+  CI(1, 256, 3, 8, POST, UNIFORM), CI(1, 256, 4, 8, PRE, UNIFORM), CI(1, 256, 4, 8, MID, UNIFORM), CI(1, 256, 4, 8, POST, UNIFORM), CI(1, 256, 5, 8, PRE, UNIFORM),
+  CI(1, 256, 5, 8, MID, UNIFORM), CI(1, 256, 5, 8, POST, UNIFORM),
+  // generation 1, 4 waves
+  CI(1, 512, 2, 4, PRE, UNIFORM), CI(1, 512, 2, 4, MID, UNIFORM), CI(1, 512, 2, 4, POST, UNIFORM), CI(1, 512, 3, 4, PRE, UNIFORM), CI(1, 512, 3, 4, MID, UNIFORM),
+  CI(1, 512, 3, 4, POST, UNIFORM), CI(1, 512, 4, 4, PRE, UNIFORM), CI(1, 512, 4, 4, MID, UNIFORM), CI(1, 512, 4, 4, POST, UNIFORM),
+  CI(1, 256, 2, 4, PRE, UNIFORM), CI(1, 256, 2, 4, MID, UNIFORM), CI(1, 256, 2, 4, POST, UNIFORM), CI(1, 256, 3, 4, PRE, UNIFORM), CI(1, 256, 3, 4, MID, UNIFORM),
+  CI(1, 256, 3, 4, POST, UNIFORM), CI(1, 256, 4, 4, PRE, UNIFORM), CI(1, 256, 4, 4, MID, UNIFORM), CI(1, 256, 4, 4, POST, UNIFORM), CI(1, 256, 5, 4, PRE, UNIFORM),
+  CI(1, 256, 5, 4, MID, UNIFORM), CI(1, 256, 5, 4, POST, UNIFORM), CI(1, 256, 6, 4, PRE, UNIFORM), CI(1, 256, 6, 4, MID, UNIFORM), CI(1, 256, 6, 4, POST, UNIFORM),
+  // body model only (d = 256): MID2 | keyframe attention | POST in one kernel
+  CI(1, 256, 2, 8, MIDPOST, UNIFORM), CI(1, 256, 3, 8, MIDPOST, UNIFORM), CI(1, 256, 4, 8, MIDPOST, UNIFORM), CI(1, 256, 5, 8, MIDPOST, UNIFORM),
+  CI(1, 256, 2, 4, MIDPOST, UNIFORM), CI(1, 256, 3, 4, MIDPOST, UNIFORM), CI(1, 256, 4, 4, MIDPOST, UNIFORM), CI(1, 256, 5, 4, MIDPOST, UNIFORM), CI(1, 256, 6, 4, MIDPOST, UNIFORM),
+  // tall (face model, 8 waves); paired panels are 48 rows
+  CI(4, 512, 3, 8, IN, NEXT), CI(4, 512, 3, 8, MID, NEXT), CI(4, 512, 3, 8, POST, NEXT), CI(4, 512, 3, 8, POST, LAST), CI(4, 512, 3, 8, POST, LAST_FINAL),
+  CI(4, 512, 3, 8, POST, PAIRED_TAIL),
+  CI(4, 512, 4, 8, IN, NEXT), CI(4, 512, 4, 8, MID, NEXT), CI(4, 512, 4, 8, POST, NEXT), CI(4, 512, 4, 8, POST, LAST), CI(4, 512, 4, 8, POST, LAST_FINAL),
+  CI(4, 512, 5, 8, IN, NEXT), CI(4, 512, 5, 8, MID, NEXT), CI(4, 512, 5, 8, POST, NEXT), CI(4, 512, 5, 8, POST, LAST), CI(4, 512, 5, 8, POST, LAST_FINAL),
+};
+#undef CI
+
+static int launch_chain(a2p_ctx* c, const ChainPick& k, const ChainP& p0, hipStream_t s) {
+  const ChainInst* inst = nullptr;
+  for (const ChainInst& i : kChainInst)
+    if (i.key.family == k.family && i.key.d == k.d && i.key.mt == k.mt && i.key.nw == k.nw && i.key.mode == k.mode && i.key.variant == k.variant) { inst = &i; break; }
+  ARG(inst, "chain: no kernel instance for family=%d d=%d mt=%d nw=%d mode=%d variant=%d", k.family, k.d, k.mt, k.nw, k.mode, k.variant);
+  ChainP p = p0;
+  p.n_tall = k.n_tall;
+  if (k.stream != CS_GEN1) p.stream = k.stream == CS_IN ? reinterpret_cast<const h16_t*>(c->ch_stream4_in.p) : k.stream == CS_TALL_WIDE ? p.stream4w : p.stream4;
+  if (k.family == 4) ++c->ch4_launches;
+  if (k.mode == CHAIN_IN) ++c->in4_launches;
+  if (k.variant == CV_LAST_FINAL || k.variant == CV_PAIRED_TAIL) ++c->fin_fused_launches;
+  if (k.variant == CV_PAIRED_TAIL) ++c->tail_fused_launches;
+  static_assert(sizeof(ChainPick) == sizeof(c->ch_picks[0]), "a chain_picks record is one ChainPick");
+  if (c->ch_npicks < 64) memcpy(c->ch_picks[c->ch_npicks++], &k, sizeof(k));
+  KernelTimer kt(c, A2P_KERNEL_CHAIN, k.mode == CHAIN_MID ? A2P_KERNEL_CHAIN_MID : k.mode == CHAIN_POST ? A2P_KERNEL_CHAIN_POST
+                                       : k.mode == CHAIN_MIDPOST ? A2P_KERNEL_CHAIN_MIDPOST : A2P_KERNEL_CHAIN_PRE);
+  A2P_LAUNCH(kt, inst->fn, k.grid, k.block, s, p);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -638,11 +595,12 @@ static int launch_cross_attention(a2p_ctx* c, int N, int T, const CrossKV& kv, h
 // shared_half: classifier-free guidance, layer 0 -- both halves of the 2B sequences start from the same x (one input
 // projection) and therefore share norm1 / Q,K,V / the self attention: those run on the first N/2 sequences only, and the MID
 // kernel of the second half reads the first half's rows (ChainP::src_rows)
-// rule_B: the batch the N sequences belong to, for the attention kernels' size rule (hinted_nseq; 0: N alone) -- also below
-static int decoder_layer_chain(a2p_ctx* c, int l, int N, int T, const CrossKV& kv, const CrossKV* kv2, const FilmRef& fr, bool first,
-                               bool has_next, hipStream_t s, hipEvent_t film_ready = nullptr, bool fuse_final = false,
-                               bool shared_half = false, bool* fused_x3 = nullptr, const float* x_in_fused = nullptr, int rule_B = 0) {
-  const int d = c->d;
+// x_in: the forward's input, read by layer 0 of a plan with fuse_in.  Returns 1 where the last POST kernel computed final_layer too (the model output is in c->mo and c->x
+// is NOT updated), 0 otherwise, < 0 on error.
+static int decoder_layer_chain(a2p_ctx* c, const FwdPlan& f, int l, const float* x_in, const CrossKV& kv, const CrossKV* kv2, const FilmRef& fr, hipStream_t s) {
+  const int d = c->d, N = f.N, T = f.T, rule_B = f.rule_B;
+  const bool first = f.single_layer || l == 0, has_next = !f.single_layer && l + 1 < c->L, shared_half = f.shared_half && l == 0;
+  const hipEvent_t film_ready = (f.overlap_tpath && l == 0) ? c->ev_join : nullptr;
   const std::string pf = "seqTransDecoder.stack." + std::to_string(l) + ".";
   ChainP p;
   const int join_at = c->opt.side_join;  // diagnostic: where the main stream joins the side stream (1 PRE, 2 self attention, default MID)
@@ -654,23 +612,21 @@ static int decoder_layer_chain(a2p_ctx* c, int l, int N, int T, const CrossKV& k
   // second-half workgroup may start after the first-half workgroup of the same source rows has stored its result
   float* x0 = shared_half ? c->hff.f() : nullptr;
   if (first) {
-    chain_base(c, p, Nsa, T, ch_index(l, CH_PRE), 3 * d);
+    chain_base(c, p, f.nw, Nsa, T, ch_index(l, CH_PRE), 3 * d);
     chain_set_pre(c, p, l, T);
     if (x0) p.x = x0;
-    if (x_in_fused) {   // input_projection inside the kernel: the rows it computes are stored (row-major) where the GEMM left them
-      p.xin = x_in_fused; p.xin_C = c->C;
+    if (f.fuse_in) {   // input_projection inside the kernel: the rows it computes are stored (row-major) where the GEMM left them
+      p.xin = x_in; p.xin_C = c->C;
       p.aux = c->ch_aux_in.f(); p.aux_kb = 10;
       p.x_in_tiled = 0; p.x_out_tiled = 0;
-      CHK(launch_chain_in(c, p, s));
-    } else {
-      CHK(launch_chain(c, CHAIN_PRE, p, s));
     }
+    CHK(launch_chain(c, chain_pick(c, f, f.fuse_in ? CHAIN_IN : CHAIN_PRE, p), p, s));
   }
   if (film_ready && join_at == 2) HIPCHK(hipStreamWaitEvent(s, film_ready, 0));
   CHK(launch_self_attention(c, Nsa, T, s, false, hinted_nseq(c, Nsa, rule_B)));
   if (film_ready && join_at >= 3) HIPCHK(hipStreamWaitEvent(s, film_ready, 0));  // FiLM / time-token K,V of this step (side stream)
   auto mid = [&](int kind, const std::string& attn_done, int film_idx, const std::string& norm) -> int {
-    chain_base(c, p, N, T, ch_index(l, kind), d);
+    chain_base(c, p, f.nw, N, T, ch_index(l, kind), d);
     chain_set_out_proj(c, p, pf + attn_done, fr, film_idx);
     p.lnA_g = W32(c, pf + norm + ".weight"); p.lnA_b = W32(c, pf + norm + ".bias");
     p.q_out = reinterpret_cast<h16_t*>(c->qk.p); p.ld_q = d;
@@ -682,7 +638,7 @@ static int decoder_layer_chain(a2p_ctx* c, int l, int N, int T, const CrossKV& k
     // touches the rows, tiled between chain kernels
     p.x_in_tiled = !(first && kind == CH_MID) && tiled;
     p.x_out_tiled = tiled;
-    return launch_chain(c, CHAIN_MID, p, s);
+    return launch_chain(c, chain_pick(c, f, CHAIN_MID, p), p, s);
   };
   CHK(mid(CH_MID, "self_attn", 0, "norm2"));
   CHK(launch_cross_attention(c, N, T, kv, s, false, hinted_nseq(c, N, rule_B)));
@@ -692,12 +648,12 @@ static int decoder_layer_chain(a2p_ctx* c, int l, int N, int T, const CrossKV& k
   // 32-wide heads.  Any other head geometry at d = 256 (the reference's argparse default is --heads 4, i.e. head_dim 64) takes the
   // three launches.  A 16-row tile of the panel may straddle TWO sequences (the kernel keeps both key sets), not three: T >= 16.
   const bool fuse_kf = kv2 && d == 256 && c->H == 8 && c->DH == 32 && T >= 16 && kv2->S_main >= 1 && kv2->S_main <= 32 &&
-                       kv2->S_tail == 0 && !c->opt.no_fused_kf && !fuse_final;
+                       kv2->S_tail == 0 && !c->opt.no_fused_kf && !f.fuse_final16;
   if (kv2 && !fuse_kf) {
     CHK(mid(CH_MID2, "multihead_attn", 1, "norm2a"));
     CHK(launch_cross_attention(c, N, T, *kv2, s, false, hinted_nseq(c, N, rule_B)));
   }
-  chain_base(c, p, N, T, ch_index(l, fuse_kf ? CH_MIDPOST : CH_POST), c->ff + (has_next ? 3 * d : 0));
+  chain_base(c, p, f.nw, N, T, ch_index(l, fuse_kf ? CH_MIDPOST : CH_POST), c->ff + (has_next ? 3 * d : 0));
   if (fuse_kf) {
     chain_set_out_proj(c, p, pf + "multihead_attn", fr, 1);                                      // first sublayer: the audio cross attention's output
     p.lnA_g = W32(c, pf + "norm2a.weight"); p.lnA_b = W32(c, pf + "norm2a.bias");
@@ -720,27 +676,24 @@ static int decoder_layer_chain(a2p_ctx* c, int l, int N, int T, const CrossKV& k
   p.x_in_tiled = tiled;
   p.x_out_tiled = tiled && has_next;   // the last layer's rows go back to the caller / the pose tail row-major
   if (has_next) chain_set_pre(c, p, l + 1, T);
-  if (!has_next && fuse_final) {  // model output rows straight from the last POST kernel (c->x is NOT updated)
-    p.has_next = 2; p.fin_out = c->mo.f(); p.ld_fin = c->C; p.fin_n = c->C;
+  const bool fuse_final16 = !has_next && f.fuse_final16;   // model output rows straight from the last gen-1 POST kernel (c->x is NOT updated)
+  if (fuse_final16) p.has_next = 2;
+  const ChainPick k = chain_pick(c, f, fuse_kf ? CHAIN_MIDPOST : CHAIN_POST, p);
+  const bool fused_x3 = k.variant == CV_LAST_FINAL || k.variant == CV_PAIRED_TAIL;   // the tall last-layer kernel computes final_layer too (c->x is NOT updated then)
+  p.fin_x3 = fused_x3;
+  if (fuse_final16 || fused_x3) {
+    p.fin_out = c->mo.f(); p.ld_fin = c->C; p.fin_n = c->C;
     p.aux_kb = (c->ff + c->C + 255) / 256;
   }
-  if (!has_next && fused_x3 && !fuse_kf && !fuse_final) {   // the caller wants the MODEL OUTPUT: the tall last-layer kernel computes final_layer too where it can (c->x is NOT updated then)
-    float* const fin_out0 = p.fin_out;   // (the diagnostic build keeps its stamp slots there)
-    p.fin_x3 = 1; p.fin_out = c->mo.f(); p.ld_fin = c->C; p.fin_n = c->C;
-    p.aux_kb = (c->ff + c->C + 255) / 256;
-    *fused_x3 = chain4_final_fused(c, CHAIN_POST, p);
-    if (!*fused_x3) { p.fin_x3 = 0; p.fin_out = fin_out0; p.aux_kb = (c->ff + 255) / 256; }
-    // A guided DDPM step (a2p_sample_step) whose last POST kernel runs 48-row panels: paired panels, the step tail in the kernel's epilogue (chain4_kernel<3, POST, 3>);
-    // the model output rows are not written at all.  Same bits as step_tail_kernel behind the kernel (A2P_FUSED_TAIL=0; tests/test_fused_step_tail_hip.py).
+  if (k.variant == CV_PAIRED_TAIL) {   // (chain_pick: a2p_sample_step's guided DDPM tail rides in the kernel's epilogue)
     const StepP* st = c->step_tail;
-    if (*fused_x3 && st && c->opt.fused_tail && N == 2 * st->B && st->Tn == T && st->C == 256 && chain4_pick_mt(c, p.M) == 3) {
-      p.pair_B = st->B;
-      p.tl_clip = st->clip; p.tl_nsteps = st->n_steps; p.tl_scale = st->scale; p.tl_t = st->t_idx; p.tl_tables = st->tables;
-      p.tl_x = st->x; p.tl_noise = st->noise; p.tl_xnext = st->x_next; p.tl_x0 = st->x0; p.tl_nonfinite = st->nonfinite;
-      c->step_tail_done = true;
-    }
+    p.pair_B = st->B;
+    p.tl_clip = st->clip; p.tl_nsteps = st->n_steps; p.tl_scale = st->scale; p.tl_t = st->t_idx; p.tl_tables = st->tables;
+    p.tl_x = st->x; p.tl_noise = st->noise; p.tl_xnext = st->x_next; p.tl_x0 = st->x0; p.tl_nonfinite = st->nonfinite;
+    c->step_tail_done = true;
   }
-  return launch_chain(c, fuse_kf ? CHAIN_MIDPOST : CHAIN_POST, p, s);
+  CHK(launch_chain(c, k, p, s));
+  return (fuse_final16 || fused_x3) ? 1 : 0;
 }
 
 // FiLMTransformerDecoderLayer.forward (transformer_modules.py:178-217) on c->x
@@ -994,17 +947,24 @@ static int pose_conv_tail(a2p_ctx* c, int N, int T, hipStream_t s) {
   return launch_gemm(c, pf, s);
 }
 
-// FiLMTransformer.forward for N sequences; result rows in c->mo ([N][mo_rows][C] fp32)
-static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, int pass, int* mo_seq_rows, hipStream_t s, bool use_chain,
-                        bool use_small) {
-  const int d = c->d, B = c->pB, T = c->pT, L = c->L, F = c->F;
-  const int N = pass_nseq(pass, B);
-  c->clk_turn = 0;
-  // audio K/V and pooled-hidden slot of every sequence; the keyframe K/V follow it except in the passes that drop the two separately
-  const int* slots = (const int*)(pass == A2P_PASS_CFG_DUAL ? c->slot_a3.p
-                                  : (pass == A2P_PASS_CFG || pass == A2P_PASS_CFG_AUDIO) ? c->slot_cfg.p
-                                  : pass == A2P_PASS_COND ? c->slot_cond.p : c->slot_unc.p);
-  const int* slots_kf = (const int*)(pass == A2P_PASS_KEYS ? c->slot_cond.p : (pass_split(pass) ? c->slot_kf3.p : (const void*)slots));
+// What a forward of `pass` over the prepared batch takes: pure, everything but the measured family pair (FwdPlan::fam, filled in by run_forward)
+static FwdPlan forward_plan(const a2p_ctx* c, int pass) {
+  const int B = c->pB, T = c->pT;
+  FwdPlan f;
+  f.N = pass_nseq(pass, B); f.T = T; f.rule_B = B; f.want_output = true;
+  // Row panels pay off once there are enough of them: every workgroup streams the whole weight set of its chain, so a
+  // forward of < ~1000 rows (config 0: B=1, T=240 -> 480 rows = 10 panels) is faster as many small 2-D tiles
+  // (measured: 0.99 vs 1.10 ms per step at 480 rows, equal at 1200, chain ahead from 2400 rows on).
+  // The kernel family is chosen from the row count of the UNSHARDED batch when the host names it (a2p_set_batch_hint;
+  // sample_parallel does): the families differ in rounding, and a sharded run must reproduce the single-process samples bit for bit
+  const int64_t rows_eff = (int64_t)(c->batch_hint > B ? (f.N / B) * c->batch_hint : f.N) * T;
+  // (the 1100-row break-even was measured against the small-forward kernels, which exist for the face model only: a context
+  // without them -- the body model, d != 512 -- keeps the round-2 threshold of 960 rows against the per-op kernels)
+  const int64_t chain_thr = small_supported(c) ? c->opt.chain_rows : (c->opt.chain_rows < 960 ? c->opt.chain_rows : 960);
+  const bool use_chain = chain_supported(c) && (rows_eff >= chain_thr || c->opt.chain_mt);
+  f.path = use_chain ? FWD_CHAIN : small_supported(c) ? FWD_SMALL : FWD_PER_OP;
+  if (!use_chain) return f;
+  f.nw = chain_pick_nw(c);
   // The time path (7 latency-bound launches, ~70 us at B=8) is not needed before the first out_proj epilogue and can run on
   // the side stream next to input projection / norm1+QKV / self attention of layer 0 (-2..3 % step time).  On by default since
   // round 2 (A2P_NO_SIDE_STREAM=1 turns it off): in round 1, with the two queues active, 1-30 % of forwards on some boxes
@@ -1013,8 +973,33 @@ static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, in
   // trajectories in both 16-bit modes in round 2 (scratch/side_stress.py).
   // (the small path keeps the time path on the main stream: on the side stream it measured 1430 against 1497 steps/s at 480 rows --
   // the fork / join costs more than the 7 launches it hides)
-  const bool overlap_tpath = use_chain && !c->opt.no_side_stream;
-  if (overlap_tpath) {
+  f.overlap_tpath = !c->opt.no_side_stream;
+  f.shared_half = f.N == 2 * B && !c->opt.no_shared_half;
+  f.fuse_final16 = !c->pose && !c->tail32;
+  // input_projection + layer 0's PRE work as ONE tall kernel (chain4_kernel<MT, CHAIN_IN>) instead of pack_input_split3 + gemm_kernel + the gen-1 PRE kernel.
+  // Face model with split-operand islands, 256 input features, the 8-wave shape, clips of >= 80 frames (a multiple of 8), and one set of rows for the whole pass
+  // (no guidance, or guidance with the shared layer-0 half).  A2P_CHAIN_V=1 keeps the gen-1 launches.
+#ifndef A2P_STAMPS
+  f.fuse_in = c->ch_stream4_in.p && c->opt.chain_v != 1 && !c->opt.no_fused_in && c->d == 512 && !c->pose && c->tail_x3 && c->C == 256 && f.nw == 8 &&
+              (T & 7) == 0 && T >= 80 && (f.N == B || f.shared_half);
+#endif
+  return f;
+}
+
+// FiLMTransformer.forward for the plan's N sequences; result rows in c->mo ([N][mo_rows][C] fp32)
+// tune0 / tune1: the family calibration's event pair around the decoder stack (chain_pick_family; NULL: an untimed forward)
+static int forward_body(a2p_ctx* c, const FwdPlan& f, const float* x_in, const int64_t* t_orig, int pass, int* mo_seq_rows, hipStream_t s,
+                        hipEvent_t tune0, hipEvent_t tune1) {
+  const int d = c->d, B = c->pB, T = f.T, L = c->L, F = c->F, N = f.N;
+  const bool use_chain = f.path == FWD_CHAIN;
+  c->clk_turn = 0;
+  c->ch_npicks = 0;
+  // audio K/V and pooled-hidden slot of every sequence; the keyframe K/V follow it except in the passes that drop the two separately
+  const int* slots = (const int*)(pass == A2P_PASS_CFG_DUAL ? c->slot_a3.p
+                                  : (pass == A2P_PASS_CFG || pass == A2P_PASS_CFG_AUDIO) ? c->slot_cfg.p
+                                  : pass == A2P_PASS_COND ? c->slot_cond.p : c->slot_unc.p);
+  const int* slots_kf = (const int*)(pass == A2P_PASS_KEYS ? c->slot_cond.p : (pass_split(pass) ? c->slot_kf3.p : (const void*)slots));
+  if (f.overlap_tpath) {   // the time path on the side stream (forward_plan)
     c->ev_fork = c->ev_fork_pool[c->ev_turn & 7];
     c->ev_join = c->ev_join_pool[c->ev_turn & 7];
     ++c->ev_turn;
@@ -1026,29 +1011,22 @@ static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, in
   } else {
     CHK(time_path(c, t_orig, N, slots, s));
   }
-  hipEvent_t tune0 = nullptr, tune1 = nullptr;
-  if (use_chain) {   // (in front of the input projection: chain_in_wanted needs the workgroup shape; the calibration's timed region now includes the projection)
-    c->ch_nw = chain_pick_nw(c);
-    chain_pick_family(c, (int64_t)N * T, &tune0, &tune1);
-    if (tune0) HIPCHK(hipEventRecord(tune0, s));
-  }
+  if (tune0) HIPCHK(hipEventRecord(tune0, s));   // (in front of the input projection: the calibration's timed region includes it)
   // input permute + projection (model/diffusion.py:345-346,364); exact fp32 in every mode (a2p_ctx::tail32).
   // Chain forwards of the face model: inside the first chain kernel (chain4_kernel<MT, CHAIN_IN>: decoder_layer_chain), nothing to launch here.
-  const bool fuse_in = use_chain && chain_in_wanted(c, T, N == B || (N == 2 * B && !c->opt.no_shared_half));
-  if (!fuse_in) {
+  if (!f.fuse_in) {
     Fp32Scope f32(c, c->tail32 && !c->tail_x3);
     dim3 grid((T + 31) / 32, (c->Cpad + 31) / 32, B);
     const int X = c->tail_x3 ? 3 : 1;
     if (c->tail_x3) pack_input_split3_kernel<<<grid, 256, 0, s>>>(x_in, (h16_t*)c->inpack.p, B, c->C, T, c->Cpad);
     else if (c->bf16) pack_input_kernel<h16_t><<<grid, 256, 0, s>>>(x_in, (h16_t*)c->inpack.p, B, c->C, T, c->Cpad);
     else pack_input_kernel<float><<<grid, 256, 0, s>>>(x_in, (float*)c->inpack.p, B, c->C, T, c->Cpad);
-    const bool shared_half = use_chain && N == 2 * B && !c->opt.no_shared_half;
     GemmP p = gemm_base(c->inpack.p, X * c->Cpad, c->wt.at("input_projection.weight").p, X * c->Cpad, W32(c, "input_projection.bias"),
-                        shared_half ? c->hff.p : c->x.p, d, B * T, d, X * c->Cpad);
+                        f.shared_half ? c->hff.p : c->x.p, d, B * T, d, X * c->Cpad);
     p.out_f32 = c->bf16 ? 1 : 0;   // gemm_kernel<float> stores fp32 either way; the flag only selects a 16-bit kernel instance
     // guidance without the shared layer-0 half (per-op and small-forward paths): the second half's copy of the rows is written by
     // the same epilogue (16-bit modes: the fp32-output store) instead of a copy kernel behind the GEMM
-    const bool dup = N >= 2 * B && !shared_half;
+    const bool dup = N >= 2 * B && !f.shared_half;
     const bool dup_in_epilogue = dup && c->bf16;
     if (dup_in_epilogue) p.dup_off = (int64_t)B * T * d;
     CHK(launch_gemm(c, p, s));
@@ -1064,7 +1042,7 @@ static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, in
     }
   }
   CrossKV kv, kv2;
-  bool fused_x3 = false;
+  int final_done = 0;   // decoder_layer_chain: the last POST kernel computed final_layer too
   for (int l = 0; l < L; ++l) {
     kv.K = c->offT(c->kc, (int64_t)l * d); kv.k_slot_stride = (int64_t)c->Sld * L * d; kv.ldk = (int64_t)L * d;
     kv.VT = c->offT(c->vtc, (int64_t)l * d * c->Sld); kv.vt_slot_stride = (int64_t)L * d * c->Sld; kv.ldvt = c->Sld;
@@ -1082,17 +1060,16 @@ static int forward_body(a2p_ctx* c, const float* x_in, const int64_t* t_orig, in
     FilmRef fr;
     fr.base = c->film.f() + (size_t)l * F * 2 * d;
     fr.seq_stride = (int64_t)L * F * 2 * d;
-    if (use_chain)
-      CHK(decoder_layer_chain(c, l, N, T, kv, c->pose ? &kv2 : nullptr, fr, l == 0, l + 1 < L, s, (overlap_tpath && l == 0) ? c->ev_join : nullptr,
-                              /*fuse_final=*/!c->pose && !c->tail32, /*shared_half=*/l == 0 && N == 2 * B && !c->opt.no_shared_half, &fused_x3, (l == 0 && fuse_in) ? x_in : nullptr,
-                              /*rule_B=*/B));
-    else if (use_small) CHK(decoder_layer_small(c, l, N, T, kv, fr, s, (overlap_tpath && l == 0) ? c->ev_join : nullptr, B));
+    if (use_chain) {
+      final_done = decoder_layer_chain(c, f, l, x_in, kv, c->pose ? &kv2 : nullptr, fr, s);
+      CHK(final_done);
+    } else if (f.path == FWD_SMALL) CHK(decoder_layer_small(c, l, N, T, kv, fr, s, nullptr, B));
     else CHK(decoder_layer(c, l, N, T, kv, c->pose ? &kv2 : nullptr, fr, s, B));
   }
   // (the family calibration times the decoder stack INCLUDING final_layer: the tall last-layer kernel may contain it)
   struct TuneEnd { hipEvent_t e; hipStream_t s; ~TuneEnd() { if (e) (void)hipEventRecord(e, s); } } tune_end{tune1, s};
   // final_layer (model/diffusion.py:397)   (A2P_TAIL16 + face + chain mode, or the tall last-layer kernel's split-operand island: already done by the last POST kernel)
-  if (use_chain && !c->pose && (!c->tail32 || fused_x3)) {
+  if (final_done) {
     *mo_seq_rows = T;
     return 0;
   }
@@ -1157,18 +1134,13 @@ static int run_forward(a2p_ctx* c, const float* x_in, const int64_t* t_orig, int
       c->slot3_B = B;
     }
   }
-  // Row panels pay off once there are enough of them: every workgroup streams the whole weight set of its chain, so a
-  // forward of < ~1000 rows (config 0: B=1, T=240 -> 480 rows = 10 panels) is faster as many small 2-D tiles
-  // (measured: 0.99 vs 1.10 ms per step at 480 rows, equal at 1200, chain ahead from 2400 rows on).
-  // The kernel family is chosen from the row count of the UNSHARDED batch when the host names it (a2p_set_batch_hint;
-  // sample_parallel does): the families differ in rounding, and a sharded run must reproduce the single-process samples bit for bit
-  const int64_t rows_eff = (int64_t)(c->batch_hint > B ? (N / B) * c->batch_hint : N) * T;
-  // (the 1100-row break-even was measured against the small-forward kernels, which exist for the face model only: a context
-  // without them -- the body model, d != 512 -- keeps the round-2 threshold of 960 rows against the per-op kernels)
-  const int64_t chain_thr = small_supported(c) ? c->opt.chain_rows : (c->opt.chain_rows < 960 ? c->opt.chain_rows : 960);
-  const bool use_chain = chain_supported(c) && (rows_eff >= chain_thr || c->opt.chain_mt);
-  const bool use_small = !use_chain && small_supported(c);
-  return forward_body(c, x_in, t_orig, pass, mo_seq_rows, s, use_chain, use_small);
+  FwdPlan f = forward_plan(c, pass);
+  hipEvent_t tune0 = nullptr, tune1 = nullptr;
+  if (f.path == FWD_CHAIN) {
+    f.fam = chain_pick_family(c, f.nw, (int64_t)N * T, &tune0, &tune1);
+    c->ch_nw = f.nw; c->ch_fam_mid = f.fam.mid; c->ch_fam_post = f.fam.post;   // the last chain plan's record (a2p_debug_read)
+  }
+  return forward_body(c, f, x_in, t_orig, pass, mo_seq_rows, s, tune0, tune1);
 }
 
 static int launch_step_tail(a2p_ctx* c, StepP& sp, hipStream_t s) {
@@ -2007,7 +1979,12 @@ extern "C" int a2p_decoder_layer_forward(a2p_ctx* c, int32_t layer, float* x, co
   fr.base = flm.f();
   fr.seq_stride = (int64_t)F * 2 * d;
   HIPCHK(hipMemcpyAsync(c->x.p, x, (size_t)N * T * d * 4, hipMemcpyDeviceToDevice, s));
-  int rc = chain_supported(c) ? decoder_layer_chain(c, layer, N, T, kv, memory2 ? &kv2 : nullptr, fr, true, false, s)
+  FwdPlan f;   // one layer on the chain kernels: the workgroup shape by rule, the families as forced, else tall (nothing is measured here)
+  f.path = FWD_CHAIN; f.N = N; f.T = T; f.single_layer = true; f.nw = chain_pick_nw(c);
+  const ChainFam* fixed = chain_family_fixed(c, f.nw);
+  f.fam = fixed ? *fixed : kFamConfigs[0];
+  c->ch_npicks = 0;
+  int rc = chain_supported(c) ? decoder_layer_chain(c, f, layer, nullptr, kv, memory2 ? &kv2 : nullptr, fr, s)
                               : decoder_layer(c, layer, N, T, kv, memory2 ? &kv2 : nullptr, fr, s);
   if (rc == 0) hipMemcpyAsync(x, c->x.p, (size_t)N * T * d * 4, hipMemcpyDeviceToDevice, s);
   hipStreamSynchronize(s);
@@ -2029,6 +2006,15 @@ extern "C" int a2p_debug_read(a2p_ctx* c, const char* name, void* host, int64_t 
   if (n == "chain_family") {   // int32: chain kernel family of the last chain forward (10 x MID + POST; 1 = kernels_chain.h, 4 = kernels_chain4.h)
     ARG(bytes >= 4, "chain_family is one int32");
     *reinterpret_cast<int32_t*>(host) = c->ch_fam_mid * 10 + c->ch_fam_post;   // 11 | 44 | 41 | 14
+    return 0;
+  }
+  if (n == "chain_picks") {   // int32: what the last forward's chain launches were, as launch_chain recorded it: [launches (<= 64), ints per record (10)], then one ChainPick
+    // per launch in launch order {family 1|4, d, mt, nw, mode CHAIN_*, variant CV_*, grid, block, n_tall, stream CS_*}
+    const size_t n_rec = sizeof(c->ch_picks[0]) * (size_t)c->ch_npicks;
+    ARG((size_t)bytes >= 8 + n_rec, "chain_picks: %d launches need %zu bytes", c->ch_npicks, 8 + n_rec);
+    int32_t* out = reinterpret_cast<int32_t*>(host);
+    out[0] = c->ch_npicks; out[1] = (int32_t)(sizeof(ChainPick) / 4);
+    memcpy(out + 2, c->ch_picks, n_rec);
     return 0;
   }
   if (n == "attn3_launches") {   // int64: launches of attn3_kernel (kernels_attn3.h) on this context so far (tests, bench)

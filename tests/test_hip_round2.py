@@ -231,7 +231,7 @@ def test_layer0_shared_half_is_bit_identical_to_the_duplicated_path(dev, fmt, B,
 @pytest.mark.parametrize("B,T", [(11, 600), (32, 600), (13, 592)])
 def test_mixed_panel_heights_are_bit_identical_to_the_uniform_launch(dev, B, T, precision, monkeypatch):
     """Forwards of more than 256 48-row panels (face, d=512) launch the chain kernels with 64-row panels for the first workgroups
-    so that the grid fills whole rounds of the 256 CUs (csrc/kernels_chain.h `chain_kernel_mix`, a2p_lib_run.h `launch_chain`).
+    so that the grid fills whole rounds of the 256 CUs (csrc/kernels_chain.h `chain_kernel_mix`, a2p_lib_run.h `chain_pick`).
     Same bits as the uniform 48-row launch for both workgroup shapes, ragged tails included."""
     spec, sd, model, _ = build("face", precision, dev, max_batch=B)
     cfg = ClassifierFreeSampleModel(model)
