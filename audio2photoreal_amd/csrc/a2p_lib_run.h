@@ -255,7 +255,7 @@ static int chain_build_streams(a2p_ctx* c, hipStream_t s) {
       CHK(chain4_pack(c, c->ch_stream4[ch_index(l, CH_MID)], m4, s));
       if (l + 1 < L || c->tail32) {   // (the last layer too, unless final_layer is fused into its POST kernel: A2P_TAIL16)
         for (int hc = 128; hc <= 256; hc += 128) {   // hidden chunk of the feed-forward block: 128 (80-row panels) | 256 (<= 64 rows): Chain4Lds::HC
-          // two consumption orders of the feed-forward block (CHAIN4_FFN_PIPE, kernels_chain4.h): waves 4-7 (q4) linear1(h) linear2(h) per chunk; waves 0-3 (q4e)
+          // two consumption orders of the feed-forward block (kernels_chain4.h): waves 4-7 (q4) linear1(h) linear2(h) per chunk; waves 0-3 (q4e)
           // run their linear2 partial one chunk late: linear1(0) | linear1(1) linear2(0) | linear1(2) linear2(1) | ... | linear2(last)
           std::vector<ChainPackDesc> q4, q4e;
           pk4_gemm(q4, c->wt.at(pf(l) + "multihead_attn.out_proj.weight").p, d, d, 0, d, 0, 4);
@@ -264,13 +264,9 @@ static int chain_build_streams(a2p_ctx* c, hipStream_t s) {
           auto lin1_4 = [&](std::vector<ChainPackDesc>& v, int h) { pk4_gemm(v, w1.p, d, ff, 0, d, 0, nh, h * nh, nh); };   // linear1, hidden columns [hc h, hc h + hc): nh tiles, k-chunk-major
           auto lin2_4 = [&](std::vector<ChainPackDesc>& v, int h) { pk4_gemm(v, w2.p, ff, d, h * hc, hc, 0, 4); };          // linear2 partial over that hidden chunk, 4 output tiles
           for (int h = 0; h < nc; ++h) { lin1_4(q4, h); lin2_4(q4, h); }
-          if (CHAIN4_FFN_PIPE) {
-            for (int i = 0; i <= nc; ++i) {
-              if (i < nc) lin1_4(q4e, i);
-              if (i >= 1) lin2_4(q4e, i - 1);
-            }
-          } else {
-            for (int h = 0; h < nc; ++h) { lin1_4(q4e, h); lin2_4(q4e, h); }
+          for (int i = 0; i <= nc; ++i) {
+            if (i < nc) lin1_4(q4e, i);
+            if (i >= 1) lin2_4(q4e, i - 1);
           }
           for (std::vector<ChainPackDesc>* v : {&q4, &q4e}) {
             if (l + 1 < L) {
@@ -501,19 +497,14 @@ static ChainPick chain_pick(const a2p_ctx* c, const FwdPlan& f, int mode, const 
   return k;
 }
 
-// Every chain kernel instance of the library, by the pick that launches it.  (Diagnostic build: the gen-1 kernels carry the stamp ablation argument.)
+// Every chain kernel instance of the library, by the pick that launches it.
 using ChainKernel = void (*)(ChainP);
 struct ChainInst { ChainPick key; ChainKernel fn; };   // key: family, d, mt, nw, mode, variant
 template <int FAM, int D, int MT, int NW, int MODE, int VAR>
 static constexpr ChainKernel chain_instance() {
-#ifdef A2P_STAMPS
-  constexpr int ABL = 64;
-#else
-  constexpr int ABL = 0;
-#endif
   if constexpr (FAM == 4) return chain4_kernel<MT, MODE, VAR - CV_NEXT>;
   else if constexpr (VAR == CV_MIX) return chain_kernel_mix<D, 4, MT, MODE, NW>;   // 64-row panels first, then MT
-  else return chain_kernel<D, MT, MODE, ABL, NW>;
+  else return chain_kernel<D, MT, MODE, NW>;
 }
 #define CI(FAM, D, MT, NW, MODE, VAR) {{FAM, D, MT, NW, CHAIN_##MODE, CV_##VAR, 0, 0, 0, 0}, chain_instance<FAM, D, MT, NW, CHAIN_##MODE, CV_##VAR>()}
 static const ChainInst kChainInst[] = {

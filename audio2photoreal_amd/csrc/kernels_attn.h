@@ -122,27 +122,21 @@ __device__ __forceinline__ float attn_rowgroup_max(float v) {
   return __uint_as_float(r);
 }
 
-// ABL: ablation switches for scratch/attn_bench.hip only (the library instantiates ABL = 0):
-//   1 = no exp, 2 = no running-max reduction, 4 = no staging / barriers after tile 0, 8 = no PV MFMAs, 16 = no QK^T MFMAs,
-//   32 = per-tile barrier without the DMA wait, 64 = per-tile DMA wait without the barrier (timing only: results are wrong)
-// NWV: waves per workgroup (each wave owns QT*16 = 32 queries); 4 in production.  NWV = 2 was tried for its even grid (T = 600: 10
+// Four waves per workgroup, each owning QT*16 = 32 queries.  Two waves were tried for their even grid (T = 600: 10
 // query blocks per (sequence, head), B=8: 1280 workgroups = exactly 5 per CU instead of 2 or 3) and lost clearly -- cross attention
 // 97 vs 70 us: every K/V tile then feeds 64 instead of 128 queries and the tile DMA / LDS traffic per query doubles.
 // waves per SIMD the register allocation is held to: 3 for the 16-bit and the fp32 dh <= 64 kernels.  The fp32 dh = 128 kernel (the
 // lip regressor of the audio front end: once per clip, 4 heads; 67 KB of LDS per workgroup) asks for 1: at 2 it spills 59 registers,
 // and a request of 3 was silently dropped by hipcc (the code it compiled was the occupancy-1 code all along)
-#ifndef A2P_ATTN_F32_MINWAVES
-#define A2P_ATTN_F32_MINWAVES 3   // fp32 parity mode, head dim 64: 3 waves per SIMD spill 42 registers; 2 waves (208 registers, no spills) measured SLOWER: 96.6 vs 101.4 steps/s (profiles/r05_fp32_attn_occupancy_ab.txt)
-#endif
+// fp32 parity mode, head dim 64: 3 waves per SIMD spill 42 registers; 2 waves (208 registers, no spills) measured SLOWER: 96.6 vs 101.4 steps/s (profiles/r05_fp32_attn_occupancy_ab.txt)
 template <typename T, int DH>
-constexpr int attn_min_waves() { return (sizeof(T) == 4 && DH == 128) ? 1 : (sizeof(T) == 4 && DH == 64) ? A2P_ATTN_F32_MINWAVES : 3; }
+constexpr int attn_min_waves() { return (sizeof(T) == 4 && DH == 128) ? 1 : 3; }
 
-template <typename T, int DH, int ABL = 0, int NWV = 4>
-__global__ __launch_bounds__(64 * NWV, (attn_min_waves<T, DH>())) void attn_kernel(AttnP p) {
+template <typename T, int DH>
+__global__ __launch_bounds__(256, (attn_min_waves<T, DH>())) void attn_kernel(AttnP p) {
   using P = Prec<T>;
   using L = AttnLds<T, DH>;
-  constexpr int QT = 2, BQ = NWV * QT * 16, KV = 64, NTHR = 64 * NWV;
-  static_assert(NWV == 4 || sizeof(T) == 2, "the register-staged fp32 path is written for 4 waves");
+  constexpr int NWV = 4, QT = 2, BQ = NWV * QT * 16, KV = 64, NTHR = 64 * NWV;   // NWV: waves per workgroup
   constexpr int KC = DH / P::KCH;   // k-chunks over head_dim (QK^T)
   constexpr int DVT = DH / 16;      // 16-row tiles of O^T
   constexpr int VEC = 16 / sizeof(T);
@@ -278,22 +272,11 @@ __global__ __launch_bounds__(64 * NWV, (attn_min_waves<T, DH>())) void attn_kern
     constexpr int buf = L::DMA ? BUF : 0;
     T* Ks = smem + buf * (L::KSZ + L::VSZ);
     T* Vs = Ks + L::KSZ;
-    if (!(ABL & 4) || tile == 0) {
-      // bf16: tile landed (vmcnt(0)) and the other buffer is free; fp32: previous tile consumed
-      if constexpr ((ABL & 32) != 0) {          // ablation: barrier, but no wait for the tile DMA
-        if (tile == 0) __syncthreads();
-        else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      } else if constexpr ((ABL & 64) != 0) {   // ablation: wait for this wave's DMA pieces, but no barrier
-        if (tile == 0) __syncthreads();
-        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      } else {
-        __syncthreads();
-      }
-      if constexpr (L::DMA) {
-        if (tile + 1 < ntiles) stage_dma(tile + 1, buf ^ 1);
-      } else {
-        stage_regs(tile);
-      }
+    __syncthreads();   // bf16: tile landed (vmcnt(0)) and the other buffer is free; fp32: previous tile consumed
+    if constexpr (L::DMA) {
+      if (tile + 1 < ntiles) stage_dma(tile + 1, buf ^ 1);
+    } else {
+      stage_regs(tile);
     }
     if (p.S_tail > 0 && kv0 + KV > p.S_main) {  // block-uniform: patch the time-token rows into the tile
       if constexpr (!L::DMA) __syncthreads();
@@ -325,10 +308,7 @@ __global__ __launch_bounds__(64 * NWV, (attn_min_waves<T, DH>())) void attn_kern
       for (int kt = 0; kt < 4; ++kt) {
         const typename P::Frag kf = P::load(&Ks[L::kidx(L::krow(kt, l15), kc * P::KCH + g * P::EPL)]);
 #pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-          if constexpr (!(ABL & 16)) s[kt][qt] = P::mfma(kf, qf[qt][kc], s[kt][qt]);
-          else asm volatile("" : "+v"(s[kt][qt]) : "v"(kf));
-        }
+        for (int qt = 0; qt < QT; ++qt) s[kt][qt] = P::mfma(kf, qf[qt][kc], s[kt][qt]);
       }
     }
     // 16-bit path: all V^T fragments of the tile are requested NOW, behind the QK^T MFMAs, so that their LDS latency passes
@@ -339,7 +319,6 @@ __global__ __launch_bounds__(64 * NWV, (attn_min_waves<T, DH>())) void attn_kern
 #pragma unroll
       for (int dv = 0; dv < DVT; ++dv)
         vfr[c][dv] = *reinterpret_cast<const h16x8*>(&Vs[L::vidx(dv * 16 + l15, c * 32 + g * 8)]);
-#ifndef A2P_ATTN_AB_R3   // (scratch A/B build: the round-3 tile body, to price the two round-4 additions on one box)
       if constexpr (MASKED) {
         // Keys past the end carry P = 0, but their V^T columns were never written by anybody: whatever the workspace held there
         // goes into the MFMA, and 0 x (inf | nan) = nan.  One earlier non-finite forward on the context (an overflowing checkpoint:
@@ -351,7 +330,6 @@ __global__ __launch_bounds__(64 * NWV, (attn_min_waves<T, DH>())) void attn_kern
           for (int e = 0; e < 8; ++e)
             if (e >= nvalid) vfr[c][dv][e] = (h16_t)0.f;
       }
-#endif
     };
     if constexpr (sizeof(T) == 2) load_vfr(0);   // the second half follows the softmax (register budget: 3 waves per SIMD)
     // ---- online softmax (log2 domain); lane owns query l15, keys kt*16 + g*4 + r ----
@@ -370,13 +348,11 @@ __global__ __launch_bounds__(64 * NWV, (attn_min_waves<T, DH>())) void attn_kern
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
       float mx = s[0][qt][0];
-      if constexpr (!(ABL & 2)) {
 #pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
+      for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kt][qt][r]);
-        mx = attn_rowgroup_max(mx);
-      }
+        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[kt][qt][r]);
+      mx = attn_rowgroup_max(mx);
       const float mnew = fmaxf(mrun[qt], mx * p.scale_log2e);
       const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
       mrun[qt] = mnew;
@@ -390,10 +366,8 @@ __global__ __launch_bounds__(64 * NWV, (attn_min_waves<T, DH>())) void attn_kern
         for (int h = 0; h < 2; ++h) {
           f32x2 v = {s[kt][qt][2 * h], s[kt][qt][2 * h + 1]};
           v = __builtin_elementwise_fma(v, sc2, mn2);
-          if constexpr (!(ABL & 1)) {
-            v[0] = __builtin_amdgcn_exp2f(v[0]);
-            v[1] = __builtin_amdgcn_exp2f(v[1]);
-          }
+          v[0] = __builtin_amdgcn_exp2f(v[0]);
+          v[1] = __builtin_amdgcn_exp2f(v[1]);
           ps2 += v;
           s[kt][qt][2 * h] = v[0];
           s[kt][qt][2 * h + 1] = v[1];
@@ -425,10 +399,7 @@ __global__ __launch_bounds__(64 * NWV, (attn_min_waves<T, DH>())) void attn_kern
         for (int dv = 0; dv < DVT; ++dv) {
           const h16x8 vf = vfr[c][dv];
 #pragma unroll
-          for (int qt = 0; qt < QT; ++qt) {
-            if constexpr (!(ABL & 8)) o[qt][dv] = P::mfma(vf, pf[qt], o[qt][dv]);
-            else asm volatile("" : "+v"(o[qt][dv]) : "v"(vf), "v"(pf[qt]));
-          }
+          for (int qt = 0; qt < QT; ++qt) o[qt][dv] = P::mfma(vf, pf[qt], o[qt][dv]);
         }
       }
       } else {
@@ -462,7 +433,6 @@ __global__ __launch_bounds__(64 * NWV, (attn_min_waves<T, DH>())) void attn_kern
   if (wave_active) tile_loop(integral_constant<bool, true>{});
   else tile_loop(integral_constant<bool, false>{});
 
-#ifndef A2P_ATTN_AB_R3
   if (p.stat_max && wave_active) {   // largest row maximum (natural units) of this wave's queries
     float m = mrun[0];
 #pragma unroll
@@ -475,7 +445,6 @@ __global__ __launch_bounds__(64 * NWV, (attn_min_waves<T, DH>())) void attn_kern
     const int mi = attn_ordered_int(m * 0.6931471805599453f);   // log2 domain -> natural units
     if (lane == 0 && mi > __atomic_load_n(p.stat_max, __ATOMIC_RELAXED)) atomicMax(p.stat_max, mi);
   }
-#endif
   // ---- normalise and store: lane owns query l15, rows dv*16 + g*4 + {0..3} ----
   if constexpr (sizeof(T) == 2) {
     // 16-bit: a lane holds 4 consecutive head-dim values (8 bytes) of one query, so a direct store writes 16 rows x 32 bytes

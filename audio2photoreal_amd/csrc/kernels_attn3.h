@@ -81,12 +81,7 @@ struct Attn3Geo {
 #define A3_AK(set, kc, kt) (120 + 64 * (set) + 4 * ((kc) * 4 + (kt)))           // K fragments (of the tile whose scores the step produces)
 #define A3_AV(set, c, dv, DVT_) (152 + 64 * (set) + 4 * ((c) * (DVT_) + (dv)))  // V^T fragments (of the tile the step consumes)
 #define A3_ONES(c) (248 + 4 * (c))   // A operand of the row-sum MFMAs of 32-key chunk c: ones -- for the LAST tile: ones on its valid keys, zeros on the padding
-#ifndef A3X
-#define A3X 0   // scratch timing experiments (results wrong): 1 no exp2, 2 no maxima, 4 no softmax packets at all, 8 no MFMAs, 16 no fragment reads
-#endif
-#ifndef A2P_ATTN3_THR
 #define A2P_ATTN3_THR 8.0f     // log2 units a score may exceed the lazy reference by before the reference moves
-#endif
 #ifdef A2P_HALF
 #define A3_MFMA "v_mfma_f32_16x16x32_f16"
 #define A3_CVT "v_cvt_pk_f16_f32"
@@ -98,8 +93,7 @@ struct Attn3Geo {
 // cdna_hip_programming.md 5.7; 8-pass MFMA -> VALU)
 #define A3_MFMA_LANDED() asm volatile("s_nop 15\n\ts_nop 7" ::: "memory")
 
-// ABL (scratch/attn3_bench.hip only): 64 no tile DMA after the prologue, 128 no barriers
-template <int DH, int ABL = 0>
+template <int DH>
 __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(A3_OWN))) void attn3_kernel(AttnP p) {
   using P = Prec<h16_t>;
   using G = Attn3Geo<DH>;
@@ -283,7 +277,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(A3_OWN))) vo
       attn3_static_for<0, 4>([&](auto t_c) __attribute__((always_inline)) {
         constexpr int kt = decltype(t_c)::value, R = A3_AK(decltype(set_c)::value, kc, kt);
         (void)&a;
-        if constexpr (!(A3X & 16)) asm volatile("ds_read_b128 a[%c0:%c1], %2 offset:%3" ::"n"(R), "n"(R + 3), "v"(a), "n"((32 * (kt >> 1) + 4 * (kt & 1)) * L::LSK * 2));
+        asm volatile("ds_read_b128 a[%c0:%c1], %2 offset:%3" ::"n"(R), "n"(R + 3), "v"(a), "n"((32 * (kt >> 1) + 4 * (kt & 1)) * L::LSK * 2));
       });
     });
   };
@@ -295,7 +289,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(A3_OWN))) vo
       attn3_static_for<0, DVT>([&](auto d_c) __attribute__((always_inline)) {
         constexpr int dv = decltype(d_c)::value, R = A3_AV(decltype(set_c)::value, c, dv, DVT);
         (void)&a;
-        if constexpr (!(A3X & 16)) asm volatile("ds_read_b128 a[%c0:%c1], %2 offset:%3" ::"n"(R), "n"(R + 3), "v"(a), "n"(dv * 16 * L::LSV * 2));
+        asm volatile("ds_read_b128 a[%c0:%c1], %2 offset:%3" ::"n"(R), "n"(R + 3), "v"(a), "n"(dv * 16 * L::LSV * 2));
       });
     });
   };
@@ -429,8 +423,8 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(A3_OWN))) vo
   // (n - 5) / 2 into the P fragment registers of the query tile.  Every index is a compile-time constant (attn3_static_for).
   auto soft = [&](auto n_c, auto q_c) __attribute__((always_inline)) {
     constexpr int n = decltype(n_c)::value, q = decltype(q_c)::value;
-    if constexpr (n < 16 && !(A3X & 5)) asm volatile("v_exp_f32 v[%c0], v[%c0]" ::"n"(A3_S(n >> 2, q, n & 3)));
-    if constexpr (n >= 5 && ((n - 5) & 1) == 0 && (n - 5) / 2 < 8 && !(A3X & 4)) {
+    if constexpr (n < 16) asm volatile("v_exp_f32 v[%c0], v[%c0]" ::"n"(A3_S(n >> 2, q, n & 3)));
+    if constexpr (n >= 5 && ((n - 5) & 1) == 0 && (n - 5) / 2 < 8) {
       constexpr int j = (n - 5) / 2, c = j >> 2, w = j & 3, kt = 2 * c + (w >> 1), r0 = (w & 1) * 2;
       asm volatile(A3_CVT " v[%c0], v[%c1], v[%c2]" ::"n"(A3_PF(q % 3, c) + w), "n"(A3_S(kt, q, r0)), "n"(A3_S(kt, q, r0 + 1)));
     }
@@ -466,7 +460,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(A3_OWN))) vo
     auto frag_read = [&](auto i_c) __attribute__((always_inline)) {   // read number i of the next step's fragments
       constexpr int i = decltype(i_c)::value;
       (void)&fa_v; (void)&fa_k;
-      if constexpr (A3X & 16) return;
       if constexpr (i < 2 * DVT) {
         constexpr int c = i / DVT, dv = i % DVT, R = A3_AV(PAR ^ 1, c, dv, DVT);
         asm volatile("ds_read_b128 a[%c0:%c1], %2 offset:%3" ::"n"(R), "n"(R + 3), "v"(fa_v[c]), "n"(dv * 16 * L::LSV * 2));
@@ -491,14 +484,13 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(A3_OWN))) vo
         // an accumulator are DVT + 1 apart, never back to back
         if constexpr (is_pv && ip % SPC == DVT) {
           constexpr int c = ip / SPC, RL = A3_AL(q);
-          if constexpr (!(A3X & 8)) asm volatile(A3_MFMA " v[%c0:%c1], a[%c2:%c3], v[%c4:%c5], v[%c0:%c1]" ::"n"(RL), "n"(RL + 3), "n"(A3_ONES(c)), "n"(A3_ONES(c) + 3), "n"(A3_PF(q % 3, c)), "n"(A3_PF(q % 3, c) + 3));
+          asm volatile(A3_MFMA " v[%c0:%c1], a[%c2:%c3], v[%c4:%c5], v[%c0:%c1]" ::"n"(RL), "n"(RL + 3), "n"(A3_ONES(c)), "n"(A3_ONES(c) + 3), "n"(A3_PF(q % 3, c)), "n"(A3_PF(q % 3, c) + 3));
         } else if constexpr (is_pv) {
           constexpr int c = ip / SPC, dv = ip % SPC, RO = A3_AO(q, dv, DVT);
-          if constexpr (!(A3X & 8)) asm volatile(A3_MFMA " a[%c0:%c1], a[%c2:%c3], v[%c4:%c5], a[%c0:%c1]" ::"n"(RO), "n"(RO + 3), "n"(A3_AV(PAR, c, dv, DVT)), "n"(A3_AV(PAR, c, dv, DVT) + 3), "n"(A3_PF(q % 3, c)), "n"(A3_PF(q % 3, c) + 3));
+          asm volatile(A3_MFMA " a[%c0:%c1], a[%c2:%c3], v[%c4:%c5], a[%c0:%c1]" ::"n"(RO), "n"(RO + 3), "n"(A3_AV(PAR, c, dv, DVT)), "n"(A3_AV(PAR, c, dv, DVT) + 3), "n"(A3_PF(q % 3, c)), "n"(A3_PF(q % 3, c) + 3));
         } else {
           constexpr int kc = iq / 4, kt = iq % 4, R = A3_S(kt, q, 0);
-          if constexpr (A3X & 8) {}
-          else if constexpr (kc == 0) asm volatile(A3_MFMA " v[%c0:%c1], a[%c2:%c3], a[%c4:%c5], v[%c6:%c7]" ::"n"(R), "n"(R + 3), "n"(A3_AK(PAR, kc, kt)), "n"(A3_AK(PAR, kc, kt) + 3), "n"(A3_AQ(q, kc, KC)), "n"(A3_AQ(q, kc, KC) + 3), "n"(A3_CI(q)), "n"(A3_CI(q) + 3));
+          if constexpr (kc == 0) asm volatile(A3_MFMA " v[%c0:%c1], a[%c2:%c3], a[%c4:%c5], v[%c6:%c7]" ::"n"(R), "n"(R + 3), "n"(A3_AK(PAR, kc, kt)), "n"(A3_AK(PAR, kc, kt) + 3), "n"(A3_AQ(q, kc, KC)), "n"(A3_AQ(q, kc, KC) + 3), "n"(A3_CI(q)), "n"(A3_CI(q) + 3));
           else asm volatile(A3_MFMA " v[%c0:%c1], a[%c2:%c3], a[%c4:%c5], v[%c0:%c1]" ::"n"(R), "n"(R + 3), "n"(A3_AK(PAR, kc, kt)), "n"(A3_AK(PAR, kc, kt) + 3), "n"(A3_AQ(q, kc, KC)), "n"(A3_AQ(q, kc, KC) + 3));
         }
         // fillers: the softmax of query tile q + 1 (behind the last group: of query tile 0 of the NEXT tile) spread over the group's
@@ -512,14 +504,14 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(A3_OWN))) vo
           constexpr int n0 = (i * NSOFT) / NM, n1 = ((i + 1) * NSOFT) / NM;
           attn3_static_for<n0, n1>([&](auto n_c) __attribute__((always_inline)) { soft(n_c, std::integral_constant<int, 0>{}); });
         }
-        if constexpr (QK && q > 0 && !(A3X & 2)) {
+        if constexpr (QK && q > 0) {
           constexpr int j0 = (i * 8) / NM, j1 = ((i + 1) * 8) / NM;
           attn3_static_for<j0, j1>([&](auto j_c) __attribute__((always_inline)) {
             constexpr int j = decltype(j_c)::value, R = A3_S(j >> 1, qp, (j & 1) * 2);
             asm volatile("v_max3_f32 v[%c0], v[%c0], v[%c1], v[%c2]" ::"n"(A3_M(qp)), "n"(R), "n"(R + 1));
           });
         }
-        if constexpr (LASTG && !(A3X & 2) && i >= NM - 4) {   // its own maxima: score tile kt was completed by MFMA NQK - 4 + kt, >= 4 MFMAs ago
+        if constexpr (LASTG && i >= NM - 4) {   // its own maxima: score tile kt was completed by MFMA NQK - 4 + kt, >= 4 MFMAs ago
           constexpr int kt = i - (NM - 4), R = A3_S(kt, q, 0);
           asm volatile("v_max3_f32 v[%c0], v[%c0], v[%c1], v[%c2]\n\tv_max3_f32 v[%c0], v[%c0], v[%c3], v[%c4]" ::"n"(A3_M(q)), "n"(R), "n"(R + 1), "n"(R + 2), "n"(R + 3));
         }
@@ -531,19 +523,15 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(A3_OWN))) vo
   // ring bookkeeping at the top of step t: tile t+1 landed for everyone (its K is read in this step), the slot of tile t-1 -- last read
   // in step t-1 -- refilled with tile t+NS-1
   auto sync_top = [&](int t) __attribute__((always_inline)) {
-    if constexpr ((ABL & 64) == 0) {
-      const int younger = ntiles - 3 - t;   // wave-uniform: tiles requested after t+2 (at most NS - 4 = 4 of them are in flight)
-      if (younger >= 4) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PW * 4) : "memory");        // steady state
-      else if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PW * 2) : "memory");   // (the last steps wait a little early: two rungs instead of four branches)
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    const int younger = ntiles - 3 - t;   // wave-uniform: tiles requested after t+2 (at most NS - 4 = 4 of them are in flight)
+    if (younger >= 4) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PW * 4) : "memory");        // steady state
+    else if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PW * 2) : "memory");   // (the last steps wait a little early: two rungs instead of four branches)
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     static_assert(NS == 8, "the wait ladder is written for 4 younger tiles");
     A3_STAMP(2);  // landed-wait states + tail maxima + the tile DMA wait
-    if constexpr (!(ABL & 128)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     A3_STAMP(3);  // barrier
-    if constexpr ((ABL & 64) == 0) {
-      if (t + NS - 1 < ntiles) issue_tile((t + NS - 1) & (NS - 1));
-    }
+    if (t + NS - 1 < ntiles) issue_tile((t + NS - 1) & (NS - 1));
     A3_STAMP(4);  // tile DMA issue
     if (t + 2 >= tfin) {   // (rare: the last one or two steps)
       for (int tile = (t == 0 ? 1 : t + 2); tile <= t + 2; ++tile)

@@ -185,43 +185,25 @@ __device__ __forceinline__ void chain_glds16(const void* gsrc, void* lds_wave_ba
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-// Activation accesses go through these helpers so their cache policy is one switch.  Non-temporal (-DCHAIN_NT_ACT) was
-// measured and rejected: 2.42 vs 2.37 ms per step at B=8 (same box, 3 alternating runs) -- the activations are re-read by
-// the next kernel from L2/MALL, and evict-first costs more there than it saves on the weight stream.
-#ifdef CHAIN_NT_ACT
-#define CHAIN_NT 1
-#else
-#define CHAIN_NT 0
-#endif
-#ifdef CHAIN_NT_STORES   // experiment: only the output stores non-temporal (write-through: no dirty-line flush at kernel end)
-#define CHAIN_NT_ST 1
-#else
-#define CHAIN_NT_ST CHAIN_NT
-#endif
-__device__ __forceinline__ f32x4 chain_ld4(const float* p) {
-  if constexpr (CHAIN_NT) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-  else return *reinterpret_cast<const f32x4*>(p);
-}
-__device__ __forceinline__ void chain_st4(float* p, f32x4 v) {
-  if constexpr (CHAIN_NT_ST) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-  else *reinterpret_cast<f32x4*>(p) = v;
-}
-__device__ __forceinline__ void chain_st_bf8(h16_t* p, h16x8 v) {
-  if constexpr (CHAIN_NT_ST) __builtin_nontemporal_store(v, reinterpret_cast<h16x8*>(p));
-  else *reinterpret_cast<h16x8*>(p) = v;
-}
-__device__ __forceinline__ void chain_st_bf4(h16_t* p, h16x4 v) {
-  if constexpr (CHAIN_NT_ST) __builtin_nontemporal_store(v, reinterpret_cast<h16x4*>(p));
-  else *reinterpret_cast<h16x4*>(p) = v;
-}
+// Activation accesses go through these helpers.  Non-temporal accesses were measured and rejected: 2.42 vs 2.37 ms per step
+// at B=8 (same box, 3 alternating runs) -- the activations are re-read by the next kernel from L2/MALL, and evict-first
+// costs more there than it saves on the weight stream.
+__device__ __forceinline__ f32x4 chain_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ void chain_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+__device__ __forceinline__ void chain_st_bf8(h16_t* p, h16x8 v) { *reinterpret_cast<h16x8*>(p) = v; }
+__device__ __forceinline__ void chain_st_bf4(h16_t* p, h16x4 v) { *reinterpret_cast<h16x4*>(p) = v; }
 
 // LDS-only barrier: never waits for the DMA queue
 __device__ __forceinline__ void chain_bar() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// ABL: ablation switches for scratch/chain_bench.hip only (the library instantiates ABL = 0):
-//   1 = no global stores, 2 = no MFMA, 4 = no weight DMA / waits, 8 = no workgroup barriers in the FFN,
-//   16 = no fragment reads from LDS, 64 = phase time stamps (100 MHz s_memrealtime) of blocks 0 / 101 into p.fin_out,
-//   debug (scratch/chain_dbg.hip): 256 = stop after the out_proj epilogue, 512 = out_proj result discarded, 1024 = FFN result discarded
+// Diagnostic build (-DA2P_STAMPS): chain_kernel writes phase time stamps (100 MHz s_memrealtime) of blocks 0 / 101 into p.fin_out; the
+// results stay right.  chain_body takes the switch as STAMP because chain_kernel_mix never stamps (its blocks 0 and 101 may run
+// different panel heights).
+#ifdef A2P_STAMPS
+constexpr bool CHAIN_STAMPS = true;
+#else
+constexpr bool CHAIN_STAMPS = false;
+#endif
 // NW: waves per workgroup.  4 = one 512-register wave per SIMD; 8 = two 256-register waves per SIMD, each owning 16 of a
 // tile's 128 columns (half the accumulators, half the weight slice, its own DMA ring): a wave's LDS-DMA pieces and
 // fragment reads cost it 40-60 issue cycles each that its own MFMAs do not hide (measured additive, docs/lab_notebook_r1_r4.md section 4),
@@ -236,7 +218,7 @@ struct ChainLds {
 };
 
 // The chain of one row panel: rows [m0, m0 + 16*MT) of the launch, LDS at `smem` (ChainLds<D, MT>::ELEMS elements).
-template <int D, int MT, int MODE, int ABL, int NW>
+template <int D, int MT, int MODE, bool STAMP, int NW>
 __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, const int m0) {
   constexpr int CW = 128 / NW;   // columns of a 128-column tile owned by one wave
   constexpr int NJ = CW / 16;    // 16-column sub-tiles per wave per tile
@@ -263,7 +245,7 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
   const int l15 = lane & 15, g = lane >> 4;
   const int W4 = NW == 4 ? wid : (wid >> 1), J0 = NW == 4 ? 0 : (wid & 1);  // 32-column group and first 16-column sub-tile of this wave
   auto stamp = [&](int i) __attribute__((always_inline)) {
-    if constexpr (ABL & 64) {
+    if constexpr (STAMP) {
       if (tid == 0 && (blockIdx.x == 0 || blockIdx.x == 101))
         reinterpret_cast<unsigned long long*>(p.fin_out)[(blockIdx.x ? 32 : 0) + i] = wall_clock64();
     }
@@ -282,15 +264,14 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
   int issue_off = 0, consume_off = 0;
   auto issue_stage = [&]() __attribute__((always_inline)) {
     h16_t* buf = myring + issue_off;
-    if constexpr (!(ABL & 4)) {  // 4 x 1 KiB; the instruction offset advances the global AND the LDS address (one M0 write per stage)
-      const auto gp = (const __attribute__((address_space(1))) void*)wsrc;
-      const auto lp = (__attribute__((address_space(3))) void*)buf;
-      __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(gp, lp, 16, 1024, 0);
-      if constexpr (PCS == 4) {
-        __builtin_amdgcn_global_load_lds(gp, lp, 16, 2048, 0);
-        __builtin_amdgcn_global_load_lds(gp, lp, 16, 3072, 0);
-      }
+    // 4 x 1 KiB; the instruction offset advances the global AND the LDS address (one M0 write per stage)
+    const auto gp = (const __attribute__((address_space(1))) void*)wsrc;
+    const auto lp = (__attribute__((address_space(3))) void*)buf;
+    __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(gp, lp, 16, 1024, 0);
+    if constexpr (PCS == 4) {
+      __builtin_amdgcn_global_load_lds(gp, lp, 16, 2048, 0);
+      __builtin_amdgcn_global_load_lds(gp, lp, 16, 3072, 0);
     }
     wsrc += CHAIN_STAGE_ELEMS;  // past the end of the stream: the host pads CHAIN_STREAM_PAD stages
     issue_off = issue_off + WSLICE == NS * WSLICE ? 0 : issue_off + WSLICE;
@@ -298,7 +279,7 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
   // wait for this wave's oldest slice (NS-2 newer ones stay in flight), hand the just-freed slot to the DMA
   auto stage_begin = [&]() __attribute__((always_inline)) -> const h16_t* {
     // lgkmcnt(0): the fragment reads of the slot that is about to be refilled have returned
-    if constexpr (!(ABL & 4)) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(PCS * (NS - 2)) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(PCS * (NS - 2)) : "memory");
     // pin the step boundary: hipcc otherwise hoists the NEXT step's MFMAs above this wait, right behind their fragment
     // reads, which un-pipelines the loop (cdna_hip_programming.md §5.4 rule 18)
     __builtin_amdgcn_sched_barrier(0);
@@ -317,13 +298,11 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
     for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
-        if constexpr (ABL & 16) asm volatile("" : "=v"(f.a[kk][mt]));
-        else f.a[kk][mt] = *reinterpret_cast<const h16x8*>(P + (mt * 16 + l15) * pld + (((kchunk0 + kk * 4 + g) ^ l15) << 3));
+        f.a[kk][mt] = *reinterpret_cast<const h16x8*>(P + (mt * 16 + l15) * pld + (((kchunk0 + kk * 4 + g) ^ l15) << 3));
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int wrow = j * 16 + l15;
-        if constexpr (ABL & 16) asm volatile("" : "=v"(f.w[kk][j]));
-        else f.w[kk][j] = *reinterpret_cast<const h16x8*>(wb + wrow * 64 + (((kk * 4 + g) ^ ((wrow >> 1) & 7)) << 3));
+        f.w[kk][j] = *reinterpret_cast<const h16x8*>(wb + wrow * 64 + (((kk * 4 + g) ^ ((wrow >> 1) & 7)) << 3));
       }
     }
   };
@@ -336,12 +315,8 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
-          if constexpr (!(ABL & 2)) {
-            if (swap) acc[mt][j] = A2P_MFMA16(f.a[kk][mt], f.w[kk][j], acc[mt][j]);
-            else acc[mt][j] = A2P_MFMA16(f.w[kk][j], f.a[kk][mt], acc[mt][j]);
-          } else {
-            asm volatile("" ::"v"(f.w[kk][j]), "v"(f.a[kk][mt]));
-          }
+          if (swap) acc[mt][j] = A2P_MFMA16(f.a[kk][mt], f.w[kk][j], acc[mt][j]);
+          else acc[mt][j] = A2P_MFMA16(f.w[kk][j], f.a[kk][mt], acc[mt][j]);
         }
   };
   // acc += P[:, 0:64*nks] * (the next nks stream stages)^T, nks even
@@ -520,7 +495,7 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
       m = m < p.M ? m : p.M - 1;
       m = (p.src_rows > 0 && m >= p.src_rows) ? m - p.src_rows : m;
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.ain + (int64_t)m * p.ld_ain + ((pos ^ (row & 15)) << 3)),
-                                       (__attribute__((address_space(3))) void*)(panelA + r0 * D), 16, 0, CHAIN_NT ? 2 : 0);
+                                       (__attribute__((address_space(3))) void*)(panelA + r0 * D), 16, 0, 0);
     }
   }
   for (int kb = wid; kb < p.aux_kb; kb += NW) chain_glds16(p.aux + kb * 256 + lane * 4, aux + kb * 256);
@@ -701,7 +676,6 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
     chain_bar();  // the panel is complete before any wave's fragment reads
   };
   auto store_x = [&]() __attribute__((always_inline)) {
-    if constexpr (ABL & 1) return;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       if (m0 + mt * 16 + l15 >= p.M) continue;
@@ -738,7 +712,7 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
     }
     [[maybe_unused]] h16x4 held[MT];   // 8 waves: the even tile of a pair, kept until its neighbour is done
     for (int t = 0; t < ntiles; ++t) {
-      if constexpr (ABL & 64) { if (t > 0 && gs_stamp < 31) stamp(gs_stamp++); }   // previous tile's epilogue done
+      if constexpr (STAMP) { if (t > 0 && gs_stamp < 31) stamp(gs_stamp++); }   // previous tile's epilogue done
       f32x4 acc[MT][NJ];
       if constexpr (NW == 8) {
         if (!transposed) init_bias_o(acc, bias_lds, t);
@@ -748,7 +722,7 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
         else init_bias_t(acc, bias_lds + t * 128);
       }
       gemm_tile(acc, panelA, D, KS, transposed);
-      if constexpr (ABL & 64) { if (gs_stamp < 31) stamp(gs_stamp++); }   // diagnostic build: tile GEMM done / tile stored (below)
+      if constexpr (STAMP) { if (gs_stamp < 31) stamp(gs_stamp++); }   // diagnostic build: tile GEMM done / tile stored (below)
       if (fin && t == ntiles - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if constexpr (NW == 8) {
         if (!transposed) {
@@ -779,10 +753,6 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
                            : "=v"(w)
                            : "v"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) h16_t*)(stg + prow * 32 + (((pp >> 1) ^ ((prow >> 2) & 1)) * 2 + (pp & 1)) * 8))
                            : "memory");
-              if constexpr (ABL & 1) {
-                asm volatile("" ::"v"(w));
-                continue;
-              }
               const int m = m0 + mt * 16 + (lane >> 2);
               if (m < p.M) chain_st_bf8(out + (int64_t)m * ldo + obase(t - 1) + (lane & 3) * 8, w);
             }
@@ -793,11 +763,6 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
       if (!transposed) {  // 4 waves: 8 contiguous columns per lane, one 16-byte store per row
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-          if constexpr (ABL & 1) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) asm volatile("" ::"v"(acc[mt][j]));
-            continue;
-          }
           if (m0 + mt * 16 + l15 >= p.M) continue;
           h16_t* dst = out + (int64_t)row_m[mt] * ldo + col_of(t, 0);
           const f32x4 v = acc[mt][0];
@@ -823,10 +788,6 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
         for (int i = 0; i < VP; ++i) {
           h16x8 v;
           asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"((uint32_t)(uintptr_t)(__attribute__((address_space(3))) h16_t*)(stg + (lane + 64 * i) * 8)) : "memory");
-          if constexpr (ABL & 1) {
-            asm volatile("" ::"v"(v));
-            continue;
-          }
           if (voff[i] >= 0) chain_st_bf8(out + voff[i] + (int64_t)(NW == 8 ? obase(t) + vcol[i] : t * 128 + vcol[i]) * ldo, v);
         }
       } else {
@@ -835,10 +796,6 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
             const f32x4 v = acc[mt][j];
-            if constexpr (ABL & 1) {
-              asm volatile("" ::"v"(v));
-              continue;
-            }
             const h16x4 o = {(h16_t)v[0], (h16_t)v[1], (h16_t)v[2], (h16_t)v[3]};
             // rows m .. m+3 (m % 4 == 0) of column n: one 8-byte store when the frame count is a multiple of 4 (the four rows
             // then share a sequence and the address is aligned), else row by row (T = 30 k frames, k odd)
@@ -887,18 +844,11 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
       for (int t = 0; t < NT; ++t) zero(oacc[t]);
       gemm_group(oacc, panelA, D, std::integral_constant<int, KS>{});
       stamp(2);
-      if constexpr (!(ABL & 512)) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) film_res(oacc[t], t, bias, film);
-      }
+      for (int t = 0; t < NT; ++t) film_res(oacc[t], t, bias, film);
     };
     out_proj_block(p.bias_o, p.film_o);
     stamp(3);
-    if constexpr (ABL & 256) {
-      store_x();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      return;
-    }
     ln_stats();
     stamp(4);
     if constexpr (MODE == CHAIN_MID) {
@@ -935,7 +885,6 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
             }
         }
         chain_bar();     // the query panel is complete
-#ifndef A2P_KF_SKIP   // (scratch timing build: the kernel without its attention phase)
         {
           // S^T = K Q^T and O^T = V^T P^T per (16-row tile, head) with the fragment / key mapping of kernels_attn.h: lane (l15, g) owns
           // query row l15 and the 8 keys 8g .. 8g+7, so the probabilities feed the second MFMA without data movement.  Wave w takes
@@ -1040,7 +989,6 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
             if (lane == 0 && mi > __atomic_load_n(p.stat_max, __ATOMIC_RELAXED)) atomicMax(p.stat_max, mi);
           }
         }
-#endif
         chain_bar();     // the attention output panel is complete: the state a POST kernel starts from
         out_proj_block(p.bias_o2, p.film_o2);
         ln_stats();
@@ -1055,7 +1003,7 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
         f32x4 acc[MT][NJ];
         init_bias(acc, aux + h * 128);
         gemm_tile(acc, panelA, D, KS);
-        if (h > 0 && !(ABL & 8)) chain_bar();  // every wave finished the linear2 partial of the previous chunk
+        if (h > 0) chain_bar();  // every wave finished the linear2 partial of the previous chunk
         {
           const int c = W4 * 32 + g * 8 + J0 * 4;  // first column inside the hidden chunk (col_of within the tile)
           auto gelu4 = [&](const f32x4 v) __attribute__((always_inline)) {
@@ -1072,14 +1020,12 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
             }
           }
         }
-        if (!(ABL & 8)) chain_bar();  // the hidden chunk is complete
+        chain_bar();  // the hidden chunk is complete
         gemm_group(facc, panelH, HLD, std::integral_constant<int, 2>{});
       }
       stamp(6);
-      if constexpr (!(ABL & 1024)) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) film_res(facc[t], t, p.bias_2, p.film_f);
-      }
+      for (int t = 0; t < NT; ++t) film_res(facc[t], t, p.bias_2, p.film_f);
       stamp(7);
       if (p.has_next == 2) {
         // final_layer on the finished rows: plain bf16 cast into the A panel, [BM x fin_n] GEMM, fp32 store
@@ -1103,8 +1049,7 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
               if (m0 + mt * 16 + l15 >= p.M || n >= p.fin_n) continue;
-              if constexpr (!(ABL & 1))
-                chain_st4(p.fin_out + (int64_t)row_m[mt] * p.ld_fin + n, acc[mt][j]);
+              chain_st4(p.fin_out + (int64_t)row_m[mt] * p.ld_fin + n, acc[mt][j]);
             }
           }
         }
@@ -1125,10 +1070,10 @@ __device__ __forceinline__ void chain_body(const ChainP& p, h16_t* const smem, c
   stamp(12);
 }
 
-template <int D, int MT, int MODE, int ABL = 0, int NW = 4>
+template <int D, int MT, int MODE, int NW = 4>
 __global__ __launch_bounds__(64 * NW, 1) void chain_kernel(const ChainP p) {
   __shared__ __attribute__((aligned(16))) h16_t smem[ChainLds<D, MT>::ELEMS];
-  chain_body<D, MT, MODE, ABL, NW>(p, smem, blockIdx.x * (16 * MT));
+  chain_body<D, MT, MODE, CHAIN_STAMPS, NW>(p, smem, blockIdx.x * (16 * MT));
 }
 
 // Two panel heights in ONE launch: workgroups [0, p.n_tall) take 16*MTA rows each, the rest 16*MTB (MTA > MTB).  A forward of
@@ -1140,7 +1085,7 @@ template <int D, int MTA, int MTB, int MODE, int NW>
 __global__ __launch_bounds__(64 * NW, 1) void chain_kernel_mix(const ChainP p) {
   __shared__ __attribute__((aligned(16))) h16_t smem[ChainLds<D, MTB>::ELEMS > ChainLds<D, MTA>::ELEMS ? ChainLds<D, MTB>::ELEMS : ChainLds<D, MTA>::ELEMS];
   const int b = blockIdx.x;   // wave-uniform
-  if (b < p.n_tall) chain_body<D, MTA, MODE, 0, NW>(p, smem, b * (16 * MTA));
-  else chain_body<D, MTB, MODE, 0, NW>(p, smem, p.n_tall * (16 * MTA) + (b - p.n_tall) * (16 * MTB));
+  if (b < p.n_tall) chain_body<D, MTA, MODE, false, NW>(p, smem, b * (16 * MTA));
+  else chain_body<D, MTB, MODE, false, NW>(p, smem, p.n_tall * (16 * MTA) + (b - p.n_tall) * (16 * MTB));
 }
 #pragma clang fp contract(fast)

@@ -24,7 +24,7 @@
 //     column map writes as 64-byte runs anyway.
 //
 // Round 6 (docs/lab_notebook_r6.md sections 12-14), each bit-identical to what it replaces:
-//   * THE FEED-FORWARD BLOCK HAS NO WORKGROUP BARRIER (CHAIN4_FFN_PIPE): per-chunk LDS counters, two chunk buffers (the second over LDS that is dead during the block), the
+//   * THE FEED-FORWARD BLOCK HAS NO WORKGROUP BARRIER: per-chunk LDS counters, two chunk buffers (the second over LDS that is dead during the block), the
 //     two waves of a SIMD one chunk apart so that one computes the GELU while the other issues MFMAs; the stream is packed per wave group.
 //   * LAST = 2: final_layer (model/diffusion.py:397) inside the last decoder layer's POST kernel, as a split-operand exact island on the rows in registers.
 //   * MODE = CHAIN_IN: input permute + input_projection (model/diffusion.py:345-346,364) + layer 0's PRE work in one launch.
@@ -38,31 +38,9 @@
 #pragma clang fp contract(off)
 
 #define CHAIN4_PF 8            // half stages in flight per wave (register ring); every GEMM of a chain consumes a multiple of it
-#ifndef CHAIN4_ASM_ALL
-#define CHAIN4_ASM_ALL 0     // A/B builds: inline-asm panel-fragment reads in every tall kernel (default: the 80-row POST kernel only)
-#endif
-#ifndef CHAIN4_PF_MID
 #define CHAIN4_PF_MID 16       // ... of the 48-row MID kernel, which has the registers (208 used): 27.2 -> 26.4 us at B=8 (profiles/r05_chain4_mid_ring16_ab.txt);
                                // at 80 rows a 16-deep ring spills 37-71 registers (38 -> 52 us), at 64 rows it is unmeasured: both keep 8
-#endif
-#ifndef CHAIN4_PF_POST3
-#define CHAIN4_PF_POST3 8
-#endif
-#ifndef CHAIN4_PARK3
-#define CHAIN4_PARK3 0         // 48-row POST kernel with parked rows (frees 48 registers, e.g. for a 16-deep ring: CHAIN4_PF_POST3=16)
-#endif
-#ifndef CHAIN4_ABL
-#define CHAIN4_ABL 0           // scratch timing experiments (results wrong): 1 no weight loads after the ring is primed, 2 panel fragments read once per GEMM call, 4 the weight stream wraps inside its first 256 KiB (always L2-resident)
-#endif
-#define CHAIN4_HS_ELEMS 4096   // 128 output columns x 32 k: 8 KiB
-#ifndef CHAIN4_SPREAD
-#define CHAIN4_SPREAD 0        // stream layout: blocks of four half stages, a wave's four 1 KiB slices contiguous (4 KiB), the eight waves 4 KiB apart -- the eight requests of a
-                               // half stage go to eight different 4 KiB blocks instead of one 8 KiB run (0: [half stage][wave][lane], A/B)
-#endif
-
-#ifndef CHAIN4_FFN_PIPE
-#define CHAIN4_FFN_PIPE 1      // feed-forward block without workgroup barriers: per-chunk LDS counters, the two waves of a SIMD one phase apart (0: round-5 form, A/B)
-#endif
+#define CHAIN4_HS_ELEMS 4096   // 128 output columns x 32 k: 8 KiB; stream layout [half stage][wave][lane]
 
 template <int MT>
 struct Chain4Lds {
@@ -72,7 +50,7 @@ struct Chain4Lds {
   // block has half the chunk hand-offs.  The host packs the stream accordingly (a2p_lib_run.h: two POST streams).
   static constexpr int HC = MT <= 4 ? 256 : 128;
   // Epilogue block (fp32 offsets).  Operands that are dead once the feed-forward block starts come first: the SECOND hidden-chunk buffer
-  // (CHAIN4_FFN_PIPE) lies over the LayerNorm partials + those operands (+ PAD_F floats where that is not enough), so 80 rows still fit.
+  // of the feed-forward block lies over the LayerNorm partials + those operands (+ PAD_F floats where that is not enough), so 80 rows still fit.
   //   dead by the FFN: out_proj bias, norm-A gamma / beta, FiLM rows of the out_proj epilogue;  live: linear2 bias, norm-B gamma / beta, FiLM rows of the FFN epilogue
   // (FiLM blocks: [sequence A: scale 512 | shift 512][sequence B: scale 512 | shift 512])
   static constexpr int E_BIAS_O = 0, E_LNA_G = 512, E_LNA_B = 1024, E_FILM_O = 1536, E_DEAD_F = 3584;
@@ -117,7 +95,7 @@ __global__ __launch_bounds__(256) void chain4_pack_kernel(const ChainPackDesc* _
   for (int q = threadIdx.x; q < 512; q += 256) {
     const int w = q >> 6, lane = q & 63, i = lane & 15, g = lane >> 4;
     const int64_t h = blockIdx.x;
-    uint4* out = reinterpret_cast<uint4*>(dst) + (CHAIN4_SPREAD ? (h >> 2) * 2048 + w * 256 + (h & 3) * 64 + lane : h * 512 + q);
+    uint4* out = reinterpret_cast<uint4*>(dst) + (h * 512 + q);
     const ChainPackDesc d = descs[(w < 4 ? n : 0) + blockIdx.x];
     const int w4 = w >> 1, J = w & 1, tile = d.row0 >> 7;
     const int row = d.omap ? (tile >> 1) * 256 + w4 * 64 + J * 32 + (tile & 1) * 16 + i : d.row0 + w4 * 32 + (i >> 2) * 8 + J * 4 + (i & 3);
@@ -129,7 +107,7 @@ __global__ __launch_bounds__(256) void chain4_pack_kernel(const ChainPackDesc* _
 
 template <int MT, int MODE, int LAST>
 __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, const int m0) {
-  constexpr int D = 512, NW = 8, CW = 16, BM = 16 * MT, NT = 4, KC = D / 32, FT = 8, HLD = Chain4Lds<MT>::HC, NH = HLD / 128, PF = (MODE == CHAIN_MID && MT == 3) ? CHAIN4_PF_MID : (MODE == CHAIN_POST && MT == 3) ? CHAIN4_PF_POST3 : CHAIN4_PF;
+  constexpr int D = 512, NW = 8, CW = 16, BM = 16 * MT, NT = 4, KC = D / 32, FT = 8, HLD = Chain4Lds<MT>::HC, NH = HLD / 128, PF = (MODE == CHAIN_MID && MT == 3) ? CHAIN4_PF_MID : CHAIN4_PF;
   using LY = Chain4Lds<MT>;
   constexpr int AUX_F = LY::AUX_F;
   constexpr int E4_BIAS_O = LY::E_BIAS_O, E4_BIAS_2 = LY::E_BIAS_2, E4_LNA_G = LY::E_LNA_G, E4_LNB_G = LY::E_LNB_G, E4_FILM_O = LY::E_FILM_O, E4_FILM_F = LY::E_FILM_F;
@@ -138,7 +116,7 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
   float* const red = reinterpret_cast<float*>(panelH + BM * HLD);   // [2][8][BM] LayerNorm partial sums, one per wave
   float* const epi = red + LY::RED_F;                                 // [EPI_F] epilogue operands (Chain4Lds::E_*)
   float* const aux = epi + LY::EPI_F;                                 // [AUX_F] per-tile biases of the stored / FFN GEMMs
-  uint32_t* const flags = reinterpret_cast<uint32_t*>(aux + AUX_F);   // [2][16] chunk counters of the feed-forward block (CHAIN4_FFN_PIPE)
+  uint32_t* const flags = reinterpret_cast<uint32_t*>(aux + AUX_F);   // [2][16] chunk counters of the feed-forward block
   h16_t* const panelH1 = reinterpret_cast<h16_t*>(red);               // second hidden-chunk buffer: over red + the epilogue operands that are dead by then
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), l15 = lane & 15, g = lane >> 4;
   const int W4 = wid >> 1, J0 = wid & 1;
@@ -157,15 +135,11 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
   stamp(0);
 
   // ---- weight stream: register ring of PF half stages --------------------------------------------------------------------
-  uint32_t woff = CHAIN4_SPREAD ? (uint32_t)(wid * 4096 + lane * 16) : (uint32_t)(wid * 64 + lane) * 16;   // byte offset of this lane's 16 bytes of the next half stage to load
+  uint32_t woff = (uint32_t)(wid * 64 + lane) * 16;   // byte offset of this lane's 16 bytes of the next half stage to load
   h16x8 wr[PF];
-  bool w_primed = false;
   auto w_issue = [&](int slot) __attribute__((always_inline)) {
-    if ((CHAIN4_ABL & 1) && w_primed) { asm volatile("" : "+v"(wr[slot])); return; }
-    if (CHAIN4_ABL & 4) wr[slot] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const char*>(p.stream) + (woff & 0x3ffffu));   // (every half stage from the first 256 KiB: L2 hits by construction)
-    else wr[slot] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const char*>(p.stream) + woff);   // uniform base + 32-bit offset
-    // the host pads the stream behind the last half stage.  (SPREAD: every GEMM starts on a multiple of the ring depth, so slot & 3 is the half stage's place in its block of four)
-    woff += CHAIN4_SPREAD ? ((slot & 3) == 3 ? 32768u - 3072u : 1024u) : CHAIN4_HS_ELEMS * 2;
+    wr[slot] = *reinterpret_cast<const h16x8*>(reinterpret_cast<const char*>(p.stream) + woff);   // uniform base + 32-bit offset
+    woff += CHAIN4_HS_ELEMS * 2;   // the host pads the stream behind the last half stage
   };
 
   // ---- helpers -----------------------------------------------------------------------------------------------------------
@@ -234,7 +208,7 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
   auto gemm = [&](auto ntg_c, auto nkc_c, auto pld_c, auto& acc, const h16_t* P, bool swap) __attribute__((always_inline)) {
     constexpr int NTG = decltype(ntg_c)::value, NKC = decltype(nkc_c)::value, PLD = decltype(pld_c)::value;
     static_assert((NTG * NKC) % PF == 0 && PF % NTG == 0, "ring phase");
-    constexpr bool ASM_FRAGS = CHAIN4_ASM_ALL || (MT == 5 && MODE == CHAIN_POST);
+    constexpr bool ASM_FRAGS = MT == 5 && MODE == CHAIN_POST;
     if constexpr (ASM_FRAGS) {
       constexpr int RSTEP = 32 * PLD;   // bytes between the 16-row blocks of a panel
       const uint32_t rp = lds_off(P) + (uint32_t)(l15 * PLD * 2);
@@ -286,10 +260,7 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
       for (int c = 0; c < NKC; ++c) {
         if (c + 1 < NKC) {
 #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) {
-            if (CHAIN4_ABL & 2) { a[(c + 1) & 1][mt] = a[c & 1][mt]; asm volatile("" : "+v"(a[(c + 1) & 1][mt])); }
-            else a[(c + 1) & 1][mt] = *reinterpret_cast<const h16x8*>(rp + aswz[(c + 1) & 3] + ((c + 1) >> 2) * 256 + mt * rstep);
-          }
+          for (int mt = 0; mt < MT; ++mt) a[(c + 1) & 1][mt] = *reinterpret_cast<const h16x8*>(rp + aswz[(c + 1) & 3] + ((c + 1) >> 2) * 256 + mt * rstep);
         }
 #pragma unroll
         for (int t = 0; t < NTG; ++t) {
@@ -347,7 +318,6 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
   }
 #pragma unroll
   for (int i = 0; i < PF; ++i) w_issue(i);
-  w_primed = true;
   if constexpr (MODE == CHAIN_IN) {
     // The noisy input x [B][256][T] (model/diffusion.py:345-346: permute to [T][256]) as the split operand panel [BM][hi 256 | lo 256] over the A panel: wave w takes
     // channels 32 w .. 32 w + 31, lane = panel row (consecutive frames: each load instruction reads BM contiguous floats of one channel).  What pack_input_split3_kernel
@@ -631,7 +601,7 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
     stamp(3);
   }
   // POST kernels that park their rows around the feed-forward block: the store leaves here, in front of the LayerNorm (see the second park below for why)
-  constexpr bool PARK_FFN = MODE == CHAIN_POST && (MT >= 4 || CHAIN4_PARK3);
+  constexpr bool PARK_FFN = MODE == CHAIN_POST && MT >= 4;
   if constexpr (PARK_FFN) {
     if (!p.x_in_tiled) chain_bar();   // (parked in the tiled layout: with a row-major predecessor layout -- A/B only -- other lanes' unread bytes lie under the store)
     store_x(R, 1);
@@ -651,7 +621,7 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
     // 64 / 80-row panels: the rows are PARKED (stored, re-read) around the feed-forward block and again around the [Q|K] GEMM -- 80 registers
     // per lane that the linear2 partials / the four-tile groups need.  At 48 rows they stay in registers from load to the final
     // store (X), as in kernels_chain.h: no extra traffic, and no store in front of a GEMM's weight loads.
-    constexpr bool PARK = MT >= 4 || CHAIN4_PARK3;   // (64 rows without parking: 91 registers spilled)
+    constexpr bool PARK = MT >= 4;   // (64 rows without parking: 91 registers spilled)
     if constexpr (MODE != CHAIN_IN) {   // (CHAIN_IN: the rows just computed go straight to layer 0's PRE work below)
     ln_write(R, E4_LNA_G, F);
     [[maybe_unused]] f32x4 X[PARK ? 1 : NT][PARK ? 1 : MT];
@@ -671,7 +641,6 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) R[t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if CHAIN4_FFN_PIPE
     // No workgroup barrier inside the block.  Per hidden chunk two LDS counters: ready[c] = waves whose GELU'd columns of chunk c are in the buffer,
     // done[c] = waves that have read chunk c for their linear2 partial.  Two chunk buffers (c & 1).  The waves w and w + 4 share a SIMD; waves 0-3 run
     // their linear2 partial ONE CHUNK LATE (linear1(c+1) -> GELU(c+1) -> linear2(c)), waves 4-7 in the natural order (linear1(c) -> GELU(c) -> linear2(c)):
@@ -741,37 +710,6 @@ __device__ __forceinline__ void chain4_body(const ChainP& p, h16_t* const smem, 
       }
       wait_all(64u + 4u * (NC - 1));   // the second chunk buffer lies over the LayerNorm partials: nobody reads it any more
     }
-#else
-#pragma unroll
-    for (int h = 0; h < FT / NH; ++h) {
-      f32x4 acc[NH][MT];
-#pragma unroll
-      for (int tt = 0; tt < NH; ++tt) {
-        const f32x4 b = *reinterpret_cast<const f32x4*>(aux + (h * NH + tt) * 128 + W4 * 32 + g * 8 + J0 * 4);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[tt][mt] = b;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      gemm(std::integral_constant<int, NH>{}, std::integral_constant<int, KC>{}, std::integral_constant<int, D>{}, acc, panelA, false);
-      __builtin_amdgcn_sched_barrier(0);
-      if (13 + 3 * h < 28) stamp(13 + 3 * h);       // (stamped builds: linear1 of this hidden chunk done in wave 0)
-      if (h > 0) chain_bar();   // every wave finished the linear2 partial of the previous chunk
-#pragma unroll
-      for (int tt = 0; tt < NH; ++tt)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          const f32x4 v = acc[tt][mt];
-          *reinterpret_cast<h16x4*>(panelH + (mt * 16 + l15) * HLD + tt * 128 + pswz) =
-              h16x4{(h16_t)act_gelu_fast(v[0]), (h16_t)act_gelu_fast(v[1]), (h16_t)act_gelu_fast(v[2]), (h16_t)act_gelu_fast(v[3])};
-        }
-      chain_bar();              // the hidden chunk is complete
-      if (14 + 3 * h < 29) stamp(14 + 3 * h);       // (GELU + both barriers)
-      __builtin_amdgcn_sched_barrier(0);
-      gemm(std::integral_constant<int, NT>{}, std::integral_constant<int, HLD / 32>{}, std::integral_constant<int, HLD>{}, R, panelH, false);
-      __builtin_amdgcn_sched_barrier(0);
-      if (15 + 3 * h < 30) stamp(15 + 3 * h);       // (linear2 partial)
-    }
-#endif
     stamp(6);
     if constexpr (PARK) {
       // the parked rows come back from where store_x left them (same workgroup, same lanes: program order makes them visible)

@@ -74,32 +74,6 @@ template <int DH> void shape(int nseq, int T, int S_main, int S_tail, int shared
          sqrt(num / (den + 1e-30)), mx, nan, f1, f2);
   CK(hipFree(q)); CK(hipFree(k)); CK(hipFree(vt)); CK(hipFree(o1)); CK(hipFree(o2)); CK(hipFree(kt)); CK(hipFree(vtl)); CK(hipFree(stat));
 }
-#ifdef ATTN3_ABL
-template <int ABL> float abl_time(AttnP a, int H, int nseq) {
-  return time_it([&] { attn3_kernel<64, ABL><<<dim3(a.nq * H * nseq), 256>>>(a); });
-}
-void ablate() {
-  const int DH = 64, nseq = 16, T = 600, S_main = 2000, H = 8, d = H * DH, Sld = 2048;
-  h16_t *q, *k, *vt, *o;
-  CK(hipMalloc(&q, (size_t)nseq * T * d * 2)); CK(hipMalloc(&k, (size_t)(nseq + 1) * Sld * d * 2)); CK(hipMalloc(&vt, (size_t)(nseq + 1) * d * Sld * 2));
-  CK(hipMalloc(&o, (size_t)nseq * T * d * 2));
-  std::vector<uint16_t> h((size_t)(nseq + 1) * Sld * d);
-  for (auto& v : h) v = rnd_h(1.0f);
-  CK(hipMemcpy(k, h.data(), h.size() * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(vt, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-  CK(hipMemcpy(q, h.data(), (size_t)nseq * T * d * 2, hipMemcpyHostToDevice));
-  AttnP a; memset(&a, 0, sizeof(a));
-  a.Q = q; a.q_seq_stride = (int64_t)T * d; a.ldq = d; a.K = k; a.k_slot_stride = (int64_t)Sld * d; a.ldk = d;
-  a.VT = vt; a.vt_slot_stride = (int64_t)d * Sld; a.ldvt = Sld; a.O = o; a.o_seq_stride = (int64_t)T * d; a.ldo = d;
-  a.tail_mod = nseq; a.Tq = T; a.S_main = S_main; a.S_tail = 0; a.scale_log2e = 1.4426950408889634f / 8.0f;
-  a.slot_rule = 1; a.nheads = H; a.nseq = nseq; a.xcd_remap = 1; a.nq = (T + 319) / 320;
-  printf("attn3 ablation (us): full %.1f | no exp %.1f | no max %.1f | no sum/cvt.. %.1f | no exp,max,sum %.1f | no PV %.1f | no QK %.1f | no MFMA %.1f | skeleton (no MFMA, no softmax) %.1f | skeleton no DMA %.1f | skeleton no DMA no barrier %.1f | full no DMA %.1f\n",
-         abl_time<0>(a, H, nseq), abl_time<1>(a, H, nseq), abl_time<2>(a, H, nseq), abl_time<32>(a, H, nseq), abl_time<35>(a, H, nseq), abl_time<8>(a, H, nseq),
-         abl_time<16>(a, H, nseq), abl_time<24>(a, H, nseq), abl_time<59>(a, H, nseq), abl_time<59 | 64>(a, H, nseq), abl_time<59 | 64 | 128>(a, H, nseq), abl_time<64>(a, H, nseq));
-}
-#endif
-#ifndef A3_ABL
-#define A3_ABL 0
-#endif
 #ifdef A3_WGSTAMPS
 // per-workgroup timeline of one launch (wave 0 of every workgroup): when it started, how long its prologue / loop / epilogue took
 template <int DH> void wg_timeline(const char* name, int nseq, int T, int S_main, int S_tail, int shared_slot0, int nt) {
@@ -122,7 +96,7 @@ template <int DH> void wg_timeline(const char* name, int nseq, int T, int S_main
   const int nwg = a.nq * H * nseq;
   CK(hipMalloc(&dbg, (size_t)nwg * 64)); CK(hipMemset(dbg, 0, (size_t)nwg * 64));
   a.kv_slot = (const int*)dbg;
-  const float us = time_it([&] { attn3_kernel<DH, A3_ABL><<<dim3(nwg), 256>>>(a); });
+  const float us = time_it([&] { attn3_kernel<DH><<<dim3(nwg), 256>>>(a); });
   std::vector<long long> hd((size_t)nwg * 8);
   CK(hipMemcpy(hd.data(), dbg, hd.size() * 8, hipMemcpyDeviceToHost));
   long long t0 = hd[0], t3 = hd[3];
@@ -161,34 +135,6 @@ int main(int argc, char** argv) {
     return 0;
   }
 #endif
-#ifdef ATTN3_ABL
-  if (argc > 1 && !strcmp(argv[1], "abl")) { ablate(); return 0; }
-#endif
-  if (argc > 1 && !strcmp(argv[1], "sk")) {   // skeleton experiments: tile DMA / barriers / cache policy (timing only)
-    const int DH = 64, nseq = 16, T = 600, S_main = 2000, H = 8, d = H * DH, Sld = 2048;
-    h16_t *q, *k, *vt, *o;
-    CK(hipMalloc(&q, (size_t)nseq * T * d * 2)); CK(hipMalloc(&k, (size_t)(nseq + 1) * Sld * d * 2)); CK(hipMalloc(&vt, (size_t)(nseq + 1) * d * Sld * 2));
-    CK(hipMalloc(&o, (size_t)nseq * T * d * 2));
-    std::vector<uint16_t> h((size_t)(nseq + 1) * Sld * d);
-    for (auto& v : h) v = rnd_h(1.0f);
-    CK(hipMemcpy(k, h.data(), h.size() * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(vt, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    CK(hipMemcpy(q, h.data(), (size_t)nseq * T * d * 2, hipMemcpyHostToDevice));
-    AttnP a; memset(&a, 0, sizeof(a));
-    a.Q = q; a.q_seq_stride = (int64_t)T * d; a.ldq = d; a.K = k; a.k_slot_stride = (int64_t)Sld * d; a.ldk = d;
-    a.VT = vt; a.vt_slot_stride = (int64_t)d * Sld; a.ldvt = Sld; a.O = o; a.o_seq_stride = (int64_t)T * d; a.ldo = d;
-    a.tail_mod = nseq; a.Tq = T; a.S_main = S_main; a.S_tail = 0; a.scale_log2e = 1.4426950408889634f / 8.0f;
-    a.nheads = H; a.nseq = nseq; a.xcd_remap = 1; a.nq = (T + 319) / 320;
-    for (int rule = 1; rule <= 3; rule += 2)
-      for (int nt = 0; nt < 2; ++nt) {
-        a.slot_rule = rule; a.slot_b = nseq / 2; a.kv_stream = nt;
-        const float t0 = time_it([&] { attn3_kernel<64, 0><<<dim3(a.nq * H * nseq), 256>>>(a); });
-        const float t1 = time_it([&] { attn3_kernel<64, 64><<<dim3(a.nq * H * nseq), 256>>>(a); });
-        const float t2 = time_it([&] { attn3_kernel<64, 128><<<dim3(a.nq * H * nseq), 256>>>(a); });
-        const float t3 = time_it([&] { attn3_kernel<64, 192><<<dim3(a.nq * H * nseq), 256>>>(a); });
-        printf("A3X=%d slot_rule=%d nt=%d: full skeleton %.1f us | no tile DMA %.1f | no barrier %.1f | neither %.1f\n", A3X, rule, nt, t0, t1, t2, t3);
-      }
-    return 0;
-  }
 #ifdef A3_STAMPS
   if (argc > 1 && !strcmp(argv[1], "st")) {
     const int DH = 64, nseq = 16, T = 600, S_main = 1984, H = 8, d = H * DH, Sld = 2048;   // 31 full tiles, no partial tile

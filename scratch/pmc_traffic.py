@@ -27,7 +27,7 @@ def one(name_part):
     if not ks: return None
     k = ks[0]
     return fetch[k] * 1024 * 2, write.get(k, 0) * 1024
-names = {"pre": "chain4_kernel<3, 4, 0>", "mid1": "chain_kernel<512, 3, 1, 0, 8>", "post1": "chain_kernel<512, 3, 2, 0, 8>",
+names = {"pre": "chain4_kernel<3, 4, 0>", "mid1": "chain_kernel<512, 3, 1, 8>", "post1": "chain_kernel<512, 3, 2, 8>",
          "mid4": "chain4_kernel<3, 1, 0>", "post4": "chain4_kernel<3, 2, 0>", "last4": "chain4_kernel<3, 2, 2>"}
 v = {k: one(n) for k, n in names.items()}
 fam = {}
