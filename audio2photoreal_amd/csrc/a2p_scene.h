@@ -11,10 +11,7 @@ extern "C" int a2p_scene_render(const a2p_scene_body* bodies, int32_t P, const i
   const char* who = "scene_render";
   ARG(bodies && faces && K && Rt && proj && key && out && alpha && depth && body_alpha, "%s: null argument", who);
   ARG(P >= 1 && P <= A2P_SCENE_MAX_BODIES, "%s: P=%d bodies: need 1 <= P <= %d", who, P, A2P_SCENE_MAX_BODIES);
-  ARG(S >= 1 && S <= A2P_RENDER_MAX_SUPERSAMPLE, "%s: S=%d samples per axis: need 1 <= S <= %d", who, S, A2P_RENDER_MAX_SUPERSAMPLE);
-  ARG(H >= 1 && W >= 1 && (int64_t)S * H <= A2P_RENDER_MAX_SIZE && (int64_t)S * W <= A2P_RENDER_MAX_SIZE,
-      "%s: a %d x %d image at S=%d: need 1 <= H, W and S H, S W <= %d", who, H, W, S, A2P_RENDER_MAX_SIZE);
-  ARG(near > 0.0f && near < __builtin_inff(), "%s: near=%g: need a positive finite distance", who, (double)near);
+  CHK(render_samples(who, H, W, S, near));
   int64_t pblocks;
   CHK(render_pixel_grid(who, N, C, H, W, &pblocks));
   SceneDesc d = {};
@@ -40,26 +37,14 @@ extern "C" int a2p_scene_render(const a2p_scene_body* bodies, int32_t P, const i
     d.body[p].v0 = d.body[p].f0 = 0x7fffffff;
   }
   d.P = P, d.V = (int)sumV, d.F = (int)sumF;
-  const int64_t vtiles = render_tiles(sumV), fblocks = render_tiles(sumF), sH = (int64_t)S * H, sW = (int64_t)S * W;
-  ARG(N * vtiles <= 0x7fffffff && N * fblocks <= 0x7fffffff, "%s: N=%lld frames x %lld vertex tiles or %lld face blocks exceed the grid", who,
-      (long long)N, (long long)vtiles, (long long)fblocks);
-  const void* outs[] = {proj, key, out, alpha, depth, body_alpha};
-  for (int a = 0; a < 6; ++a) {
-    const void* shared[] = {faces, K, Rt, bg};
-    for (int b = 0; b < 4; ++b) ARG(outs[a] != shared[b], "%s: a scratch or output array must not alias an input", who);
-    for (int p = 0; p < P; ++p) {
-      const void* ins[] = {bodies[p].verts, bodies[p].placement, bodies[p].tex, bodies[p].vt, bodies[p].vti};
-      for (int b = 0; b < 5; ++b) ARG(outs[a] != ins[b], "%s: a scratch or output array must not alias an input", who);
-    }
-    for (int b = 0; b < a; ++b) ARG(outs[a] != outs[b], "%s: the scratch and output arrays must be distinct", who);
-  }
+  CHK(render_mesh_grid(who, N, sumV, sumF));
+  const SceneBody* b = d.body;                                       // entries P.. repeat the last body: they add no array
+  CHK(render_distinct(who, {proj, key, out, alpha, depth, body_alpha},
+                      {faces, K, Rt, bg, b[0].verts, b[0].place, b[0].tex, b[0].vt, b[0].vti, b[1].verts, b[1].place, b[1].tex, b[1].vt, b[1].vti,
+                       b[2].verts, b[2].place, b[2].tex, b[2].vt, b[2].vti, b[3].verts, b[3].place, b[3].tex, b[3].vt, b[3].vti}));
   if (N == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
-  scene_project_kernel<<<(unsigned)(N * vtiles), RENDER_THREADS, 0, s>>>(d, (int)vtiles, K, k_per_frame ? 9 : 0, Rt, rt_per_frame ? 12 : 0,
-                                                                         (float)S, proj);
-  HIPCHK(hipMemsetAsync(key, 0xff, (size_t)(N * sH * sW) * sizeof(uint64_t), s));
-  render_cover_kernel<<<(unsigned)(N * fblocks), RENDER_THREADS, 0, s>>>(proj, d.V, faces, d.F, (int)fblocks, (int)sH, (int)sW, near,
-                                                                         (unsigned long long*)key);
+  CHK(render_front(&d, nullptr, d.V, faces, d.F, N, K, k_per_frame, Rt, rt_per_frame, H, W, S, near, proj, key, s));
   scene_resolve_kernel<<<(unsigned)(N * pblocks), RENDER_THREADS, 0, s>>>(d, proj, faces, (const unsigned long long*)key, H, W, S,
                                                                           (int)pblocks, C, bg, bg_per_frame ? (int64_t)C * H * W : 0, out,
                                                                           alpha, depth, body_alpha);

@@ -32,14 +32,17 @@ __device__ __forceinline__ void render_project_vertex(const float* __restrict__ 
   proj[o + 2] = zc;
 }
 
-__global__ __launch_bounds__(RENDER_THREADS) void render_project_kernel(
+// k * scale is one float32 multiplication: scale = S gives K' = K with its first two rows times S, the camera of the S H x S W sample
+// grid (kernels_render_aa.h), the same bits as a K' the caller had scaled in float32; scale = 1 changes no bit (the plain rasteriser).
+__global__ __launch_bounds__(RENDER_THREADS) void render_project_scaled_kernel(
     const float* __restrict__ verts, int V, int tiles, const float* __restrict__ K, int64_t k_stride,
-    const float* __restrict__ Rt, int64_t rt_stride, float* __restrict__ proj) {
+    const float* __restrict__ Rt, int64_t rt_stride, float scale, float* __restrict__ proj) {
   const int64_t n = blockIdx.x / tiles;
   const int v = (blockIdx.x % tiles) * RENDER_THREADS + threadIdx.x;
   if (v >= V) return;
   const float* k = K + n * k_stride;
-  render_project_vertex(verts, Rt + n * rt_stride, k[0], k[1], k[2], k[4], k[5], 3 * (n * V + v), proj);
+  render_project_vertex(verts, Rt + n * rt_stride, k[0] * scale, k[1] * scale, k[2] * scale, k[4] * scale, k[5] * scale,
+                        3 * (n * V + v), proj);
 }
 
 // One projected face: corners (u, v, z) and twice its signed screen area.
@@ -78,6 +81,51 @@ __device__ __forceinline__ bool render_pixel(const RenderFace& t, int i, int j, 
   qc = w0 / t.cz;
   depth = t.area / (qa + qb + qc);
   return depth > 0.0f && depth < __builtin_inff();                 // false for a NaN too: such a pixel is not covered
+}
+
+// The perspective-correct barycentrics q / s of a pixel (or sample) the face won: every resolve computes them here.
+__device__ __forceinline__ void render_barycentrics(const RenderFace& t, int i, int j, float& b0, float& b1, float& b2) {
+  float qa, qb, qc, d;
+  render_pixel(t, i, j, qa, qb, qc, d);
+  const float s = qa + qb + qc;
+  b0 = qa / s, b1 = qb / s, b2 = qc / s;
+}
+
+// Where a uv falls in a texture plane [Ht, Wt]: the north-west texel (yi, xi), whether its east / south neighbours exist, and the
+// weights of the taps nw, ne, sw, se: (1 - fy)(1 - fx), (1 - fy) fx, fy (1 - fx), fy fx of the position's fractions.
+struct RenderTaps {
+  int xi, yi;
+  bool east, south;
+  float nw, ne, sw, se;
+};
+
+// uv = b0 t0 + b1 t1 + b2 t2 (v <- 1 - v when flip_v); sample position x = u (Wt - 1), y = v (Ht - 1), clamped to the border.
+__device__ __forceinline__ RenderTaps render_taps(float b0, float b1, float b2, const float* __restrict__ t0, const float* __restrict__ t1,
+                                                  const float* __restrict__ t2, int Ht, int Wt, int flip_v) {
+  const float u = b0 * t0[0] + b1 * t1[0] + b2 * t2[0];
+  float v = b0 * t0[1] + b1 * t1[1] + b2 * t2[1];
+  if (flip_v) v = 1.0f - v;
+  // fmaxf first: a NaN becomes 0, so the taps stay inside the plane whatever the inputs hold
+  const float x = fminf(fmaxf(u * (float)(Wt - 1), 0.0f), (float)(Wt - 1));
+  const float y = fminf(fmaxf(v * (float)(Ht - 1), 0.0f), (float)(Ht - 1));
+  const float xw = floorf(x), yn = floorf(y);
+  const float w = x - xw, e = 1.0f - w, s = y - yn, nn = 1.0f - s;
+  RenderTaps k;
+  k.xi = (int)xw, k.yi = (int)yn;
+  k.east = k.xi + 1 <= Wt - 1, k.south = k.yi + 1 <= Ht - 1;
+  k.nw = nn * e, k.ne = nn * w, k.sw = s * e, k.se = s * w;
+  return k;
+}
+
+// One channel: p is texel (yi, xi) of the channel's plane.  nw + ne + sw + se of the weighted taps in that order, where the ne
+// product is rounded and every other product is fused into the sum (one rounding each).  That is the contraction the compiler chose
+// for this expression since the first renderer; it is spelled with fmaf so that every kernel gets the same bits wherever the
+// optimiser meets the products.  A tap outside the image (the east / south tap of a position on the last column / row, weight 0)
+// counts 0 and is not read.
+__device__ __forceinline__ float render_tap_sum(const float* __restrict__ p, int Wt, const RenderTaps& k) {
+  float a = fmaf(p[0], k.nw, (k.east ? p[1] : 0.0f) * k.ne);
+  a = fmaf(k.south ? p[Wt] : 0.0f, k.sw, a);
+  return fmaf(k.east && k.south ? p[Wt + 1] : 0.0f, k.se, a);
 }
 
 // The pixels a face can cover: those whose centre lies in the box of its corners, clipped to the image.  floor / ceil round
@@ -162,10 +210,7 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_resolve_kernel(
     const int pix = (int)(t % hw);
     f = (int)(unsigned)(k & 0xffffffffull);
     const RenderFace tri = render_load_face(proj + n * V * 3, vi + 3 * (int64_t)f);
-    float qa, qb, qc, d;
-    render_pixel(tri, pix / W, pix % W, qa, qb, qc, d);
-    const float s = qa + qb + qc;
-    b0 = qa / s, b1 = qb / s, b2 = qc / s;
+    render_barycentrics(tri, pix / W, pix % W, b0, b1, b2);
     z = __uint_as_float((unsigned)(k >> 32));
   }
   if (face) face[t] = f;
@@ -202,10 +247,8 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_interpolate_kernel(
   for (int c = 0; c < C; ++c) o[c * HW] = b0 * x0[c] + b1 * x1[c] + b2 * x2[c];
 }
 
-// Pass C2.  The same grid.  Pixel uv = b0 vt[t0] + b1 vt[t1] + b2 vt[t2] with (t0, t1, t2) = vti[face] (v <- 1 - v when flip_v);
-// sample position x = u (Wt - 1), y = v (Ht - 1) on tex [., C, Ht, Wt] as given, clamped to the border; the taps nw, ne, sw, se
-// weighted (1 - fy)(1 - fx), (1 - fy) fx, fy (1 - fx), fy fx are summed in that order, a tap outside the image (the east / south
-// tap of a position on the last column / row, weight 0) counting 0.  out [N, C, H, W], 0 where the face is outside [0, F).
+// Pass C2.  The same grid.  The pixel's uv from the corners (t0, t1, t2) = vti[face] of vt, sampled bilinearly on tex [., C, Ht, Wt]
+// as given: render_taps and render_tap_sum above.  out [N, C, H, W], 0 where the face is outside [0, F).
 __global__ __launch_bounds__(RENDER_THREADS) void render_texture_kernel(
     const int* __restrict__ face, const float* __restrict__ bary, int64_t HW, int pblocks, const float* __restrict__ vt,
     const int* __restrict__ vti, int F, const float* __restrict__ tex, int64_t tex_stride, int C, int Ht, int Wt, int flip_v,
@@ -224,24 +267,8 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_texture_kernel(
   const float* t0 = vt + 2 * (int64_t)vti[3 * (int64_t)f];
   const float* t1 = vt + 2 * (int64_t)vti[3 * (int64_t)f + 1];
   const float* t2 = vt + 2 * (int64_t)vti[3 * (int64_t)f + 2];
-  const float u = b0 * t0[0] + b1 * t1[0] + b2 * t2[0];
-  float v = b0 * t0[1] + b1 * t1[1] + b2 * t2[1];
-  if (flip_v) v = 1.0f - v;
-  // fmaxf first: a NaN becomes 0, so the taps stay inside the plane whatever the inputs hold
-  const float x = fminf(fmaxf(u * (float)(Wt - 1), 0.0f), (float)(Wt - 1));
-  const float y = fminf(fmaxf(v * (float)(Ht - 1), 0.0f), (float)(Ht - 1));
-  const float xw = floorf(x), yn = floorf(y);
-  const float w = x - xw, e = 1.0f - w, s = y - yn, nn = 1.0f - s;
-  const int xi = (int)xw, yi = (int)yn;
-  const bool east = xi + 1 <= Wt - 1, south = yi + 1 <= Ht - 1;
+  const RenderTaps k = render_taps(b0, b1, b2, t0, t1, t2, Ht, Wt, flip_v);
   const int64_t plane = (int64_t)Ht * Wt;
-  const float* img = tex + n * tex_stride + (int64_t)yi * Wt + xi;
-  for (int c = 0; c < C; ++c) {
-    const float* p = img + c * plane;
-    float a = p[0] * (nn * e);
-    a += (east ? p[1] : 0.0f) * (nn * w);
-    a += (south ? p[Wt] : 0.0f) * (s * e);
-    a += (east && south ? p[Wt + 1] : 0.0f) * (s * w);
-    o[c * HW] = a;
-  }
+  const float* img = tex + n * tex_stride + (int64_t)k.yi * Wt + k.xi;
+  for (int c = 0; c < C; ++c) o[c * HW] = render_tap_sum(img + c * plane, Wt, k);
 }

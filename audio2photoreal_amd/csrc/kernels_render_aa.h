@@ -1,24 +1,14 @@
 // Anti-aliased rendered images (audio2photoreal_amd/render.py render_antialiased / interpolate_antialiased; INTEGRATION.md "Rendered
 // images", the supersampling rule).  S samples per axis: sample (a, b) of pixel (i, j) is pixel (S i + a, S j + b) of the S H x S W
-// image seen through K' = K with its first two rows times S in float32.  Projection, key fill and cover pass run unchanged on that
-// grid (kernels_render.h); the one kernel here reads the [N, S H, S W] keys and writes only the [N, C, H, W] image and its coverage.
+// image seen through K' = K with its first two rows times S in float32.  Projection (scale S), key fill and cover pass run unchanged
+// on that grid (kernels_render.h); the one pass here reads the [N, S H, S W] keys and writes only the [N, C, H, W] image, its coverage
+// and its depth.  What a sample is shaded from is a source type: hold(f) takes up face f when the walk reaches another face,
+// sample(b0, b1, b2) one sample's barycentrics, channel(c) gives that sample's value in channel c.  All members are inlined and the
+// type is a template argument: no kernel branches on the kind of source.
 #pragma once
 #include "kernels_render.h"
 
-// Pass 0 at S samples per axis: render_project_kernel through K'.  k * scale is one float32 multiplication, the same bits as a K'
-// the caller had scaled in float32 (scale 1 changes nothing).
-__global__ __launch_bounds__(RENDER_THREADS) void render_project_scaled_kernel(
-    const float* __restrict__ verts, int V, int tiles, const float* __restrict__ K, int64_t k_stride,
-    const float* __restrict__ Rt, int64_t rt_stride, float scale, float* __restrict__ proj) {
-  const int64_t n = blockIdx.x / tiles;
-  const int v = (blockIdx.x % tiles) * RENDER_THREADS + threadIdx.x;
-  if (v >= V) return;
-  const float* k = K + n * k_stride;
-  render_project_vertex(verts, Rt + n * rt_stride, k[0] * scale, k[1] * scale, k[2] * scale, k[4] * scale, k[5] * scale,
-                        3 * (n * V + v), proj);
-}
-
-// What a sample is shaded from: a UV texture (TEX) or per-vertex values.  tab is vti [F, 3] for a texture and vi [F, 3] for values.
+// The kernel argument of render_aa_kernel: a UV texture (TEX) or per-vertex values.  tab is vti [F, 3] for a texture, vi for values.
 struct RenderAASource {
   const float* data;     // tex [N or 1, C, Ht, Wt] | values [N, V, C]
   int64_t stride;        // floats between the frames of data (0: shared)
@@ -27,37 +17,68 @@ struct RenderAASource {
   int Ht, Wt, flip_v;    // texture only
 };
 
-// Resolve + shade + downsample.  Grid pblocks * N (pblocks = ceil(H W / RENDER_THREADS)): a thread owns one output pixel of one
-// frame, consecutive lanes consecutive pixels of a plane, so the C + 1 (+ 1) plane stores are coalesced and a wave reads 64 S
-// contiguous keys of a sample row.  The samples are walked a outer, b inner; a sample's barycentrics are render_pixel's q / sum at
-// (S i + a, S j + b), as render_resolve_kernel computes them, its colour render_texture_kernel's / render_interpolate_kernel's
-// expression.  The face's corners, uv / value pointers are kept while consecutive samples hold the same face (most of a pixel's
-// samples do).  fp32 accumulators from 0; alpha = n / S^2, mean = acc / S^2 (divisions); n == S^2 -> mean (bg not read), n == 0 ->
-// bg, else mean + (1 - alpha) bg; without bg, mean.  Accumulators are indexed by unrolled constants only: registers, no scratch.
-template <bool TEX>
-__global__ __launch_bounds__(RENDER_THREADS) void render_aa_kernel(
-    const float* __restrict__ proj, int V, const int* __restrict__ vi, const unsigned long long* __restrict__ key, int H, int W, int S,
-    int pblocks, RenderAASource src, int C, const float* __restrict__ bg, int64_t bg_stride, float* __restrict__ out,
-    float* __restrict__ alpha, float* __restrict__ depth) {
-  const int64_t n = blockIdx.x / pblocks;
+// Per-vertex values: render_interpolate_kernel's expression on the value rows of the held face's corners.
+struct RenderValueSource {
+  const float* rows;     // values [V, C] of this frame
+  const int* tab;
+  int64_t C;
+  const float *c0 = nullptr, *c1 = nullptr, *c2 = nullptr;
+  float b0, b1, b2;
+  __device__ __forceinline__ RenderValueSource(const RenderAASource& s, int64_t n, int C) : rows(s.data + n * s.stride), tab(s.tab), C(C) {}
+  __device__ __forceinline__ void hold(int f) {
+    const int* t = tab + 3 * (int64_t)f;
+    c0 = rows + t[0] * C, c1 = rows + t[1] * C, c2 = rows + t[2] * C;
+  }
+  __device__ __forceinline__ void sample(float a0, float a1, float a2) { b0 = a0, b1 = a1, b2 = a2; }
+  __device__ __forceinline__ float channel(int c) const { return b0 * c0[c] + b1 * c1[c] + b2 * c2[c]; }
+};
+
+// One body's UV texture: render_texture_kernel's bilinear expression on the uv corners of the held face.
+struct RenderTextureSource {
+  const float* data = nullptr;   // tex [C, Ht, Wt] of this frame
+  const float* vt = nullptr;
+  const int* tab = nullptr;
+  int Ht = 1, Wt = 1, flip_v = 0;
+  const float *c0 = nullptr, *c1 = nullptr, *c2 = nullptr;
+  RenderTaps k;
+  const float* img;              // texel (yi, xi) of channel 0
+  RenderTextureSource() = default;
+  __device__ __forceinline__ RenderTextureSource(const RenderAASource& s, int64_t n, int)
+      : data(s.data + n * s.stride), vt(s.vt), tab(s.tab), Ht(s.Ht), Wt(s.Wt), flip_v(s.flip_v) {}
+  __device__ __forceinline__ void hold(int f) {
+    const int* t = tab + 3 * (int64_t)f;
+    c0 = vt + t[0] * (int64_t)2, c1 = vt + t[1] * (int64_t)2, c2 = vt + t[2] * (int64_t)2;
+  }
+  __device__ __forceinline__ void sample(float b0, float b1, float b2) {
+    k = render_taps(b0, b1, b2, c0, c1, c2, Ht, Wt, flip_v);
+    img = data + (int64_t)k.yi * Wt + k.xi;
+  }
+  __device__ __forceinline__ float channel(int c) const { return render_tap_sum(img + c * ((int64_t)Ht * Wt), Wt, k); }
+};
+
+// Resolve + shade + downsample of output pixel pix of frame n; p, key: the frame's proj and [S H, S W] keys.  The samples are walked
+// a outer, b inner; a sample's barycentrics are render_barycentrics at (S i + a, S j + b), as render_resolve_kernel computes them.
+// The face's corners (and what hold() keeps) stay while consecutive samples hold the same face (most of a pixel's samples do).  fp32
+// accumulators from 0; alpha = n / S^2, mean = acc / S^2, depth = sum of the samples' depths / S^2 (divisions; an uncovered sample
+// counts 0); n == S^2 -> mean (bg not read), n == 0 -> bg, else mean + (1 - alpha) bg; without bg, mean.  alpha, depth (NULL: not
+// written) [N, 1, H, W], out [N, C, H, W].  Accumulators are indexed by unrolled constants only: registers, no scratch.
+template <class Source>
+__device__ __forceinline__ void render_aa_pixel(Source& src, const float* __restrict__ p, const int* __restrict__ vi,
+                                                const unsigned long long* __restrict__ key, int H, int W, int S, int64_t n, int64_t pix, int C,
+                                                const float* __restrict__ bg, int64_t bg_stride, float* __restrict__ out,
+                                                float* __restrict__ alpha, float* __restrict__ depth) {
   const int64_t HW = (int64_t)H * W;
-  const int64_t pix = (int64_t)(blockIdx.x % pblocks) * RENDER_THREADS + threadIdx.x;
-  if (pix >= HW) return;
   const int i = (int)(pix / W), j = (int)(pix % W);
   const int64_t sW = (int64_t)S * W;
-  const unsigned long long* kn = key + n * HW * S * S;
-  const float* p = proj + n * V * 3;
-  const float* data = src.data + n * src.stride;
   float acc[RENDER_MAX_CHANNELS];
 #pragma unroll
   for (int c = 0; c < RENDER_MAX_CHANNELS; ++c) acc[c] = 0.0f;
   float zacc = 0.0f;
   int count = 0, held = -1;
   RenderFace tri = {};
-  const float *c0 = nullptr, *c1 = nullptr, *c2 = nullptr;               // uv corners (TEX) or value rows of the held face
   for (int a = 0; a < S; ++a) {
     const int si = S * i + a;
-    const unsigned long long* krow = kn + si * sW + (int64_t)S * j;
+    const unsigned long long* krow = key + si * sW + (int64_t)S * j;
     for (int b = 0; b < S; ++b) {
       const unsigned long long k = krow[b];
       if (k == RENDER_EMPTY_KEY) continue;
@@ -65,47 +86,16 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_aa_kernel(
       if (f != held) {
         held = f;
         tri = render_load_face(p, vi + 3 * (int64_t)f);
-        const int* t = src.tab + 3 * (int64_t)f;
-        const int64_t w = TEX ? 2 : C;
-        const float* base = TEX ? src.vt : data;
-        c0 = base + t[0] * w, c1 = base + t[1] * w, c2 = base + t[2] * w;
+        src.hold(f);
       }
-      float qa, qb, qc, d;
-      render_pixel(tri, si, S * j + b, qa, qb, qc, d);
-      const float s = qa + qb + qc;
-      const float b0 = qa / s, b1 = qb / s, b2 = qc / s;
+      float b0, b1, b2;
+      render_barycentrics(tri, si, S * j + b, b0, b1, b2);
       ++count;
       zacc += __uint_as_float((unsigned)(k >> 32));
-      if (TEX) {
-        const int Ht = src.Ht, Wt = src.Wt;
-        const float u = b0 * c0[0] + b1 * c1[0] + b2 * c2[0];
-        float v = b0 * c0[1] + b1 * c1[1] + b2 * c2[1];
-        if (src.flip_v) v = 1.0f - v;
-        // fmaxf first: a NaN becomes 0, so the taps stay inside the plane whatever the inputs hold
-        const float x = fminf(fmaxf(u * (float)(Wt - 1), 0.0f), (float)(Wt - 1));
-        const float y = fminf(fmaxf(v * (float)(Ht - 1), 0.0f), (float)(Ht - 1));
-        const float xw = floorf(x), yn = floorf(y);
-        const float we = x - xw, e = 1.0f - we, so = y - yn, nn = 1.0f - so;
-        const int xi = (int)xw, yi = (int)yn;
-        const bool east = xi + 1 <= Wt - 1, south = yi + 1 <= Ht - 1;
-        const int64_t plane = (int64_t)Ht * Wt;
-        const float* img = data + (int64_t)yi * Wt + xi;
+      src.sample(b0, b1, b2);
 #pragma unroll
-        for (int c = 0; c < RENDER_MAX_CHANNELS; ++c) {
-          if (c < C) {
-            const float* t = img + c * plane;
-            float r = t[0] * (nn * e);
-            r += (east ? t[1] : 0.0f) * (nn * we);
-            r += (south ? t[Wt] : 0.0f) * (so * e);
-            r += (east && south ? t[Wt + 1] : 0.0f) * (so * we);
-            acc[c] += r;
-          }
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < RENDER_MAX_CHANNELS; ++c)
-          if (c < C) acc[c] += b0 * c0[c] + b1 * c1[c] + b2 * c2[c];
-      }
+      for (int c = 0; c < RENDER_MAX_CHANNELS; ++c)
+        if (c < C) acc[c] += src.channel(c);
     }
   }
   {
@@ -129,4 +119,18 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_aa_kernel(
       }
     }
   }
+}
+
+// Grid pblocks * N (pblocks = ceil(H W / RENDER_THREADS)): a thread owns one output pixel of one frame, consecutive lanes consecutive
+// pixels of a plane, so the C + 1 (+ 1) plane stores are coalesced and a wave reads 64 S contiguous keys of a sample row.
+template <bool TEX>
+__global__ __launch_bounds__(RENDER_THREADS) void render_aa_kernel(
+    const float* __restrict__ proj, int V, const int* __restrict__ vi, const unsigned long long* __restrict__ key, int H, int W, int S,
+    int pblocks, RenderAASource src, int C, const float* __restrict__ bg, int64_t bg_stride, float* __restrict__ out,
+    float* __restrict__ alpha, float* __restrict__ depth) {
+  const int64_t n = blockIdx.x / pblocks, HW = (int64_t)H * W;
+  const int64_t pix = (int64_t)(blockIdx.x % pblocks) * RENDER_THREADS + threadIdx.x;
+  if (pix >= HW) return;
+  typename std::conditional<TEX, RenderTextureSource, RenderValueSource>::type source(src, n, C);
+  render_aa_pixel(source, proj + n * V * 3, vi, key + n * HW * S * S, H, W, S, n, pix, C, bg, bg_stride, out, alpha, depth);
 }

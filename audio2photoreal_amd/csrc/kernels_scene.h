@@ -3,7 +3,7 @@
 // and rasterised as one mesh through the merged face table [sum F, 3] (built once on the host, each body's vertex offset added): the
 // key fill and render_cover_kernel of kernels_render.h run unchanged, so the z-buffer is shared per sample.  The key is still depth
 // bits << 32 | global face index: at exactly equal depth the earlier body wins, then the lower face.  The resolve below is
-// render_aa_kernel<true> (kernels_render_aa.h) with the face's body looked up per sample.  Per-body pointers and sizes travel by value
+// render_aa_pixel (kernels_render_aa.h) over a source that looks the face's body up where the face changes.  Per-body pointers and sizes travel by value
 // in the kernel arguments (SceneDesc): nothing is uploaded per call.
 #pragma once
 #include "kernels_render_aa.h"
@@ -68,120 +68,53 @@ __global__ __launch_bounds__(RENDER_THREADS) void scene_project_kernel(SceneDesc
   render_project_vertex(w, m, k0, k1, k2, k4, k5, 0, proj + 3 * (n * d.V + v));
 }
 
-// Resolve + shade + downsample for a scene: render_aa_kernel<true> with the sample's body found from its global face index.  Grid
-// pblocks * N, a thread per output pixel and frame; samples walked a outer, b inner; the face's corners, uv corners and the body's
-// texture are kept while consecutive samples hold the same face.  Shading is render_texture_kernel's bilinear expression on the
-// body's own vt / vti / texture / flip.  fp32 accumulators from 0: alpha = n / S^2, mean = acc / S^2, depth = sum of the samples'
-// depths / S^2 (an uncovered sample counts 0), body_alpha[p] = n_p / S^2 with n_p the samples body p wins (sum over p = n).
-// n == S^2 -> mean (bg not read), n == 0 -> bg, else mean + (1 - alpha) bg; without bg, mean.  Accumulators and the per-body
-// counters are indexed by unrolled constants only: registers, no scratch.
+// The textures of a scene's bodies as one source: the held face's body is found from its global face index, that body's vt / vti /
+// texture / flip shade the sample (RenderTextureSource), and the samples each body wins are counted.  The body's fields are chosen
+// by a select chain over d.body[q] with constant q and the counters indexed by unrolled constants only: registers, no scratch.
+struct SceneSource {
+  const SceneDesc& d;
+  int64_t n;
+  RenderTextureSource cur;            // the held face's body, this frame
+  int body = 0, f0 = 0;
+  int cnt[SCENE_MAX_BODIES] = {};
+  __device__ __forceinline__ SceneSource(const SceneDesc& d, int64_t n) : d(d), n(n) {}
+  __device__ __forceinline__ void take(const SceneBody& b) {
+    cur.vt = b.vt, cur.tab = b.vti, f0 = b.f0;
+    cur.data = b.tex + n * b.tex_stride;
+    cur.Ht = b.Ht, cur.Wt = b.Wt, cur.flip_v = b.flip_v;
+  }
+  __device__ __forceinline__ void hold(int f) {
+    body = scene_body_of(f, d.body[1].f0, d.body[2].f0, d.body[3].f0);
+    take(d.body[0]);
+#pragma unroll
+    for (int q = 1; q < SCENE_MAX_BODIES; ++q)
+      if (body == q) take(d.body[q]);
+    cur.hold(f - f0);
+  }
+  __device__ __forceinline__ void sample(float b0, float b1, float b2) {
+#pragma unroll
+    for (int q = 0; q < SCENE_MAX_BODIES; ++q) cnt[q] += body == q;
+    cur.sample(b0, b1, b2);
+  }
+  __device__ __forceinline__ float channel(int c) const { return cur.channel(c); }
+};
+
+// Resolve + shade + downsample for a scene: render_aa_pixel (kernels_render_aa.h) over a SceneSource, on render_aa_kernel's grid,
+// and body_alpha[p] = n_p / S^2 with n_p the samples body p wins (their sum over p is alpha S^2).
 __global__ __launch_bounds__(RENDER_THREADS) void scene_resolve_kernel(
     SceneDesc d, const float* __restrict__ proj, const int* __restrict__ vi, const unsigned long long* __restrict__ key, int H, int W, int S,
     int pblocks, int C, const float* __restrict__ bg, int64_t bg_stride, float* __restrict__ out, float* __restrict__ alpha,
     float* __restrict__ depth, float* __restrict__ body_alpha) {
-  const int64_t n = blockIdx.x / pblocks;
-  const int64_t HW = (int64_t)H * W;
+  const int64_t n = blockIdx.x / pblocks, HW = (int64_t)H * W;
   const int64_t pix = (int64_t)(blockIdx.x % pblocks) * RENDER_THREADS + threadIdx.x;
   if (pix >= HW) return;
-  const int i = (int)(pix / W), j = (int)(pix % W);
-  const int64_t sW = (int64_t)S * W;
-  const unsigned long long* kn = key + n * HW * S * S;
-  const float* p = proj + n * d.V * 3;
-  float acc[RENDER_MAX_CHANNELS];
-#pragma unroll
-  for (int c = 0; c < RENDER_MAX_CHANNELS; ++c) acc[c] = 0.0f;
-  int cnt[SCENE_MAX_BODIES];
-#pragma unroll
-  for (int q = 0; q < SCENE_MAX_BODIES; ++q) cnt[q] = 0;
-  float zacc = 0.0f;
-  int count = 0, held = -1, body = 0;
-  RenderFace tri = {};
-  const float *c0 = nullptr, *c1 = nullptr, *c2 = nullptr;           // uv corners of the held face
-  const float* data = nullptr;                                       // the held face's texture, this frame
-  int Ht = 1, Wt = 1, flip_v = 0;
-  for (int a = 0; a < S; ++a) {
-    const int si = S * i + a;
-    const unsigned long long* krow = kn + si * sW + (int64_t)S * j;
-    for (int b = 0; b < S; ++b) {
-      const unsigned long long k = krow[b];
-      if (k == RENDER_EMPTY_KEY) continue;
-      const int f = (int)(unsigned)(k & 0xffffffffull);
-      if (f != held) {
-        held = f;
-        tri = render_load_face(p, vi + 3 * (int64_t)f);
-        body = scene_body_of(f, d.body[1].f0, d.body[2].f0, d.body[3].f0);
-        const float* vt = d.body[0].vt;
-        const int* tab = d.body[0].vti;
-        int f0 = 0;
-        data = d.body[0].tex + n * d.body[0].tex_stride;
-        Ht = d.body[0].Ht, Wt = d.body[0].Wt, flip_v = d.body[0].flip_v;
-#pragma unroll
-        for (int q = 1; q < SCENE_MAX_BODIES; ++q) {
-          if (body == q) {
-            vt = d.body[q].vt, tab = d.body[q].vti, f0 = d.body[q].f0;
-            data = d.body[q].tex + n * d.body[q].tex_stride;
-            Ht = d.body[q].Ht, Wt = d.body[q].Wt, flip_v = d.body[q].flip_v;
-          }
-        }
-        const int* t = tab + 3 * (int64_t)(f - f0);
-        c0 = vt + t[0] * 2, c1 = vt + t[1] * 2, c2 = vt + t[2] * 2;
-      }
-      float qa, qb, qc, dd;
-      render_pixel(tri, si, S * j + b, qa, qb, qc, dd);
-      const float s = qa + qb + qc;
-      const float b0 = qa / s, b1 = qb / s, b2 = qc / s;
-      ++count;
-#pragma unroll
-      for (int q = 0; q < SCENE_MAX_BODIES; ++q) cnt[q] += body == q;
-      zacc += __uint_as_float((unsigned)(k >> 32));
-      const float u = b0 * c0[0] + b1 * c1[0] + b2 * c2[0];
-      float v = b0 * c0[1] + b1 * c1[1] + b2 * c2[1];
-      if (flip_v) v = 1.0f - v;
-      // fmaxf first: a NaN becomes 0, so the taps stay inside the plane whatever the inputs hold
-      const float x = fminf(fmaxf(u * (float)(Wt - 1), 0.0f), (float)(Wt - 1));
-      const float y = fminf(fmaxf(v * (float)(Ht - 1), 0.0f), (float)(Ht - 1));
-      const float xw = floorf(x), yn = floorf(y);
-      const float we = x - xw, e = 1.0f - we, so = y - yn, nn = 1.0f - so;
-      const int xi = (int)xw, yi = (int)yn;
-      const bool east = xi + 1 <= Wt - 1, south = yi + 1 <= Ht - 1;
-      const int64_t plane = (int64_t)Ht * Wt;
-      const float* img = data + (int64_t)yi * Wt + xi;
-#pragma unroll
-      for (int c = 0; c < RENDER_MAX_CHANNELS; ++c) {
-        if (c < C) {
-          const float* t = img + c * plane;
-          float r = t[0] * (nn * e);
-          r += (east ? t[1] : 0.0f) * (nn * we);
-          r += (south ? t[Wt] : 0.0f) * (so * e);
-          r += (east && south ? t[Wt + 1] : 0.0f) * (so * we);
-          acc[c] += r;
-        }
-      }
-    }
-  }
+  SceneSource source(d, n);
+  render_aa_pixel(source, proj + n * d.V * 3, vi, key + n * HW * S * S, H, W, S, n, pix, C, bg, bg_stride, out, alpha, depth);
   {
-#pragma clang fp contract(off)      // the resolve as stated: divisions, then a product and a sum, each rounded
-    const float ss = (float)(S * S);
-    const float cover = (float)count / ss;
-    const bool full = count == S * S, none = count == 0;
-    alpha[n * HW + pix] = cover;
-    depth[n * HW + pix] = zacc / ss;
+#pragma clang fp contract(off)      // part of the resolve: a division like alpha's
     float* ba = body_alpha + n * d.P * HW + pix;
 #pragma unroll
     for (int q = 0; q < SCENE_MAX_BODIES; ++q)
-      if (q < d.P) ba[q * HW] = (float)cnt[q] / ss;
-    float* o = out + n * C * HW + pix;
-    const float* g = bg ? bg + n * bg_stride + pix : nullptr;
-#pragma unroll
-    for (int c = 0; c < RENDER_MAX_CHANNELS; ++c) {
-      if (c < C) {
-        float r = acc[c] / ss;
-        if (g && !full) {
-          const float back = g[c * HW];
-          r = none ? back : r + (1.0f - cover) * back;
-        }
-        o[c * HW] = r;
-      }
-    }
+      if (q < d.P) ba[q * HW] = (float)source.cnt[q] / (float)(S * S);
   }
 }

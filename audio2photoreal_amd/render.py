@@ -54,7 +54,71 @@ def look_at(eye, target, up, height: int, width: int, fov_degrees: float, device
     return torch.from_numpy(K.astype(np.float32)).to(device or "cpu"), torch.from_numpy(Rt.astype(np.float32)).to(device or "cpu")
 
 
-class BodyRasterizer:
+class _RenderArguments:
+    """The argument checks and the chunking that BodyRasterizer and scene.SceneRasterizer share; both have a height and a width."""
+
+    _tensor = staticmethod(BodySurface._tensor)
+
+    def _verts(self, verts, V: int, name: str = "verts", N=None):
+        return self._tensor(verts, name, f"[{'N' if N is None else N}, {V}, 3]", lambda s: len(s) == 3 and s[1:] == (V, 3) and N in (None, s[0]))
+
+    def _tex(self, tex, N: int, dev, name: str = "tex", C=None, beside: str = "verts", planes_below_2_31: bool = False):
+        """A texture as (contiguous tensor, per-frame flag): [N or 1, C, Ht, Wt] on dev, with C channels when C is given."""
+        C_max = _lib.RENDER_MAX_CHANNELS
+        tex = self._tensor(tex, name, f"[{N} or 1, {'C' if C is None else C}, Ht, Wt] with 1 <= C <= {C_max}",
+                           lambda s: len(s) == 4 and s[0] in (1, N) and 1 <= s[1] <= C_max and C in (None, s[1]) and min(s[2:]) >= 1
+                           and (not planes_below_2_31 or s[2] * s[3] < 1 << 31))
+        if tex.device != dev:
+            raise A2PError(f"{name} is on {tex.device}, {beside} on {dev}")
+        return tex, int(tex.shape[0] == N and N != 1)
+
+    def _camera(self, x, name: str, cols: int, N: int, dev):
+        """A camera array as (contiguous tensor, per-frame flag): [N or 1, 3, cols], or [3, cols] for one shared by all frames."""
+        x = self._tensor(x, name, f"[{N} or 1, 3, {cols}]",
+                         lambda s: s == (3, cols) or (len(s) == 3 and s[1:] == (3, cols) and s[0] in (1, N)))
+        if x.device != dev:
+            raise A2PError(f"{name} is on {x.device}, verts on {dev}")
+        return x, int(x.dim() == 3 and x.shape[0] == N and N != 1)
+
+    def _supersample(self, supersample) -> int:
+        s = int(supersample)
+        if s != supersample or not 1 <= s <= _lib.RENDER_MAX_SUPERSAMPLE:
+            raise ValueError(f"supersample={supersample} is outside [1, {_lib.RENDER_MAX_SUPERSAMPLE}] samples per axis")
+        for name, size in (("height", self.height), ("width", self.width)):
+            if s * size > _lib.RENDER_MAX_SIZE:
+                raise ValueError(f"supersample={s} x {name}={size} exceeds {_lib.RENDER_MAX_SIZE} samples per axis")
+        return s
+
+    def _background(self, background, C, verts):
+        """A background as (contiguous [n, C, H, W] tensor or None, per-frame flag): None, a colour [C] or [N or 1, C, H, W] on the
+        device of verts.  Checked before anything is asked of the GPU."""
+        if background is None or C is None:                                   # C is None: tex is malformed and is refused next
+            return None, 0
+        H, W = self.height, self.width
+        N = verts.shape[0] if torch.is_tensor(verts) and verts.dim() else 1
+        if not torch.is_tensor(background):
+            raise A2PError(f"background must be None or a tensor on the MI355X (got {type(background).__name__})")
+        shape = tuple(background.shape)
+        if background.dtype != torch.float32 or not (shape == (C,) or (len(shape) == 4 and shape[1:] == (C, H, W) and shape[0] in (1, N))):
+            raise A2PError(f"background must be float32 [{C}] or [{N} or 1, {C}, {H}, {W}] (got {background.dtype} {list(shape)})")
+        if torch.is_tensor(verts) and background.device != verts.device:
+            raise A2PError(f"background is on {background.device}, verts on {verts.device}")
+        bg = background.reshape(1, C, 1, 1).expand(1, C, H, W) if background.dim() == 1 else background
+        return bg.contiguous(), int(bg.shape[0] == N and N != 1)
+
+    def _scratch_bytes(self, V: int, s: int) -> int:
+        return 12 * V + 8 * s * s * self.height * self.width                  # proj and key of one frame
+
+    def _chunks(self, N: int, V: int, s: int, max_bytes, dev):
+        """(a, b, proj, key): frames a..b-1 per chunk; its scratch proj [., V, 3] and key [., s H, s W] stays below max_bytes (or is one frame)."""
+        step = min(N, max(1, int(max_bytes) // self._scratch_bytes(V, s)))
+        proj = torch.empty(step, V, 3, dtype=torch.float32, device=dev)
+        key = torch.empty(step, s * self.height, s * self.width, dtype=torch.int64, device=dev)
+        for a in range(0, N, step):
+            yield a, min(N, a + step), proj, key
+
+
+class BodyRasterizer(_RenderArguments):
     """A triangle mesh with a UV layout and an image size, ready to rasterise.  `surface_or_arrays` is a BodySurface or a tuple
     (vi [F, 3], vt [T, 2], vti [F, 3]) or (vi, vt, vti, n_verts).  flip_uv samples textures at v <- 1 - v (the meaning it has in BodySurface); a face with
     a corner nearer than `near` along the camera's z axis is dropped whole."""
@@ -119,16 +183,6 @@ class BodyRasterizer:
             self._dev[key] = {"vi": i32(self._vi), "vti": i32(self._vti), "vt": torch.from_numpy(self._vt).to(device)}
         return self._dev[key]
 
-    _tensor = staticmethod(BodySurface._tensor)
-
-    def _camera(self, x, name: str, cols: int, N: int, dev):
-        """A camera array as (contiguous tensor, per-frame flag): [N or 1, 3, cols], or [3, cols] for one shared by all frames."""
-        x = self._tensor(x, name, f"[{N} or 1, 3, {cols}]",
-                         lambda s: s == (3, cols) or (len(s) == 3 and s[1:] == (3, cols) and s[0] in (1, N)))
-        if x.device != dev:
-            raise A2PError(f"{name} is on {x.device}, verts on {dev}")
-        return x, int(x.dim() == 3 and x.shape[0] == N and N != 1)
-
     def _fragments(self, fragments, N=None):
         if not isinstance(fragments, dict) or "face" not in fragments or "bary" not in fragments:
             raise A2PError("fragments must be the dict rasterize returns (keys face, bary)")
@@ -147,7 +201,7 @@ class BodyRasterizer:
     def rasterize(self, verts, K, Rt) -> dict:
         """{"face": int32 [N, H, W] (-1: background), "bary": float32 [N, H, W, 3] perspective-correct barycentrics (0), "depth":
         float32 [N, H, W] camera-space z of the visible surface (0)} of verts [N, V, 3] seen through K and Rt."""
-        verts = self._tensor(verts, "verts", f"[N, {self.V}, 3]", lambda s: len(s) == 3 and s[1:] == (self.V, 3))
+        verts = self._verts(verts, self.V)
         N, dev, H, W = verts.shape[0], verts.device, self.height, self.width
         K, k_per = self._camera(K, "K", 3, N, dev)
         Rt, rt_per = self._camera(Rt, "Rt", 4, N, dev)
@@ -190,11 +244,7 @@ class BodyRasterizer:
         texture coordinate; 0 on background."""
         face, bary = self._fragments(fragments)
         N, dev, H, W = face.shape[0], face.device, self.height, self.width
-        C_max = _lib.RENDER_MAX_CHANNELS
-        tex = self._tensor(tex, "tex", f"[{N} or 1, C, Ht, Wt] with 1 <= C <= {C_max}",
-                           lambda s: len(s) == 4 and s[0] in (1, N) and 1 <= s[1] <= C_max and min(s[2:]) >= 1)
-        if tex.device != dev:
-            raise A2PError(f"tex is on {tex.device}, the fragments on {dev}")
+        tex, tex_per = self._tex(tex, N, dev, beside="the fragments")
         C, Ht, Wt = tex.shape[1:]
         out = torch.empty(N, C, H, W, dtype=torch.float32, device=dev)
         if N == 0:
@@ -203,7 +253,7 @@ class BodyRasterizer:
         with _lib.on_device_of(face):
             _lib.check(_lib.load().a2p_render_texture(
                 _lib.ptr(face), _lib.ptr(bary), N, H, W, _lib.ptr(t["vt"]), self.T, _lib.ptr(t["vti"]), self.F, _lib.ptr(tex),
-                int(tex.shape[0] == N and N != 1), C, Ht, Wt, int(self.flip_uv), _lib.ptr(out), _lib.current_stream(dev)),
+                tex_per, C, Ht, Wt, int(self.flip_uv), _lib.ptr(out), _lib.current_stream(dev)),
                 "a2p_render_texture")
         return out
 
@@ -215,35 +265,9 @@ class BodyRasterizer:
         return {"render": self.sample_texture(self.rasterize(verts, K, Rt), tex)}
 
     # -------------------------------------------------------------------------------------------- anti-aliased images
-    def _supersample(self, supersample) -> int:
-        s = int(supersample)
-        if s != supersample or not 1 <= s <= _lib.RENDER_MAX_SUPERSAMPLE:
-            raise ValueError(f"supersample={supersample} is outside [1, {_lib.RENDER_MAX_SUPERSAMPLE}] samples per axis")
-        for name, size in (("height", self.height), ("width", self.width)):
-            if s * size > _lib.RENDER_MAX_SIZE:
-                raise ValueError(f"supersample={s} x {name}={size} exceeds {_lib.RENDER_MAX_SIZE} samples per axis")
-        return s
-
-    def _background(self, background, C, verts):
-        """A background as (contiguous [n, C, H, W] tensor or None, per-frame flag): None, a colour [C] or [N or 1, C, H, W] on the
-        device of verts.  Checked before anything is asked of the GPU."""
-        if background is None or C is None:                                   # C is None: tex is malformed and is refused next
-            return None, 0
-        H, W = self.height, self.width
-        N = verts.shape[0] if torch.is_tensor(verts) and verts.dim() else 1
-        if not torch.is_tensor(background):
-            raise A2PError(f"background must be None or a tensor on the MI355X (got {type(background).__name__})")
-        shape = tuple(background.shape)
-        if background.dtype != torch.float32 or not (shape == (C,) or (len(shape) == 4 and shape[1:] == (C, H, W) and shape[0] in (1, N))):
-            raise A2PError(f"background must be float32 [{C}] or [{N} or 1, {C}, {H}, {W}] (got {background.dtype} {list(shape)})")
-        if torch.is_tensor(verts) and background.device != verts.device:
-            raise A2PError(f"background is on {background.device}, verts on {verts.device}")
-        bg = background.reshape(1, C, 1, 1).expand(1, C, H, W) if background.dim() == 1 else background
-        return bg.contiguous(), int(bg.shape[0] == N and N != 1)
-
     def _antialiased(self, verts, K, Rt, s: int, max_bytes, C: int, background, source, want_depth: bool):
-        """The chunk loop both anti-aliased methods share; source(tables, a, b) -> (export name, its arguments before the cameras,
-        its arguments after `near`) for frames a..b-1.  background: what _background returned."""
+        """What both anti-aliased methods share; source(tables, a, b) -> (export name, its arguments before the cameras, its
+        arguments after `near`) for frames a..b-1.  background: what _background returned."""
         if int(max_bytes) < 1:
             raise A2PError(f"max_bytes={max_bytes}: need a positive byte budget")
         N, dev, H, W = verts.shape[0], verts.device, self.height, self.width
@@ -255,13 +279,9 @@ class BodyRasterizer:
         if N == 0:
             return out, alpha, depth
         t = self._tables(dev)
-        step = min(N, max(1, int(max_bytes) // (12 * self.V + 8 * s * s * H * W)))          # proj and key of one frame
-        proj = torch.empty(step, self.V, 3, dtype=torch.float32, device=dev)
-        key = torch.empty(step, s * H, s * W, dtype=torch.int64, device=dev)
         lib = _lib.load()
         with _lib.on_device_of(verts):
-            for a in range(0, N, step):
-                b = min(N, a + step)
+            for a, b, proj, key in self._chunks(N, self.V, s, max_bytes, dev):
                 part = lambda x, per: x[a:b] if per else x
                 name, before, after = source(t, a, b)
                 _lib.check(getattr(lib, name)(
@@ -281,15 +301,10 @@ class BodyRasterizer:
         Frames are processed in chunks whose scratch stays below max_bytes; a frame's bits do not depend on the chunking."""
         s = self._supersample(supersample)
         background = self._background(background, tex.shape[1] if torch.is_tensor(tex) and tex.dim() == 4 else None, verts)
-        verts = self._tensor(verts, "verts", f"[N, {self.V}, 3]", lambda s: len(s) == 3 and s[1:] == (self.V, 3))
+        verts = self._verts(verts, self.V)
         N, dev = verts.shape[0], verts.device
-        C_max = _lib.RENDER_MAX_CHANNELS
-        tex = self._tensor(tex, "tex", f"[{N} or 1, C, Ht, Wt] with 1 <= C <= {C_max}",
-                           lambda s: len(s) == 4 and s[0] in (1, N) and 1 <= s[1] <= C_max and min(s[2:]) >= 1)
-        if tex.device != dev:
-            raise A2PError(f"tex is on {tex.device}, verts on {dev}")
+        tex, tex_per = self._tex(tex, N, dev)
         C, Ht, Wt = tex.shape[1:]
-        tex_per = int(tex.shape[0] == N and N != 1)
         source = lambda t, a, b: ("a2p_render_antialiased_texture", (_lib.ptr(t["vt"]), self.T, _lib.ptr(t["vti"])),
                                   (_lib.ptr(tex[a:b] if tex_per else tex), tex_per, C, Ht, Wt, int(self.flip_uv)))
         out, alpha, _ = self._antialiased(verts, K, Rt, s, max_bytes, C, background, source, False)
@@ -299,7 +314,7 @@ class BodyRasterizer:
         """{"values": [N, C, H, W], "alpha": [N, 1, H, W], "depth": [N, 1, H, W]}: values [N, V, C] (1 <= C <= 16) interpolated at
         every sample and averaged like render_antialiased (premultiplied by alpha); depth is the same mean of the samples' depths."""
         s = self._supersample(supersample)
-        verts = self._tensor(verts, "verts", f"[N, {self.V}, 3]", lambda s: len(s) == 3 and s[1:] == (self.V, 3))
+        verts = self._verts(verts, self.V)
         N, dev = verts.shape[0], verts.device
         C_max = _lib.RENDER_MAX_CHANNELS
         values = self._tensor(values, "values", f"[{N}, {self.V}, C] with 1 <= C <= {C_max}",

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import A2PError
-from .render import BodyRasterizer, camera_centre
+from .render import BodyRasterizer, _RenderArguments, camera_centre
 from .surface import BodySurface
 
 MAX_BODIES = _lib.SCENE_MAX_BODIES
@@ -94,7 +94,7 @@ def _as_rasterizer(body, p: int, height: int, width: int, near: float) -> BodyRa
     return BodyRasterizer(body if isinstance(body, BodySurface) else tuple(body), height, width, bool(flip), near)
 
 
-class SceneRasterizer:
+class SceneRasterizer(_RenderArguments):
     """1 to 4 triangle meshes with UV layouts and one image size, ready to rasterise together.  Each entry of `bodies` is a
     BodySurface (whose validated topology tables are shared, not copied), a BodyRasterizer (its tables and flip_uv) or a tuple (vi
     [F, 3], vt [T, 2], vti [F, 3][, n_verts]); `(entry, flip_uv)` or {"body": entry, "flip_uv": bool} sets the body's flip.  The
@@ -133,7 +133,7 @@ class SceneRasterizer:
 
     def scratch_bytes_per_frame(self, supersample: int) -> int:
         """proj and key of one frame: 12 sum V + 8 S^2 H W."""
-        return 12 * self.sum_V + 8 * supersample * supersample * self.height * self.width
+        return self._scratch_bytes(self.sum_V, supersample)
 
     def render(self, verts, textures, K, Rt, placements=None, supersample: int = 1, background=None, max_bytes: int = 1 << 30) -> dict:
         """{"render": [N, C, H, W], "alpha": [N, 1, H, W], "depth": [N, 1, H, W], "body_alpha": [N, P, H, W]} of the bodies seen
@@ -145,34 +145,26 @@ class SceneRasterizer:
         the samples' camera-space depths.  background as in BodyRasterizer.render_antialiased: a fully covered pixel does not read
         it, an uncovered one holds its value itself, the others render + (1 - alpha) background.  Frames are processed in chunks
         whose scratch (12 sum V + 8 S^2 H W bytes a frame) stays below max_bytes; a frame's bits do not depend on the chunking."""
-        first = self.bodies[0]
-        s = first._supersample(supersample)
+        s = self._supersample(supersample)
         if int(max_bytes) < 1:
             raise A2PError(f"max_bytes={max_bytes}: need a positive byte budget")
         verts, textures = self._sequence(verts, "verts"), self._sequence(textures, "textures")
         placements = [None] * self.P if placements is None else self._sequence(placements, "placements")
         N = verts[0].shape[0] if torch.is_tensor(verts[0]) and verts[0].dim() == 3 else None
         for p in range(self.P):
-            verts[p] = first._tensor(verts[p], f"verts[{p}]", f"[{'N' if N is None else N}, {self.V[p]}, 3]",
-                                     lambda sh: len(sh) == 3 and sh[1:] == (self.V[p], 3) and sh[0] == (sh[0] if N is None else N))
+            verts[p] = self._verts(verts[p], self.V[p], f"verts[{p}]", N)
         N, dev = verts[0].shape[0], verts[0].device
-        C_max = _lib.RENDER_MAX_CHANNELS
         C = textures[0].shape[1] if torch.is_tensor(textures[0]) and textures[0].dim() == 4 else None
         tex_per, place_per = [0] * self.P, [0] * self.P
         for p in range(self.P):
             if verts[p].device != dev:
                 raise A2PError(f"verts[{p}] is on {verts[p].device}, verts[0] on {dev}")
-            textures[p] = first._tensor(textures[p], f"textures[{p}]", f"[{N} or 1, {'C' if C is None else C}, Ht, Wt] with 1 <= C <= {C_max}",
-                                        lambda sh: len(sh) == 4 and sh[0] in (1, N) and 1 <= sh[1] <= C_max and sh[1] == C and min(sh[2:]) >= 1
-                                        and sh[2] * sh[3] < 1 << 31)
-            if textures[p].device != dev:
-                raise A2PError(f"textures[{p}] is on {textures[p].device}, verts on {dev}")
-            tex_per[p] = int(textures[p].shape[0] == N and N != 1)
+            textures[p], tex_per[p] = self._tex(textures[p], N, dev, f"textures[{p}]", C, planes_below_2_31=True)    # C is None: textures[0] is refused
             if placements[p] is not None:
-                placements[p], place_per[p] = first._camera(placements[p], f"placements[{p}]", 4, N, dev)
-        K, k_per = first._camera(K, "K", 3, N, dev)
-        Rt, rt_per = first._camera(Rt, "Rt", 4, N, dev)
-        bg, bg_per = first._background(background, C, verts[0])
+                placements[p], place_per[p] = self._camera(placements[p], f"placements[{p}]", 4, N, dev)
+        K, k_per = self._camera(K, "K", 3, N, dev)
+        Rt, rt_per = self._camera(Rt, "Rt", 4, N, dev)
+        bg, bg_per = self._background(background, C, verts[0])
         H, W, P = self.height, self.width, self.P
         new = lambda c: torch.empty(N, c, H, W, dtype=torch.float32, device=dev)
         out = {"render": new(C), "alpha": new(1), "depth": new(1), "body_alpha": new(P)}
@@ -180,14 +172,10 @@ class SceneRasterizer:
             return out
         tables = [b._tables(dev) for b in self.bodies]
         faces = self._faces(dev)
-        step = min(N, max(1, int(max_bytes) // self.scratch_bytes_per_frame(s)))
-        proj = torch.empty(step, self.sum_V, 3, dtype=torch.float32, device=dev)
-        key = torch.empty(step, s * H, s * W, dtype=torch.int64, device=dev)
         lib = _lib.load()
         desc = (_lib.A2PSceneBody * P)()
         with _lib.on_device_of(verts[0]):
-            for a in range(0, N, step):
-                b = min(N, a + step)
+            for a, b, proj, key in self._chunks(N, self.sum_V, s, max_bytes, dev):
                 part = lambda x, per: x[a:b] if per else x
                 for p in range(P):
                     tex = part(textures[p], tex_per[p])
@@ -201,7 +189,6 @@ class SceneRasterizer:
                     _lib.ptr(out["alpha"][a:b]), _lib.ptr(out["depth"][a:b]), _lib.ptr(out["body_alpha"][a:b]), _lib.current_stream(dev)),
                     "a2p_scene_render")
         return out
-
 
 # ------------------------------------------------------------------------------------------------ people
 class Avatar(NamedTuple):
@@ -283,7 +270,7 @@ def render_conversation_motion(avatars, poses, face_codes, placements, K, Rt, he
     host_place = [None if m is None else check_rigid(m, f"placements[{p}]") for p, m in enumerate(placements)]
     shown, linear = display_background(background, H, W)
     scene = SceneRasterizer([a.surface for a in avatars], H, W)
-    s = scene.bodies[0]._supersample(supersample)
+    s = scene._supersample(supersample)
     frames, codes, lead = [], [], None
     for p, a in enumerate(avatars):
         if a.skeleton.P_pos != 6 + a.decoder.n_pose_dims:
