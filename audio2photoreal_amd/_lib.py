@@ -61,6 +61,7 @@ EXPORTS = (
     "a2p_set_guidance",
     "a2p_render_antialiased_texture", "a2p_render_antialiased_values",
     "a2p_scene_render",
+    "a2p_skin_steer", "a2p_sample_step_steer",
 )
 
 
@@ -155,6 +156,17 @@ class A2PSceneBody(C.Structure):
                 + [(n, C.c_int32) for n in ("V", "F", "T", "Ht", "Wt", "flip_v", "placement_per_frame", "tex_per_frame")])
 
 
+class A2PSteer(C.Structure):
+    """a2p_steer (include/a2p_hip.h "steering joints to 3D targets"): the skeleton, the constraints and the descent of
+    a2p_skin_steer / a2p_sample_step_steer.  joints_host / kinds_host / axes_host are HOST arrays."""
+    _fields_ = ([(n, C.c_void_p) for n in ("row_ptr", "cols", "vals", "offsets", "joint_offset", "pre_rotation", "parents", "order",
+                                           "level_start", "child_ptr", "child_idx", "col_ptr", "rows", "cvals", "mean", "std", "scale")]
+                + [("joints_host", C.POINTER(C.c_int32)), ("kinds_host", C.POINTER(C.c_int32)), ("axes_host", C.POINTER(C.c_float))]
+                + [("targets", C.c_void_p), ("weights", C.c_void_p), ("global_scaling", C.c_float * 3), ("alpha", C.c_float),
+                   ("max_step", C.c_float)]
+                + [(n, C.c_int32) for n in ("P_pos", "P_scale", "J", "n_levels", "scale_per_frame", "K", "iterations")])
+
+
 EPI_STORE, EPI_STORE_T, EPI_FILM_RES, EPI_CONV = 0, 1, 2, 3                          # csrc/kernels_gemm.h
 ACT_NONE, ACT_GELU, ACT_MISH, ACT_SILU, ACT_LRELU, ACT_RELU = 0, 1, 2, 3, 4, 5       # csrc/a2p_common.h
 
@@ -185,6 +197,7 @@ NORMALIZE_NONE, NORMALIZE_PEAK = 0, 1 # A2P_NORMALIZE_*
 WINDOW_MAX = 256                      # A2P_WINDOW_MAX
 DATASET_MAX_BATCH = 64                # A2P_DATASET_MAX_BATCH
 SKIN_MAX_JOINTS, SKIN_MAX_PARAMS, SKIN_MAX_INFLUENCES = 1024, 1024, 16   # A2P_SKIN_MAX_*
+STEER_MAX_CONSTRAINTS, STEER_REACH, STEER_AIM = 16, 0, 1                   # A2P_STEER_MAX_CONSTRAINTS, a2p_steer_kind
 SURFACE_MAX_UV, SURFACE_MAX_CHANNELS = 16384, 16                         # A2P_SURFACE_MAX_* (3 H H fits in int32)
 RENDER_MAX_SIZE, RENDER_MAX_CHANNELS = 8192, 16                          # A2P_RENDER_MAX_*
 RENDER_MAX_SUPERSAMPLE = 4                                               # A2P_RENDER_MAX_SUPERSAMPLE
@@ -286,6 +299,8 @@ def load(half: bool = False) -> C.CDLL:
                               f32, f32, f32, i32, vp, vp, vp, vp, vp],
         "a2p_skin_states": [vp, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
         "a2p_skin_vertices": [vp, i64, i32, vp, vp, i32, vp, vp, i32, i32, f32, f32, f32, vp, vp],
+        "a2p_skin_steer": [C.POINTER(A2PSteer), vp, i64, i64, vp, i64, vp, vp, vp],
+        "a2p_sample_step_steer": [vp, i32, vp, vp, vp, vp, i32, vp, vp, f32, i32, C.POINTER(A2PSteer), vp, vp, vp],
         "a2p_surface_normals": [vp, i64, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp],
         "a2p_surface_to_uv": [vp, i64, i32, i32, vp, vp, i32, vp, vp],
         "a2p_surface_from_uv": [vp, i64, i32, i32, i32, vp, i32, vp, i32, vp, vp],

@@ -43,6 +43,7 @@
 #include "kernels_scene.h"
 #include "kernels_skin.h"
 #include "kernels_small.h"
+#include "kernels_steer.h"
 #include "kernels_surface.h"
 #include "kernels_tail.h"
 #include "kernels_video.h"
@@ -1016,6 +1017,7 @@ extern "C" int a2p_finalize_weights(a2p_ctx* c, void* stream) {
 #include "a2p_eval.h"
 #include "a2p_dataset.h"
 #include "a2p_skin.h"
+#include "a2p_steer.h"
 #include "a2p_surface.h"
 #include "a2p_render.h"
 #include "a2p_scene.h"

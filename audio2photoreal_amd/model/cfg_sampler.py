@@ -68,6 +68,10 @@ class ClassifierFreeSampleModel(nn.Module):
         """a2p_sample_step with held elements (sample/inpaint.py inpaint_sample_loop)."""
         return self.model.sample_step_inpaint(sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised, known, known_mask)
 
+    def a2p_sample_step_steer(self, sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised, steer):
+        """a2p_sample_step with the x0 prediction steered to joint targets (sample/steer.py steered_sample_loop)."""
+        return self.model.sample_step_steer(sampler, x, t_idx, timestep_map, tables, y, noise, eta, clip_denoised, steer)
+
     def a2p_sample_step_multistep(self, x, t_idx, timestep_map, coefs, y, x0_prev, clip_denoised, known=None, known_mask=None):
         """One DPM-Solver++(2M) step, plain or with held elements (GaussianDiffusion.dpm_solver_sample, inpaint_sample_loop)."""
         return self.model.sample_step_multistep(x, t_idx, timestep_map, coefs, y, x0_prev, clip_denoised, known, known_mask)

@@ -577,6 +577,29 @@ class FiLMTransformer(nn.Module):
                        "a2p_sample_step_inpaint")
         return x_next, x0
 
+    def sample_step_steer(self, sampler: int, x, t_idx, timestep_map, tables, y, noise, eta: float, clip_denoised: bool, steer):
+        """One step whose guided x0 prediction is steered towards joint targets before the clamp and the DDIM / DDPM update
+        (include/a2p_hip.h a2p_sample_step_steer; sample/steer.py).  `steer`: (a2p_steer, keep-alive) of
+        BodySkeleton.steer_description, targets [B T, K, 3] and weights [B T, K] on x's device.  Body model only.
+        Returns (x_next, pred_xstart)."""
+        guide = self._guidance(y, x.shape[0])
+        x = x.to(torch.float32).contiguous()
+        desc = steer[0]
+        if self.nfeats != desc.P_pos:
+            raise _lib.A2PError(f"steer step: the model has {self.nfeats} features, the skeleton {desc.P_pos} pose parameters "
+                                "(the body model is steered)")
+        self.prepare(x, y)
+        self._send_guidance(guide, x.device)
+        x_next, x0 = torch.empty_like(x), torch.empty_like(x)
+        sc = y["scale"].to(device=x.device, dtype=torch.float32).contiguous()
+        nz = None if noise is None else noise.to(device=x.device, dtype=torch.float32).contiguous()
+        with _lib.on_device_of(x):
+            _lib.check(self._lib().a2p_sample_step_steer(self._ctx, sampler, _lib.ptr(x), _lib.ptr(t_idx), _lib.ptr(timestep_map),
+                                                         _lib.ptr(tables), tables.shape[1], _lib.ptr(sc), _lib.ptr(nz), float(eta),
+                                                         int(bool(clip_denoised)), C.byref(desc), _lib.ptr(x_next), _lib.ptr(x0),
+                                                         _lib.current_stream(x.device)), "a2p_sample_step_steer")
+        return x_next, x0
+
     def sample_step_multistep(self, x, t_idx, timestep_map, coefs, y, x0_prev, clip_denoised: bool, known=None, known_mask=None):
         """One DPM-Solver++(2M) step (include/a2p_hip.h a2p_sample_step_multistep): the guided forward, then
         x_next = CX x + B x0 + P x0_prev from `coefs` fp32 [A2P_NMS, n_steps] (GaussianDiffusion._multistep_coefs).  `x0_prev`: the

@@ -239,11 +239,12 @@ def _conditions(face_m, pose_m, audio: torch.Tensor, share_features: bool):
 
 
 def _face_body_runs(face, pose, audio: torch.Tensor, T: int, nk: int, uniforms, noise_face, noise_pose, top_p, face_scale, pose_scale,
-                    sampler: str, share_features: bool, plan=None, known=None, chain_keyframes: bool = False):
+                    sampler: str, share_features: bool, plan=None, known=None, chain_keyframes: bool = False, body_loop=None):
     """The conditioning of the B = audio.shape[0] sequences (computed here, on the current stream) and two closures: run_face()
     -> the face sample, run_body() -> guide keyframes into y_body["keyframes"], then the body sample.  plan None: the plain loops
     over T frames (known: the forced keyframes of generate_from_recording); else windowed_sample_loop over the plan's windows
-    (rows r * W + w, T the window length, noise per global frame)."""
+    (rows r * W + w, T the window length, noise per global frame).  body_loop(diffusion, model, noise, y): the body's loop when it
+    is not the face's (sample/steer.py)."""
     face_m, face_d = face
     pose_m, pose_d = pose
     fm, pm = _denoiser(face_m), _denoiser(pose_m)
@@ -275,7 +276,7 @@ def _face_body_runs(face, pose, audio: torch.Tensor, T: int, nk: int, uniforms, 
             guide_y = {**guide_cond, "keyframes": torch.zeros(B, nk, pm.nfeats, device=device)}
             kk = {} if known is None else {"known": known[0].expand(B, -1, -1), "known_mask": known[1].expand(B, -1)}
             y_body["keyframes"] = _replace_keyframes({"y": guide_y}, pose_m, uniforms, top_p=top_p, **kk).to(device)
-        return loop(pose_d, pose_m, noise_pose, y_body)
+        return (body_loop or loop)(pose_d, pose_m, noise_pose, y_body)
 
     return run_face, run_body, y_body
 

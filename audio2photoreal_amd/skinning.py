@@ -8,6 +8,8 @@ LinearBlendSkinning.forward, LBSModule.pose), as two HIP launches for all frames
 (`from_arrays`).  Construction is host work: it packs the ragged skinning list, sorts the joints into depth levels, compresses the
 parameter transform to its non-zeros, computes the bind state and its inverse in float64, and rejects anything a kernel could
 not index safely.  The methods take poses that live on the GPU and run on the caller's current stream; there is no CPU path.
+`joint_loss_grad` and `solve_ik` go the other way -- a loss on joint positions and orientations, its gradient through the skeleton
+solve, and descent towards the targets (csrc/kernels_steer.h; sample/steer.py steers a sampler with them).
 
 Poses are the UN-NORMALISED 104 joint parameters: the `"pose"` entry of generate_from_recording / generate_from_long_recording /
 generate_conversation / sample.dataset, or the `motions` of a results.npy.  A sampler's raw output [B, 104, 1, T] is normalised:
@@ -15,6 +17,7 @@ multiply by pose_std and add pose_mean first (sample.generate.make_inv_transform
 from __future__ import annotations
 
 import argparse
+import ctypes as C
 import sys
 from typing import Optional
 
@@ -76,6 +79,25 @@ def level_schedule(parents):
     order = np.argsort(depth, kind="stable")
     level_start = np.concatenate([[0], np.cumsum(np.bincount(depth))])
     return order.astype(np.int64), level_start.astype(np.int64), depth
+
+
+def child_list(parents):
+    """(child_ptr [J + 1], child_idx): the children of joint j are child_idx[child_ptr[j]:child_ptr[j + 1]], ascending -- the
+    order in which the backward pass of the skeleton solve sums their adjoints (csrc/kernels_steer.h)."""
+    p = normalise_parents(parents)
+    kids = np.nonzero(p >= 0)[0]
+    kids = kids[np.argsort(p[kids], kind="stable")]
+    child_ptr = np.concatenate([[0], np.cumsum(np.bincount(p[kids], minlength=p.size))])
+    return child_ptr.astype(np.int64), kids.astype(np.int64)
+
+
+def compress_columns(transform, n_cols: int):
+    """The first n_cols columns of the dense [R, P] transform as compressed columns (col_ptr [n_cols + 1], rows, vals float32),
+    rows ascending inside a column: the transposed parameter transform, one output per column."""
+    t = np.asarray(transform, np.float32)[:, :n_cols]
+    cols, rows = np.nonzero(t.T)
+    col_ptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=n_cols))])
+    return col_ptr.astype(np.int64), rows.astype(np.int64), t[rows, cols]
 
 
 def compress_transform(transform):
@@ -158,6 +180,58 @@ def motion_frames(motion, n_params: int = 104):
     return (m.to(torch.float32).contiguous() if is_t else np.ascontiguousarray(m, np.float32)), tuple(int(v) for v in lead)
 
 
+# ------------------------------------------------------------------------------------------------ joint constraints
+REACH, AIM = _lib.STEER_REACH, _lib.STEER_AIM
+
+
+class JointConstraints:
+    """K <= 16 constraints on N frames, as the steer kernel reads them (include/a2p_hip.h a2p_steer): host lists `joints` [K]
+    (indices), `kinds` [K] (REACH / AIM) and `axes` [K, 3] (the unit axis of an aim in the joint's frame; ignored by a reach), and
+    `targets` [N, K, 3] / `weights` [N, K] (float32; numpy, or tensors on any device).  Targets are in the units of
+    pose_motion's "joints": translation times global_scaling.  Host data is validated here; sample.steer.JointTargets builds these."""
+
+    def __init__(self, joints, kinds, axes, targets, weights, n_joints: Optional[int] = None):
+        self.joints = [int(j) for j in joints]
+        self.kinds = [int(k) for k in kinds]
+        self.axes = np.ascontiguousarray(axes, np.float32).reshape(-1, 3)
+        K = len(self.joints)
+        if K < 1 or K > _lib.STEER_MAX_CONSTRAINTS:
+            raise A2PError(f"{K} constraints: the steer kernel takes 1..{_lib.STEER_MAX_CONSTRAINTS}")
+        if len(self.kinds) != K or self.axes.shape[0] != K:
+            raise A2PError(f"joints ({K}), kinds ({len(self.kinds)}) and axes ({self.axes.shape[0]}) differ in length")
+        for k in range(K):
+            if self.kinds[k] not in (REACH, AIM):
+                raise A2PError(f"constraint {k}: kind {self.kinds[k]} is neither REACH ({REACH}) nor AIM ({AIM})")
+            if self.joints[k] < 0 or (n_joints is not None and self.joints[k] >= n_joints):
+                raise A2PError(f"constraint {k}: joint {self.joints[k]} is outside [0, {n_joints})")
+            if self.kinds[k] == AIM:
+                check_axis(self.axes[k], f"constraint {k}")
+        as_t = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.float32))
+        self.targets, self.weights = as_t(targets).to(torch.float32), as_t(weights).to(torch.float32)
+        N = self.weights.shape[0]
+        if tuple(self.targets.shape) != (N, K, 3) or tuple(self.weights.shape) != (N, K):
+            raise A2PError(f"targets must be [N, {K}, 3] and weights [N, {K}] (got {list(self.targets.shape)}, {list(self.weights.shape)})")
+        if not self.weights.is_cuda:
+            w = self.weights.numpy()
+            if not (np.isfinite(w).all() and (w >= 0).all()):
+                raise A2PError("weights must be finite and >= 0")
+        if not self.targets.is_cuda and not bool(torch.isfinite(self.targets).all()):
+            raise A2PError("targets must be finite")
+        self.N, self.K = int(N), K
+
+    def on(self, device):
+        """(targets, weights) contiguous on `device`."""
+        return self.targets.to(device).contiguous(), self.weights.to(device).contiguous()
+
+
+def check_axis(axis, what: str) -> np.ndarray:
+    """A finite unit 3-vector (|axis| within 1e-4 of 1), or A2PError."""
+    a = np.asarray(axis, np.float64).reshape(-1)
+    if a.size != 3 or not np.isfinite(a).all() or abs(float(np.linalg.norm(a)) - 1.0) > 1e-4:
+        raise A2PError(f"{what}: axis {a.tolist()} is not a finite unit 3-vector")
+    return a.astype(np.float32)
+
+
 # ------------------------------------------------------------------------------------------------ the skeleton
 class BodySkeleton:
     """A skinned skeleton, validated and laid out for the kernels.  Host arrays live on the object; device copies are made on
@@ -230,6 +304,8 @@ class BodySkeleton:
         self.joint_names = list(joint_names) if joint_names is not None else [f"joint{j}" for j in range(J)]
         self.J, self.V, self.K = J, V, K
         self.row_ptr, self.cols, self.vals = compress_transform(self.transform)
+        self.col_ptr, self.col_rows, self.col_vals = compress_columns(self.transform, self.P_pos)
+        self.child_ptr, self.child_idx = child_list(self.parents)
         self.bind_state, self.inv_bind = bind_state64(self.parents, self.pre_rotation, self.joint_offset, self.transform_offsets)
         _finite("bind_state", self.bind_state)
         _finite("inverse bind state", self.inv_bind)
@@ -270,6 +346,9 @@ class BodySkeleton:
                 "row_ptr": i32(self.row_ptr), "cols": i32(self.cols), "vals": f32(self.vals), "offsets": f32(self.transform_offsets),
                 "joint_offset": f32(self.joint_offset), "pre_rotation": f32(self.pre_rotation), "parents": i32(self.parents),
                 "order": i32(self.order), "level_start": i32(self.level_start), "inv_bind": f32(self.inv_bind),
+                "child_ptr": i32(self.child_ptr), "child_idx": i32(self.child_idx if self.child_idx.size else [0]),
+                "col_ptr": i32(self.col_ptr), "col_rows": i32(self.col_rows if self.col_rows.size else [0]),
+                "col_vals": f32(self.col_vals if self.col_vals.size else [0]),
                 "idx": i32(self.skin_indices.T), "w": f32(self.skin_weights.T),             # [K, V]: a wave reads consecutive entries
                 "base": f32(base), "lbs_scale": None if self.lbs_scale is None else f32(self.lbs_scale.reshape(1, -1))}
         return self._dev[key]
@@ -327,6 +406,79 @@ class BodySkeleton:
         """[N, J, 3]: the state translations times global_scaling."""
         states = self.joint_states(poses, scales)
         return states[:, :, 0:3] * torch.from_numpy(self.global_scaling).to(states.device)
+
+    # -------------------------------------------------------------------------------------------- steering
+    def steer_description(self, t, cons: "JointConstraints", targets, weights, mean, std, scales, per_frame: int, alpha: float,
+                          iterations: int, max_step: float):
+        """(a2p_steer, keep-alive tuple) for a library call: `t` the device tables, targets / weights / mean / std / scales
+        contiguous fp32 tensors on that device (mean / std / scales may be None)."""
+        if not isinstance(cons, JointConstraints):
+            raise A2PError(f"constraints must be JointConstraints (got {type(cons).__name__})")
+        if max(cons.joints) >= self.J:
+            raise A2PError(f"constraint joint {max(cons.joints)} is outside [0, J={self.J})")
+        iterations = int(iterations)
+        if iterations < 0 or iterations > 1024:
+            raise A2PError(f"iterations must be in [0, 1024] (got {iterations})")
+        if not (np.isfinite(alpha) and alpha > 0 and np.isfinite(max_step) and max_step > 0):
+            raise A2PError(f"alpha ({alpha}) and max_step ({max_step}) must be positive and finite")
+        K = cons.K
+        joints, kinds = (C.c_int32 * K)(*cons.joints), (C.c_int32 * K)(*cons.kinds)
+        axes = (C.c_float * (3 * K))(*[float(v) for v in cons.axes.reshape(-1)])
+        d = _lib.A2PSteer()
+        for name, key in (("row_ptr", "row_ptr"), ("cols", "cols"), ("vals", "vals"), ("offsets", "offsets"),
+                          ("joint_offset", "joint_offset"), ("pre_rotation", "pre_rotation"), ("parents", "parents"), ("order", "order"),
+                          ("level_start", "level_start"), ("child_ptr", "child_ptr"), ("child_idx", "child_idx"), ("col_ptr", "col_ptr"),
+                          ("rows", "col_rows"), ("cvals", "col_vals")):
+            setattr(d, name, _lib.ptr(t[key]))
+        d.mean, d.std, d.scale = _lib.ptr(mean), _lib.ptr(std), _lib.ptr(scales)
+        d.joints_host, d.kinds_host, d.axes_host = joints, kinds, axes
+        d.targets, d.weights = _lib.ptr(targets), _lib.ptr(weights)
+        d.global_scaling = (C.c_float * 3)(*[float(v) for v in self.global_scaling])
+        d.alpha, d.max_step = float(alpha), float(max_step)
+        d.P_pos, d.P_scale, d.J, d.n_levels = self.P_pos, self.P_scale, self.J, self.level_start.size - 1
+        d.scale_per_frame, d.K, d.iterations = int(per_frame), K, iterations
+        return d, (joints, kinds, axes, targets, weights, mean, std, scales)
+
+    def _steer(self, poses, cons, scales, mean, std, iterations, alpha, max_step, want_grad: bool):
+        poses, scales, per_frame, t = self._inputs(poses, scales)
+        N, dev = poses.shape[0], poses.device
+        if not isinstance(cons, JointConstraints):
+            raise A2PError(f"constraints must be JointConstraints (got {type(cons).__name__})")
+        if cons.N != N:
+            raise A2PError(f"the constraints cover {cons.N} frames, poses {N}")
+        stat = []
+        for name, v in (("mean", mean), ("std", std)):
+            if v is not None:
+                v = torch.as_tensor(v, dtype=torch.float32).reshape(-1).to(dev).contiguous()
+                if v.numel() != self.P_pos:
+                    raise A2PError(f"{name} must hold P_pos = {self.P_pos} values (got {v.numel()})")
+            stat.append(v)
+        targets, weights = cons.on(dev)
+        d, keep = self.steer_description(t, cons, targets, weights, stat[0], stat[1], scales, per_frame, alpha, iterations, max_step)
+        out = torch.empty_like(poses)
+        loss = torch.empty(N, dtype=torch.float32, device=dev)
+        grad = torch.empty(N, self.P_pos, dtype=torch.float32, device=dev) if want_grad else None
+        with _lib.on_device_of(poses):
+            _lib.check(_lib.load().a2p_skin_steer(C.byref(d), _lib.ptr(poses), self.P_pos, N, _lib.ptr(out), self.P_pos, _lib.ptr(loss),
+                                                  _lib.ptr(grad), _lib.current_stream(dev)), "a2p_skin_steer")
+        del keep
+        return out, loss, grad
+
+    def joint_loss_grad(self, poses, constraints, scales=None, mean=None, std=None):
+        """(loss [N], grad [N, P_pos]) of the constraints at `poses` [N, P_pos] (include/a2p_hip.h a2p_skin_steer with
+        iterations = 0): reach w/2 |p - y|^2, aim w (1 - rot(q, axis) . d), summed over the constraints of a frame, and the
+        gradient with respect to the poses -- or, with `mean` / `std` [P_pos], with respect to z where pose = mean + std z and
+        `poses` holds z.  The scale parameters are constants."""
+        _, loss, grad = self._steer(poses, constraints, scales, mean, std, 0, 1.0, 1.0, True)
+        return loss, grad
+
+    def solve_ik(self, poses, constraints, iterations: int = 2, alpha: float = 1.0, max_step: float = 0.25, scales=None, mean=None,
+                 std=None):
+        """Poses [N, P_pos] moved towards the constraints by `iterations` steps of z <- z - min(alpha L / |g|^2, max_step / |g|inf) g
+        (Polyak's step under a trust region; a2p_skin_steer).  With `mean` / `std` the descent runs in the z-scored space
+        (`poses` holds z, and max_step is in standard deviations); without them in the pose parameters themselves.  Frames
+        whose weights are all zero, and frames whose loss or gradient is zero or not finite, come back unchanged."""
+        return self._steer(poses, constraints, scales, mean, std, iterations, alpha, max_step, False)[0]
 
     def skin(self, mats, verts_unposed=None):
         """[N, V, 3] from skinning matrices [N, J, 3, 4] (what `transforms` returns): LBSModule.pose after the skeleton solve."""

@@ -675,6 +675,52 @@ int a2p_skin_vertices(const float* mats, int64_t N, int32_t J, const float* base
                       const int32_t* idx, const float* w, int32_t V, int32_t K, float gx, float gy, float gz, float* out,
                       void* stream);
 
+/* ---- steering joints to 3D targets (audio2photoreal_amd/sample/steer.py, skinning.py; csrc/kernels_steer.h) -------------------
+ * The skeleton solve of a2p_skin_states with a loss on joint positions and orientations, its gradient with respect to the pose
+ * parameters (a backward pass through the solve) and a few steps of descent, per frame, in one launch.  a2p_steer describes the
+ * skeleton, the constraints and the descent for both entry points:
+ *   skeleton: a2p_skin_states' device tables, plus the children of every joint (child_ptr [J + 1], child_idx ascending inside a
+ *     joint) and the P_pos pose columns of the parameter transform as compressed columns (col_ptr [P_pos + 1], rows ascending /
+ *     cvals); scale [N or 1, P_scale] (scale_per_frame as a2p_skin_states) are constants; global_scaling multiplies a joint's
+ *     translation into its position p.
+ *   theta = mean + std z (mean / std fp32 [P_pos] on the device; either may be NULL: 0 / 1).
+ *   constraints k < K <= A2P_STEER_MAX_CONSTRAINTS: joints / kinds / axes are HOST arrays (joint in [0, J), kind A2P_STEER_REACH
+ *     or A2P_STEER_AIM, axes [K, 3]); targets fp32 [N, K, 3] and weights fp32 [N, K] (>= 0) are device arrays, frame n = b T + t
+ *     in a step.  reach: w/2 |p - y|^2.  aim: w (1 - rot(q_j, axis) . d) with d = (y - p) / |y - p| held constant (the term
+ *     and its gradient are 0 when y = p).  L = the sum over k.
+ *   descent: g = std dL/dtheta; `iterations` times z <- z - min(alpha L / |g|^2, max_step / |g|inf) g.  L = 0, g = 0 and
+ *     non-finite values leave z unchanged.  A frame whose weights are all zero is not touched.
+ * No atomics and a fixed summation order: a frame's result depends on neither N nor its index, and two runs give the same bits.
+ *
+ * a2p_skin_steer: context-free.  z_in [N] rows of P_pos with row stride z_in_stride -> z_out (row stride z_out_stride; may be
+ * z_in with the same stride), loss [N] and grad [N, P_pos] (L and g before the first iteration; either may be NULL).
+ * iterations = 0 computes loss and grad only (z_out = z_in).
+ *
+ * a2p_sample_step_steer: a2p_sample_step of a pose context (nfeats == P_pos; N = B T) whose guided output -- u + scale (a - u), or
+ * the combine of a2p_set_guidance -- is steered per frame before the clamp of clip_denoised and the DDIM / DDPM update.  The
+ * steered rows replace both sequence blocks of the model output, and the unchanged step tail then returns them bit for bit; a
+ * frame whose weights are all zero gets a2p_sample_step's bits.  steer->scale_per_frame must be 0. */
+#define A2P_STEER_MAX_CONSTRAINTS 16
+enum a2p_steer_kind { A2P_STEER_REACH = 0, A2P_STEER_AIM = 1 };
+typedef struct a2p_steer {
+  const int32_t* row_ptr; const int32_t* cols; const float* vals; const float* offsets;
+  const float* joint_offset; const float* pre_rotation;
+  const int32_t* parents; const int32_t* order; const int32_t* level_start;
+  const int32_t* child_ptr; const int32_t* child_idx;
+  const int32_t* col_ptr; const int32_t* rows; const float* cvals;
+  const float* mean; const float* std; const float* scale;
+  const int32_t* joints_host; const int32_t* kinds_host; const float* axes_host;
+  const float* targets; const float* weights;
+  float global_scaling[3];
+  float alpha, max_step;
+  int32_t P_pos, P_scale, J, n_levels, scale_per_frame, K, iterations;
+} a2p_steer;
+int a2p_skin_steer(const a2p_steer* steer, const float* z_in, int64_t z_in_stride, int64_t N, float* z_out, int64_t z_out_stride,
+                   float* loss, float* grad, void* stream);
+int a2p_sample_step_steer(a2p_ctx* ctx, int32_t sampler, const float* x, const int64_t* t_idx, const int64_t* timestep_map,
+                          const float* tables, int32_t n_steps, const float* scale, const float* noise, float eta,
+                          int32_t clip_denoised, const a2p_steer* steer, float* x_next, float* pred_xstart, void* stream);
+
 /* ---- surface maps (reference visualize/ca_body/utils/geom.py; audio2photoreal_amd/surface.py) ---------------------------------
  * Normals, view cosine and UV maps of the posed mesh, fp32 like the reference, for all N frames in one launch each.  Context-free;
  * the topology tables are device arrays built and validated once by the caller (vi / vti [F, 3] int32 with entries in [0, V) /
