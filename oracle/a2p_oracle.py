@@ -151,7 +151,8 @@ def rotary(x: Tensor, freqs: Tensor) -> Tensor:
     L = x.shape[-2]
     ang = torch.arange(L).type(freqs.dtype)[:, None] * freqs[None, :]       # fp32 [L, d/2]
     ang = ang.repeat_interleave(2, dim=-1)                                 # (n r) r=2
-    cos, sin = ang.cos().to(x.dtype), ang.sin().to(x.dtype)
+    ang = ang.to(x.dtype)                                                  # (float64 rows: cos / sin of the fp32 angle in float64, the same on every CPU)
+    cos, sin = ang.cos(), ang.sin()
     x2 = x.reshape(*x.shape[:-1], -1, 2)
     rot = torch.stack((-x2[..., 1], x2[..., 0]), dim=-1).reshape(x.shape)
     return x * cos + rot * sin
@@ -227,9 +228,14 @@ def encoder_layer_rotary(sd: Dict[str, Tensor], p: str, x: Tensor, nheads: int, 
 
 
 def sinusoidal_pos_emb(times: Tensor, dim: int, dtype) -> Tensor:
-    """model/utils.py:67-79 (fp32 like the reference, then cast)."""
+    """model/utils.py:67-79 (fp32 like the reference, then cast).  dtype float64: frequencies, angles and sin / cos in float64 -- the fp32 exp differs
+    in its last bit between CPUs, which moves the angle of timestep 900 by 5e-5 and with it everything a float64 comparison then measures."""
     half = dim // 2
     e = math.log(10000) / (half - 1)
+    if dtype == torch.float64:
+        e = torch.exp(torch.arange(half, dtype=dtype) * -e)
+        e = times.to(dtype)[:, None] * e[None, :]
+        return torch.cat((e.sin(), e.cos()), dim=-1)
     e = torch.exp(torch.arange(half) * -e)
     e = times[:, None] * e[None, :]
     return torch.cat((e.sin(), e.cos()), dim=-1).to(dtype)

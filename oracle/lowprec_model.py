@@ -46,14 +46,14 @@ def _round(x: Tensor, fmt: str) -> Tensor:
     if fmt == "fp32":
         return x
     if fmt == "fp16":
-        return x.half().float()
+        return x.half().to(x.dtype)
     if fmt == "bf16":
-        return x.bfloat16().float()
+        return x.bfloat16().to(x.dtype)
     if fmt == "fp16x2":
-        hi = x.half().float()
-        return hi + (x - hi).half().float()
+        hi = x.half().to(x.dtype)
+        return hi + (x - hi).half().to(x.dtype)
     if fmt in ("fp16+e4m3", "fp16+e5m2"):
-        hi = x.half().float()
+        hi = x.half().to(x.dtype)
         lo = x - hi
         dt = torch.float8_e4m3fn if fmt.endswith("e4m3") else torch.float8_e5m2
         top = 448.0 if fmt.endswith("e4m3") else 57344.0
@@ -61,7 +61,7 @@ def _round(x: Tensor, fmt: str) -> Tensor:
         if m == 0.0:
             return hi
         k = math.floor(math.log2(top / m))           # per-tensor power-of-two scale: the largest |lo| sits just under the format's max
-        return hi + (lo * 2.0 ** k).to(dt).float() * 2.0 ** -k
+        return hi + (lo * 2.0 ** k).to(dt).to(x.dtype) * 2.0 ** -k
     raise ValueError(fmt)
 
 
@@ -118,10 +118,14 @@ def _attn(R: Rounding, pre: str, q: Tensor, k: Tensor, v: Tensor, nheads: int, t
 
 class LowPrecDenoiser(O.OracleDenoiser):
     """OracleDenoiser with the GPU's rounding sites.  The hoisted conditioning (K/V of every layer) is computed once per
-    (cond_embed, drop) like a2p_prepare_cond does and cached on the object."""
+    (cond_embed, drop) like a2p_prepare_cond does and cached on the object.
 
-    def __init__(self, sd, data_format, num_layers, num_heads, rounding: Rounding):
-        super().__init__(sd, data_format, num_layers, num_heads)
+    `dtype` is the arithmetic BETWEEN the rounding sites: float32 as on the GPU (the default), or float64 -- the sites alone, without the fp32
+    accumulation noise, whose order depends on the CPU and its thread count and flips a 16-bit rounding here and there (a few per cent of the
+    largest element error): what tests/forward_paths_oracle.py takes its reproducible envelope from."""
+
+    def __init__(self, sd, data_format, num_layers, num_heads, rounding: Rounding, dtype=torch.float32):
+        super().__init__(sd, data_format, num_layers, num_heads, dtype)
         self.R = rounding
         self._kv = {}
 
@@ -151,7 +155,7 @@ class LowPrecDenoiser(O.OracleDenoiser):
             ct = sd["null_cond_embed"][:, : cond_embed.shape[1], :].expand(cond_embed.shape[0], -1, -1)
             hidden = sd["null_cond_hidden"].expand(cond_embed.shape[0], -1)
         else:
-            ct = _mm(R, "cond.a", cond_embed, "cond.w", sd["cond_projection.weight"], sd["cond_projection.bias"])
+            ct = _mm(R, "cond.a", cond_embed.to(self.dtype), "cond.w", sd["cond_projection.weight"], sd["cond_projection.bias"])
             for i in range(2 if self.data_format == "face" else 0):
                 ct = self._enc_layer(f"cond_encoder.{i}.", ct)
             pooled = ct.mean(dim=-2)                                                   # fp32 skinny path on the GPU
@@ -180,7 +184,7 @@ class LowPrecDenoiser(O.OracleDenoiser):
         if drop == 1.0:
             tok = sd["null_pose_embed"][:, : keyframes.shape[1], :].expand(keyframes.shape[0], -1, -1)
         else:
-            pred = keyframes.clone()
+            pred = keyframes.clone().to(self.dtype)
             pred[~mask[..., :: self.step].squeeze((1, 2))] = 0.0
             hid = _mm(R, "cond.a", pred, "cond.w", sd["frame_cond_projection.weight"], sd["frame_cond_projection.bias"])
             tok = O.layer_norm(hid, sd["frame_norm_cond.weight"], sd["frame_norm_cond.bias"])
@@ -209,19 +213,20 @@ class LowPrecDenoiser(O.OracleDenoiser):
         R, sd, d = self.R, self.sd, self.d
         if x.dim() == 4:
             x = x.permute(0, 3, 1, 2).squeeze(-1)
+        x = x.to(self.dtype)
         ks, vs, cond_hidden, S0 = self._prepare(cond_embed, cond_drop_prob)
         pose = self.data_format == "pose"
         if pose:
             k2s, v2s = self._prepare_keyframes(keyframes, mask, cond_drop_prob)
         x = _mm(R, "in.a", x, "in.w", sd["input_projection.weight"], sd["input_projection.bias"])
-        emb = O.sinusoidal_pos_emb(times, d, torch.float32)
+        emb = O.sinusoidal_pos_emb(times, d, self.dtype)
         t_hidden = O.mish(emb @ sd["time_mlp.1.weight"].T + sd["time_mlp.1.bias"])
         t = t_hidden @ sd["to_time_cond.0.weight"].T + sd["to_time_cond.0.bias"] + cond_hidden
         t_tok = (t_hidden @ sd["to_time_tokens.0.weight"].T + sd["to_time_tokens.0.bias"]).view(-1, 2, d)
         t_tok = O.layer_norm(t_tok, sd["norm_cond.weight"], sd["norm_cond.bias"])
         # rotary of the time tokens at positions S0, S0+1 (they sit behind the audio tokens)
         L_all = S0 + 2
-        pad = torch.zeros(t_tok.shape[0], L_all, d)
+        pad = torch.zeros(t_tok.shape[0], L_all, d, dtype=self.dtype)
         pad[:, S0:] = t_tok
         t_tok_r = O.rotary(pad, self.freqs)[:, S0:]
         for l in range(self.L):

@@ -8,7 +8,7 @@ a2p_debug_read "chain_picks": (family, d, mt, nw, mode, variant, grid, block, n_
 `class_counts(picks)` derive what the long-standing names must show for the same forward: the *_launches counters and the launch
 count of each KERNEL_CHAIN_* timing class."""
 from dataclasses import dataclass
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 PRE, MID, POST, MIDPOST, IN = 0, 1, 2, 3, 4                       # CHAIN_* of csrc/kernels_chain.h
 UNIFORM, MIX, NEXT, LAST, LAST_FINAL, PAIRED_TAIL = range(6)      # variant: generation 1 (0, 1) | tall (2 ..)
@@ -20,7 +20,7 @@ CUS = 256
 # the models of audio2photoreal_amd/spec.py: d_model, feature channels, decoder layers, head_dim, keyframe step
 MODELS = {"face": dict(d=512, C=256, L=8, dh=64, pose=False), "pose": dict(d=256, C=104, L=6, dh=32, pose=True)}
 SWITCHES = ("A2P_CHAIN_V", "A2P_CHAIN_ROWS", "A2P_CHAIN_NW", "A2P_CHAIN_MT", "A2P_CHAIN_NO_MIX", "A2P_NO_SHARED_HALF", "A2P_NO_FUSED_IN",
-            "A2P_NO_FUSED_FINAL", "A2P_NO_FUSED_KF", "A2P_FUSED_TAIL")
+            "A2P_NO_FUSED_FINAL", "A2P_NO_FUSED_KF", "A2P_FUSED_TAIL", "A2P_NO_CHAIN", "A2P_NO_SMALL")
 
 
 @dataclass(frozen=True)
@@ -33,6 +33,8 @@ class Case:
     env: Tuple[Tuple[str, str], ...] = ()      # switches a context re-reads (audio2photoreal_amd/_lib.py ENV_SWITCHES)
     ddpm_step: bool = False                    # a guided a2p_sample_step with the DDPM sampler instead of a plain forward
     tail16: bool = False                       # the context is created under A2P_TAIL16=1
+    layers: Optional[int] = None               # decoder layers of a shallow synthetic model; None: the model's own depth
+    hits: Tuple[Tuple[int, ...], ...] = ()     # SHALLOW_CASES: the kChainInst key every launch must hit, in launch order
 
     @property
     def switches(self) -> Dict[str, str]:
@@ -73,6 +75,91 @@ CASES = (
     Case("c14_body_nw4_mt6", "pose", 1, 80, True, _e(CHAIN_V=4, CHAIN_NW=4, CHAIN_MT=6)),
 )
 BY_NAME = {c.name: c for c in CASES}
+
+# Every kChainInst key (family, d, mt, nw, mode, variant) of csrc/a2p_lib_run.h, written out by hand in the table's order
+# (tests/test_forward_paths_cpu.py compares it with the CI(...) lines of the source).
+_G8_512 = tuple((1, 512, mt, 8, mode, UNIFORM) for mt in (2, 3, 4) for mode in (PRE, MID, POST))
+_G8_MIX = ((1, 512, 3, 8, PRE, MIX), (1, 512, 3, 8, MID, MIX), (1, 512, 3, 8, POST, MIX))
+_G8_256 = tuple((1, 256, mt, 8, mode, UNIFORM) for mt in (2, 3, 4, 5) for mode in (PRE, MID, POST))
+_G4_512 = tuple((1, 512, mt, 4, mode, UNIFORM) for mt in (2, 3, 4) for mode in (PRE, MID, POST))
+_G4_256 = tuple((1, 256, mt, 4, mode, UNIFORM) for mt in (2, 3, 4, 5, 6) for mode in (PRE, MID, POST))
+_MIDPOST = tuple((1, 256, mt, 8, MIDPOST, UNIFORM) for mt in (2, 3, 4, 5)) + tuple((1, 256, mt, 4, MIDPOST, UNIFORM) for mt in (2, 3, 4, 5, 6))
+_TALL = ((4, 512, 3, 8, IN, NEXT), (4, 512, 3, 8, MID, NEXT), (4, 512, 3, 8, POST, NEXT), (4, 512, 3, 8, POST, LAST), (4, 512, 3, 8, POST, LAST_FINAL),
+         (4, 512, 3, 8, POST, PAIRED_TAIL),
+         (4, 512, 4, 8, IN, NEXT), (4, 512, 4, 8, MID, NEXT), (4, 512, 4, 8, POST, NEXT), (4, 512, 4, 8, POST, LAST), (4, 512, 4, 8, POST, LAST_FINAL),
+         (4, 512, 5, 8, IN, NEXT), (4, 512, 5, 8, MID, NEXT), (4, 512, 5, 8, POST, NEXT), (4, 512, 5, 8, POST, LAST), (4, 512, 5, 8, POST, LAST_FINAL))
+INSTANCES = _G8_512 + _G8_MIX + _G8_256 + _G4_512 + _G4_256 + _MIDPOST + _TALL
+
+# ---- shallow synthetic models (1 and 2 decoder layers): the cases of tests/test_forward_paths_hip.py.  Shapes (B, T), all guided unless said:
+#   S88  2 x 88: 352 rows; 88 is a multiple of 8 and >= 80 (the tall contract) and no multiple of 32 / 48 / 64 / 80 / 96 -- every panel height has a
+#        ragged last panel and panels that straddle sequences
+#   S50  3 x 50: T is no multiple of 4 (V^T 4-row groups straddle sequences), odd batch; generation 1 only
+#   S17  5 x 17 (body): T >= 16 is the MIDPOST contract; at 17 every 16-row tile straddles two key sets; one keyframe token
+#   SMIX 26 x 480 (face, one layer): the smallest batch of 480-frame clips whose launches mix 64- and 48-row panels
+# `hits` is written from the launch pattern of the path, NOT from expected(): the CPU test holds the two against each other.
+S88, S50, S17, SMIX, S96 = (2, 88), (3, 50), (5, 17), (26, 480), (2, 96)
+GEN1_HEIGHTS = {"face": tuple((mt, nw) for nw in (8, 4) for mt in (2, 3, 4)),
+                "pose": tuple((mt, 8) for mt in (2, 3, 4, 5)) + tuple((mt, 4) for mt in (2, 3, 4, 5, 6))}
+
+
+def _shallow(name, fmt, shape, hits, layers=2, guided=True, **kw):
+    flags = {k: kw.pop(k) for k in ("ddpm_step", "tail16") if k in kw}
+    return Case(name, fmt, shape[0], shape[1], guided, _e(**kw), layers=layers, hits=tuple(hits), **flags)
+
+
+def _gen1_hits(d, mt, nw, layers, kind="post", variant=UNIFORM, pre=None):
+    """PRE once, then per layer MID + POST (face), MID + MIDPOST (body) or MID + MID2 + POST (body without the fused keyframe attention)."""
+    per_layer = {"post": (MID, POST), "midpost": (MID, MIDPOST), "mid2": (MID, MID, POST)}[kind]
+    return [pre or (1, d, mt, nw, PRE, variant)] + [(1, d, mt, nw, mode, variant) for _ in range(layers) for mode in per_layer]
+
+
+def _tall_hits(mt, first, last, post0=None):
+    """Two layers of the tall family: `first` = layer 0's first kernel, `post0` = layer 0's POST kernel where it is not tall, `last` = the last POST variant."""
+    return [first, (4, 512, mt, 8, MID, NEXT), post0 or (4, 512, mt, 8, POST, NEXT), (4, 512, mt, 8, MID, NEXT), (4, 512, mt, 8, POST, last)]
+
+
+def _shallow_cases():
+    out = []
+    for sname, shape in (("S88", S88), ("S50", S50)):
+        for mt, nw in GEN1_HEIGHTS["face"]:
+            out.append(_shallow(f"face_{sname}_gen1_mt{mt}_nw{nw}", "face", shape, _gen1_hits(512, mt, nw, 2), CHAIN_V=1, CHAIN_MT=mt, CHAIN_NW=nw))
+        for mt, nw in GEN1_HEIGHTS["pose"]:
+            out.append(_shallow(f"pose_{sname}_midpost_mt{mt}_nw{nw}", "pose", shape, _gen1_hits(256, mt, nw, 2, "midpost"), CHAIN_MT=mt, CHAIN_NW=nw))
+            out.append(_shallow(f"pose_{sname}_no_fused_kf_mt{mt}_nw{nw}", "pose", shape, _gen1_hits(256, mt, nw, 2, "mid2"),
+                                CHAIN_MT=mt, CHAIN_NW=nw, NO_FUSED_KF=1))
+    for mt, nw in GEN1_HEIGHTS["pose"]:
+        out.append(_shallow(f"pose_S17_midpost_mt{mt}_nw{nw}", "pose", S17, _gen1_hits(256, mt, nw, 2, "midpost"), CHAIN_MT=mt, CHAIN_NW=nw))
+    for mt in (3, 4, 5):
+        tall_in = (4, 512, mt, 8, IN, NEXT)
+        # a generation-1 kernel of a forward whose forced height it does not have (80 rows) takes the candidate loop: 32-row panels at 176 and 352 rows
+        # (6 / 11 panels: one round of 24 against one of 28 for 48-row panels)
+        g1 = mt if mt <= 4 else 2
+        env = dict(CHAIN_V=4, CHAIN_MT=mt)
+        out.append(_shallow(f"face_S88_tall_mt{mt}", "face", S88, _tall_hits(mt, tall_in, LAST_FINAL), **env))
+        out.append(_shallow(f"face_S88_tall_mt{mt}_no_fused_final", "face", S88, _tall_hits(mt, tall_in, LAST), NO_FUSED_FINAL=1, **env))
+        out.append(_shallow(f"face_S88_tall_mt{mt}_no_fused_in", "face", S88, _tall_hits(mt, (1, 512, g1, 8, PRE, UNIFORM), LAST_FINAL), NO_FUSED_IN=1, **env))
+        out.append(_shallow(f"face_S88_tall_mt{mt}_no_shared_half", "face", S88, _tall_hits(mt, (1, 512, g1, 8, PRE, UNIFORM), LAST_FINAL),
+                            NO_SHARED_HALF=1, **env))
+        out.append(_shallow(f"face_S88_tall_mt{mt}_family41", "face", S88, _tall_hits(mt, tall_in, LAST_FINAL, post0=(1, 512, g1, 8, POST, UNIFORM)),
+                            CHAIN_V=41, CHAIN_MT=mt))
+        out.append(_shallow(f"face_S88_tall_mt{mt}_unguided", "face", S88, _tall_hits(mt, tall_in, LAST_FINAL), guided=False, **env))
+    # A2P_TAIL16: final_layer on 16-bit operands inside the last generation-1 POST kernel; no split-operand islands, so no fused input kernel either
+    out.append(_shallow("face_S88_tail16_gen1", "face", S88, _gen1_hits(512, 3, 8, 2), tail16=True, CHAIN_V=1, CHAIN_MT=3, CHAIN_NW=8))
+    out.append(_shallow("face_S88_tail16_tall", "face", S88,
+                        [(1, 512, 3, 8, PRE, UNIFORM), (4, 512, 3, 8, MID, NEXT), (4, 512, 3, 8, POST, NEXT), (4, 512, 3, 8, MID, NEXT), (1, 512, 3, 8, POST, UNIFORM)],
+                        tail16=True, CHAIN_V=4, CHAIN_MT=3))
+    # one guided DDPM step: paired 48-row panels and the step tail in the last POST kernel (384 rows: 48-row panels by the cost rule)
+    out.append(_shallow("face_S96_ddpm_paired_tail", "face", S96, _tall_hits(3, (4, 512, 3, 8, IN, NEXT), PAIRED_TAIL), ddpm_step=True, CHAIN_V=4, CHAIN_ROWS=1))
+    # one layer, 24960 rows: MID and POST mix panel heights (the shared first half, 12480 rows, takes 32-row panels); without the shared half PRE mixes too
+    out.append(_shallow("face_SMIX", "face", SMIX, _gen1_hits(512, 3, 8, 1, variant=MIX, pre=(1, 512, 2, 8, PRE, UNIFORM)), layers=1, CHAIN_V=1))
+    out.append(_shallow("face_SMIX_no_shared_half", "face", SMIX, _gen1_hits(512, 3, 8, 1, variant=MIX), layers=1, CHAIN_V=1, NO_SHARED_HALF=1))
+    return tuple(out)
+
+
+SHALLOW_CASES = _shallow_cases()
+SHALLOW_BY_NAME = {c.name: c for c in SHALLOW_CASES}
+# instances no shallow case launches: {key: the reason, naming the source line that makes it unreachable}.  At most 4 entries.
+NOT_REACHED: Dict[Tuple[int, ...], str] = {}
 
 
 def _num(sw, name, default=0):
@@ -147,7 +234,7 @@ def expected(case: Case, family=None):
     whose family the library measures (A2P_CHAIN_V unset)."""
     assert takes_chain_path(case), case
     sw, m = case.switches, MODELS[case.fmt]
-    d, L, T, B = m["d"], m["L"], case.T, case.B
+    d, L, T, B = m["d"], case.layers or m["L"], case.T, case.B
     N = 2 * B if case.guided else B
     nw = pick_nw(case)
     fam = pick_family(case, nw) or family
