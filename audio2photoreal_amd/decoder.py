@@ -28,22 +28,19 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, avatar
 from ._lib import A2PError
+from .avatar import HostNet, as_numpy, asset, checked, gpu_f32, source
 
 LRELU_SLOPE = 0.2
 ASSET_KEYS = ("pose_cond_mask", "head_cond_mask", "face_cond_mask", "body_cond_mask", "seam_data_1024")
 
 
 # ------------------------------------------------------------------------------------------------ host preparation
-def _np(a) -> np.ndarray:
-    return np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
-
-
 def fold_weight_norm(weight_v, weight_g) -> np.ndarray:
     """float32 w = weight_v * (weight_g / ||weight_v||): weight_norm_wrapper(..., g_dim=0, v_dim=None), whose norm runs over the
     WHOLE weight_v tensor; weight_g is [C_out, 1, ...].  Computed in float64 and rounded once."""
-    v, g = _np(weight_v).astype(np.float64), _np(weight_g).astype(np.float64)
+    v, g = as_numpy(weight_v).astype(np.float64), as_numpy(weight_g).astype(np.float64)
     return np.ascontiguousarray(v * (g / np.sqrt((v * v).sum())), np.float32)
 
 
@@ -53,21 +50,9 @@ def folded_weight(state_dict, name: str, shape) -> np.ndarray:
     shape = tuple(int(s) for s in shape)
     g_shape = (shape[0],) + (1,) * (len(shape) - 1)
     if f"{name}.weight" in state_dict:
-        return _checked(state_dict, f"{name}.weight", shape)
-    v, g = _checked(state_dict, f"{name}.weight_v", shape), _checked(state_dict, f"{name}.weight_g", g_shape)
+        return checked(state_dict, f"{name}.weight", shape)
+    v, g = checked(state_dict, f"{name}.weight_v", shape), checked(state_dict, f"{name}.weight_g", g_shape)
     return fold_weight_norm(v, g)
-
-
-def _checked(state_dict, key: str, shape) -> np.ndarray:
-    if key not in state_dict:
-        raise ValueError(f"the state dict has no `{key}` (expected shape {list(shape)})")
-    a = _np(state_dict[key])
-    if tuple(a.shape) != tuple(shape):
-        raise ValueError(f"`{key}` has shape {list(a.shape)}; the configuration expects {list(shape)}")
-    bad = np.argwhere(~np.isfinite(a))
-    if bad.size:
-        raise ValueError(f"`{key}`{list(map(int, bad[0]))} is not finite ({a[tuple(bad[0])]})")
-    return np.ascontiguousarray(a, np.float32)
 
 
 def resolve_seam_pairs(dst_ij, src_ij, H: int, W: int):
@@ -76,7 +61,7 @@ def resolve_seam_pairs(dst_ij, src_ij, H: int, W: int):
     are read before any destination is written, so a chain a -> b, b -> c gives c the original b."""
     flat = []
     for name, a in (("dst_ij", dst_ij), ("src_ij", src_ij)):
-        a = _np(a)
+        a = as_numpy(a)
         if a.ndim != 2 or a.shape[1] != 2 or not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
             raise ValueError(f"{name} must be an integer array [P, 2] (got {a.dtype} {list(a.shape)})")
         a = a.astype(np.int64)
@@ -93,22 +78,13 @@ def resolve_seam_pairs(dst_ij, src_ij, H: int, W: int):
     return dst[keep], src[keep]
 
 
-def _gpu_f32(x, name: str, shape: str, ok):
-    if not torch.is_tensor(x):
-        raise A2PError(f"{name} must be a tensor on the MI355X (got {type(x).__name__})")
-    _lib.require_gpu_tensor(x, name)
-    if x.dtype != torch.float32 or not ok(tuple(x.shape)):
-        raise A2PError(f"{name} must be float32 {shape} (got {x.dtype} {list(x.shape)})")
-    return x
-
-
 # ------------------------------------------------------------------------------------------------ the seam sampler
-class SeamSampler:
+class SeamSampler(HostNet):
     """SeamSampler(seam_data) of utils/seams.py: seam_data holds dst_ij / src_ij [P, 2] (row, column), uvs [H, W, 2] and weights
     [H, W] or [H, W, 1].  The pair list is resolved on the host here (resolve_seam_pairs); device copies are made on first use."""
 
     def __init__(self, seam_data):
-        uvs, weights = _np(seam_data["uvs"]), _np(seam_data["weights"])
+        uvs, weights = as_numpy(seam_data["uvs"]), as_numpy(seam_data["weights"])
         if uvs.ndim != 3 or uvs.shape[2] != 2 or min(uvs.shape[:2]) < 1:
             raise ValueError(f"uvs must be [H, W, 2] (got {list(uvs.shape)})")
         self.H, self.W = int(uvs.shape[0]), int(uvs.shape[1])
@@ -124,18 +100,11 @@ class SeamSampler:
         self.weights = np.ascontiguousarray(weights.reshape(self.H, self.W), np.float32)
         self.dst, self.src = resolve_seam_pairs(seam_data["dst_ij"], seam_data["src_ij"], self.H, self.W)
         self.P = int(self.dst.size)
+        self.params = {"dst": self.dst.astype(np.int32), "src": self.src.astype(np.int32), "uvs": self.uvs, "weights": self.weights}
         self._dev = {}
 
-    def _tables(self, device):
-        key = str(device)
-        if key not in self._dev:
-            i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(device)
-            self._dev[key] = {"dst": i32(self.dst), "src": i32(self.src), "uvs": torch.from_numpy(self.uvs).to(device),
-                              "weights": torch.from_numpy(self.weights).to(device)}
-        return self._dev[key]
-
     def _value(self, value, name):
-        return _gpu_f32(value, name, f"[N, C, {self.H}, {self.W}]", lambda s: len(s) == 4 and s[2:] == (self.H, self.W))
+        return gpu_f32(value, name, f"[N, C, {self.H}, {self.W}]", lambda s: len(s) == 4 and s[2:] == (self.H, self.W))
 
     def impaint(self, value):
         """value[:, :, dst] = (value before the call)[:, :, src], IN PLACE like the reference (value must be contiguous); returns
@@ -172,17 +141,6 @@ class SeamSampler:
 
 
 # ------------------------------------------------------------------------------------------------ the layer
-def _source(x, name: str):
-    """(tensor kept alive, A2PConvSource): [N, C, H, W] float32 on the GPU whose planes are dense; the frames may be further apart
-    than C H W (a channel window x[:, a:b] of a contiguous tensor is passed as it is), anything else is made contiguous."""
-    x = _gpu_f32(x, name, "[N, C, H, W] with C, H, W >= 1", lambda s: len(s) == 4 and min(s[1:]) >= 1)
-    N, C, H, W = x.shape
-    dense = x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W and (N <= 1 or x.stride(0) >= C * H * W)
-    if not dense:
-        x = x.contiguous()
-    return x, _lib.A2PConvSource(_lib.ptr(x), x.stride(0) if N > 1 else C * H * W, C, H, W, 0)
-
-
 def conv2d_ub(x, weight, bias=None, *, groups: int = 1, size=None, slope=None, skip=None, skip_src=None, skip_weight=None,
               skip_bias=None, mask=None):
     """One launch of the decoder layer (a2p_conv2d_ub): out [N, C_out, H, W] =
@@ -193,13 +151,13 @@ def conv2d_ub(x, weight, bias=None, *, groups: int = 1, size=None, slope=None, s
     skip_weight [C_out, C_s / groups] (or [.., 1, 1]) and skip_bias [C_out] or None -- the 1 x 1 convolution, with the same
     groups, of a second source that is upsampled the same way; mask [H, W] or None.  At most 4096 channels per group."""
     keep = []
-    x, xs = _source(x, "x")
+    x, xs = source(x, "x")
     N, C_in, Hs, Ws = x.shape
     dev = x.device
     H, W = (Hs, Ws) if size is None else (int(size[0]), int(size[1]))
 
     def operand(t, name, shape_text, ok):
-        t = _gpu_f32(t, name, shape_text, ok)
+        t = gpu_f32(t, name, shape_text, ok)
         if t.device != dev:
             raise A2PError(f"{name} is on {t.device}, x on {dev}")
         t = t.contiguous()
@@ -224,7 +182,7 @@ def conv2d_ub(x, weight, bias=None, *, groups: int = 1, size=None, slope=None, s
         skip = operand(skip, "skip", f"[{N}, {C_out}, {H}, {W}]", lambda s: s == (N, C_out, H, W))
         d.skip, d.skip_mode = _lib.ptr(skip), _lib.CONV_SKIP_TENSOR
     if skip_src is not None:
-        skip_src, ss = _source(skip_src, "skip_src")
+        skip_src, ss = source(skip_src, "skip_src")
         keep.append(skip_src)
         C_s = skip_src.shape[1]
         if skip_src.shape[0] != N or skip_src.device != dev or C_s % groups:
@@ -248,21 +206,10 @@ def conv2d_ub(x, weight, bias=None, *, groups: int = 1, size=None, slope=None, s
 
 
 # ------------------------------------------------------------------------------------------------ the decoder
-def _asset(assets, key):
-    if hasattr(assets, "keys") and key in assets:
-        return assets[key]
-    if hasattr(assets, key):
-        return getattr(assets, key)
-    raise ValueError(f"the assets hold no `{key}` (needed: {', '.join(ASSET_KEYS)})")
-
-
-class BodyDecoder:
+class BodyDecoder(HostNet):
     """ConvDecoder of mesh_vae_drivable.py: pose, embedding and face embedding to the UV displacement of the unposed mesh and the
     mean texture.  Host arrays (folded float32 weights under the reference's key names, `name.weight` / `name.bias`) live on the
     object in `params`; device copies are made on first use, per device."""
-
-    def __init__(self):
-        raise TypeError("use BodyDecoder.from_state_dict")
 
     @classmethod
     def from_state_dict(cls, state_dict, assets, surface, prefix: str = "decoder.", uv_size: int = 1024, init_uv_size: int = 64,
@@ -305,21 +252,21 @@ class BodyDecoder:
         p = {}
         for name, cin, cout, size, k, groups in [self.pose_block, *self.embs_blocks, *self.face_blocks, self.joint_block, *self.up_blocks]:
             p[f"{name}.conv_resize.weight"] = folded_weight(sd, f"{name}.conv_resize", (cout, cin // groups, 1, 1))
-            p[f"{name}.conv_resize.bias"] = _checked(sd, f"{name}.conv_resize.bias", (cout,))
+            p[f"{name}.conv_resize.bias"] = checked(sd, f"{name}.conv_resize.bias", (cout,))
             p[f"{name}.conv1.weight"] = folded_weight(sd, f"{name}.conv1", (cin, cin // groups, k, k))
-            p[f"{name}.conv1.bias"] = _checked(sd, f"{name}.conv1.bias", (cin, size, size))
+            p[f"{name}.conv1.bias"] = checked(sd, f"{name}.conv1.bias", (cin, size, size))
             p[f"{name}.conv2.weight"] = folded_weight(sd, f"{name}.conv2", (cout, cin // groups, k, k))
-            p[f"{name}.conv2.bias"] = _checked(sd, f"{name}.conv2.bias", (cout, size, size))
+            p[f"{name}.conv2.bias"] = checked(sd, f"{name}.conv2.bias", (cout, size, size))
         for name, n_in, n_out in (("embs_fc.0", self.n_embs, 4 * 4 * 128), ("face_embs_fc.0", self.n_face_embs, 4 * 4 * 32)):
             p[f"{name}.weight"] = folded_weight(sd, name, (n_out, n_in))
-            p[f"{name}.bias"] = _checked(sd, f"{name}.bias", (n_out,))
+            p[f"{name}.bias"] = checked(sd, f"{name}.bias", (n_out,))
         for name in ("verts_conv", "tex_conv"):
             p[f"{name}.weight"] = folded_weight(sd, name, (3, C[-1], 3, 3))
-            p[f"{name}.bias"] = _checked(sd, f"{name}.bias", (3, self.uv_size, self.uv_size))
+            p[f"{name}.bias"] = checked(sd, f"{name}.bias", (3, self.uv_size, self.uv_size))
         self.params = p
 
         def mask(key, shape):
-            a = _np(_asset(assets, key))
+            a = as_numpy(asset(assets, key, ASSET_KEYS))
             if tuple(a.shape) != shape:
                 raise ValueError(f"assets `{key}` has shape {list(a.shape)}; the configuration expects {list(shape)}")
             return a.astype(np.float64)
@@ -332,23 +279,22 @@ class BodyDecoder:
         self.face_cond_mask = np.ascontiguousarray(face_m, np.float32)
         self.body_cond_mask = np.ascontiguousarray(body_m, np.float32)
         self.non_head_mask = np.clip(self.body_cond_mask * (np.float32(1.0) - self.face_cond_mask), 0.0, 1.0).astype(np.float32)
-        self.seam_sampler = SeamSampler(_asset(assets, "seam_data_1024"))
+        self.seam_sampler = SeamSampler(asset(assets, "seam_data_1024", ASSET_KEYS))
         if (self.seam_sampler.H, self.seam_sampler.W) != (self.uv_size, self.uv_size):
             raise ValueError(f"assets `seam_data_1024` is for {self.seam_sampler.H} x {self.seam_sampler.W} maps; uv_size={self.uv_size}")
         self._dev = {}
         return self
 
     def _tables(self, device):
-        key = str(device)
-        if key not in self._dev:
+        fresh = str(device) not in self._dev
+        t = super()._tables(device)
+        if fresh:
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-            t = {k: up(v) for k, v in self.params.items()}
             t.update(pose_cond_mask=up(self.pose_cond_mask), non_head_mask=up(self.non_head_mask),
                      face_quadrant=up(self.face_cond_mask[32:, :32]), non_head_quadrant=up(self.non_head_mask[32:, :32]))
             for name in ("embs_fc.0", "face_embs_fc.0"):                      # a linear layer is a 1 x 1 convolution of a 1 x 1 plane
                 t[f"{name}.weight"] = t[f"{name}.weight"][:, :, None, None]
-            self._dev[key] = t
-        return self._dev[key]
+        return t
 
     def activation_bytes_per_frame(self) -> int:
         """An upper bound of the bytes one frame's forward allocates (every intermediate counted as if none were freed)."""
@@ -377,12 +323,12 @@ class BodyDecoder:
         n_embs_enc_channels, 64, 64] skips the embedding branch (it is not modified).  Returns geom_delta_rec [N, V, 3],
         geom_uv_delta_rec and tex_mean_rec [N, 3, uv_size, uv_size], embs_conv (merged with the face features) and pose_conv."""
         P, E = self.n_pose_dims, self.n_embs_enc_channels
-        motion = _gpu_f32(motion, "motion", f"[N, {6 + P}]", lambda s: len(s) == 2 and s[1] == 6 + P)
+        motion = gpu_f32(motion, "motion", f"[N, {6 + P}]", lambda s: len(s) == 2 and s[1] == 6 + P)
         N, dev = motion.shape[0], motion.device
-        embs = _gpu_f32(embs, "embs", f"[{N}, {self.n_embs}]", lambda s: s == (N, self.n_embs))
-        face_embs = _gpu_f32(face_embs, "face_embs", f"[{N}, {self.n_face_embs}]", lambda s: s == (N, self.n_face_embs))
+        embs = gpu_f32(embs, "embs", f"[{N}, {self.n_embs}]", lambda s: s == (N, self.n_embs))
+        face_embs = gpu_f32(face_embs, "face_embs", f"[{N}, {self.n_face_embs}]", lambda s: s == (N, self.n_face_embs))
         if embs_conv is not None:
-            embs_conv = _gpu_f32(embs_conv, "embs_conv", f"[{N}, {E}, 64, 64]", lambda s: s == (N, E, 64, 64))
+            embs_conv = gpu_f32(embs_conv, "embs_conv", f"[{N}, {E}, 64, 64]", lambda s: s == (N, E, 64, 64))
         for name, x in (("embs", embs), ("face_embs", face_embs), ("embs_conv", embs_conv)):
             if x is not None and x.device != dev:
                 raise A2PError(f"{name} is on {x.device}, motion on {dev}")
@@ -423,43 +369,26 @@ def decode_motion(decoder: BodyDecoder, skeleton, poses, embs, face_embs, max_by
     same leading axes.  The decoder runs in chunks of frames whose activations (BodyDecoder.activation_bytes_per_frame) stay
     under max_bytes, at least one frame; its geom_delta_rec goes to skeleton.pose_vertices as verts_unposed.  A frame's result
     does not depend on the chunking.  The outputs themselves take N (6 V + 3 H H) 4 bytes."""
-    from .skinning import motion_frames
-    if skeleton.P_pos != 6 + decoder.n_pose_dims:
-        raise A2PError(f"the skeleton takes {skeleton.P_pos} pose parameters; the decoder 6 + n_pose_dims = {6 + decoder.n_pose_dims}")
+    avatar.check_pose_width(skeleton, decoder)
     if skeleton.V != decoder.surface.V:
         raise A2PError(f"the skeleton skins V={skeleton.V} vertices; the decoder's surface has V={decoder.surface.V}")
-    frames, lead = motion_frames(poses, skeleton.P_pos)
-    if not torch.is_tensor(frames):
-        frames = torch.from_numpy(frames)
-    if not frames.is_cuda:
-        if not torch.cuda.is_available():
-            raise A2PError("decode_motion runs on the MI355X; there is no CPU implementation")
-        frames = frames.to("cuda")
+    frames, lead = avatar.clip_frames("decode_motion", poses, skeleton.P_pos)
     N, dev = frames.shape[0], frames.device
-
-    def flat(x, name, width):
-        x = torch.as_tensor(x)
-        if tuple(x.shape) != (*lead, width):
-            raise A2PError(f"{name} must be {[*lead, width]} (got {list(x.shape)})")
-        return x.to(device=dev, dtype=torch.float32).reshape(N, width).contiguous()
-
-    embs, face_embs = flat(embs, "embs", decoder.n_embs), flat(face_embs, "face_embs", decoder.n_face_embs)
-    chunk = max(1, int(max_bytes) // decoder.activation_bytes_per_frame())
+    embs = avatar.per_frame(embs, "embs", lead, (decoder.n_embs,), dev)
+    face_embs = avatar.per_frame(face_embs, "face_embs", lead, (decoder.n_face_embs,), dev)
     H, V = decoder.uv_size, skeleton.V
     out = {"vertices": torch.empty(N, V, 3, dtype=torch.float32, device=dev),
            "tex_mean": torch.empty(N, 3, H, H, dtype=torch.float32, device=dev),
            "geom_delta": torch.empty(N, V, 3, dtype=torch.float32, device=dev)}
-    for a in range(0, N, chunk):
-        b = min(N, a + chunk)
-        preds = decoder.forward(frames[a:b], embs[a:b], face_embs[a:b])
+    for a, b in avatar.frame_chunks(N, max_bytes, decoder.activation_bytes_per_frame()):
+        preds, out["vertices"][a:b] = avatar.decode_and_pose(decoder, skeleton, frames[a:b], embs[a:b], face_embs[a:b])
         out["geom_delta"][a:b] = preds["geom_delta_rec"]
         out["tex_mean"][a:b] = preds["tex_mean_rec"]
-        out["vertices"][a:b] = skeleton.pose_vertices(frames[a:b], verts_unposed=preds["geom_delta_rec"])
     return {"vertices": out["vertices"].reshape(*lead, V, 3), "tex_mean": out["tex_mean"].reshape(*lead, 3, H, H),
             "geom_delta": out["geom_delta"].reshape(*lead, V, 3)}
 
 
-def main(argv=None) -> int:
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m audio2photoreal_amd.decoder",
                                  description="Decode body geometry and mean texture for the motions of a results.npy.")
     ap.add_argument("--results", required=True, help="results.npy of sample.generate (key `motions` [B, 104, 1, T], un-normalised)")
@@ -467,41 +396,18 @@ def main(argv=None) -> int:
     ap.add_argument("--assets", required=True, help="static_assets.pt: topology, the skinning model, the four masks, seam_data_1024")
     ap.add_argument("--checkpoint", required=True, help="the body decoder's state dict (keys under --prefix)")
     ap.add_argument("--out", required=True, help="decoded.npy: a pickled dict of float32 arrays")
-    ap.add_argument("--prefix", default="decoder.")
     ap.add_argument("--frames", default=None, metavar="A:B", help="frames A..B-1 of the time axis only")
     ap.add_argument("--max-bytes", type=int, default=1 << 30, help="activation budget of one decoder chunk")
-    for name, default in (("uv-size", 1024), ("init-uv-size", 64), ("n-pose-dims", 98), ("n-pose-enc-channels", 16), ("n-embs", 1024),
-                          ("n-embs-enc-channels", 32), ("n-face-embs", 256), ("n-init-channels", 64), ("n-min-channels", 4)):
-        ap.add_argument(f"--{name}", type=int, default=default)
-    args = ap.parse_args(argv)
-    from .skinning import BodySkeleton
-    from .surface import BodySurface
-    block = np.load(args.results, allow_pickle=True).item()
-    motions = block.get("motions", block.get("motion"))
-    if motions is None:
-        raise A2PError(f"{args.results} holds neither `motions` nor `motion` (keys: {sorted(block)})")
-    motions = np.asarray(motions, np.float32)
-    e = np.load(args.embeddings)
-    for key in ("embs", "face_embs"):
-        if key not in e.files:
-            raise A2PError(f"{args.embeddings} holds no `{key}` (keys: {sorted(e.files)})")
-    embs, face_embs = np.asarray(e["embs"], np.float32), np.asarray(e["face_embs"], np.float32)
-    if motions.ndim == 4:
-        motions = np.ascontiguousarray(motions[:, :, 0].transpose(0, 2, 1))               # [B, T, P]
-    if args.frames is not None:
-        a, _, b = args.frames.partition(":")
-        window = slice(int(a) if a else None, int(b) if b else None)
-        motions, embs, face_embs = motions[:, window], embs[:, window], face_embs[:, window]
-    if not torch.cuda.is_available():
-        raise A2PError("the decoder runs on the MI355X; there is no CPU implementation")
-    assets = torch.load(args.assets, map_location="cpu", weights_only=False)
-    state = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
-    surface = BodySurface.from_static_assets(assets, uv_size=args.uv_size)
-    decoder = BodyDecoder.from_state_dict(
-        state, assets, surface, prefix=args.prefix, uv_size=args.uv_size, init_uv_size=args.init_uv_size, n_pose_dims=args.n_pose_dims,
-        n_pose_enc_channels=args.n_pose_enc_channels, n_embs=args.n_embs, n_embs_enc_channels=args.n_embs_enc_channels,
-        n_face_embs=args.n_face_embs, n_init_channels=args.n_init_channels, n_min_channels=args.n_min_channels)
-    out = decode_motion(decoder, BodySkeleton.from_static_assets(assets), motions, embs, face_embs, max_bytes=args.max_bytes)
+    avatar.add_network_arguments(ap, decoder_only=True)
+    return ap
+
+
+def main(argv=None) -> int:
+    args = parser().parse_args(argv)
+    motions, embs, face_embs = avatar.load_motion_clip(args.results, args.embeddings, args.frames)
+    avatar.require_gpu("the decoder runs")
+    person = avatar.load_avatar(args.assets, args.checkpoint, args)
+    out = decode_motion(person.decoder, person.skeleton, motions, embs, face_embs, max_bytes=args.max_bytes)
     np.save(args.out, {k: v.cpu().numpy() for k, v in out.items()})
     print(f"{args.out}: " + ", ".join(f"{k} {list(v.shape)}" for k, v in out.items()))
     return 0

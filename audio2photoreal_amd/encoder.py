@@ -25,27 +25,16 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, avatar
 from ._lib import A2PError
-from .decoder import LRELU_SLOPE, _checked, _gpu_f32, _np, _source, conv2d_ub
-from .texture import _operand, conv_transpose2d_ub, folded_weight64, folded_weight_transposed, resize_bilinear
+from .avatar import HostNet, as_numpy, asset, checked, f32, gpu_f32, operand, resize_axis_half64, source
+from .decoder import LRELU_SLOPE, conv2d_ub
+from .texture import conv_transpose2d_ub, folded_weight64, folded_weight_transposed, resize_bilinear
 
 LOGVAR_SCALE = 0.1
 
 
 # ------------------------------------------------------------------------------------------------ host preparation
-def _f32(a) -> np.ndarray:
-    return np.ascontiguousarray(a, np.float32)
-
-
-def _asset(assets, key):
-    if hasattr(assets, "keys") and key in assets:
-        return assets[key]
-    if hasattr(assets, key):
-        return getattr(assets, key)
-    raise ValueError(f"the assets hold no `{key}`")
-
-
 def linear_slices(n_in: int) -> int:
     """The number of partial sums a2p_linear_f32 cuts a row of n_in terms into: a function of n_in alone."""
     return (int(n_in) + _lib.LINEAR_KSLICE - 1) // _lib.LINEAR_KSLICE
@@ -57,18 +46,12 @@ def _resize_axis_corners64(n_in: int, n_out: int):
     return i0, np.minimum(i0 + 1, n_in - 1), src - i0
 
 
-def _resize_axis_half64(n_in: int, n_out: int):
-    src = np.maximum((np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5, 0.0)
-    i0 = np.minimum(src.astype(np.int64), n_in - 1)
-    return i0, i0 + (i0 < n_in - 1), src - i0
-
-
 def resize_mask64(mask, size: int, align_corners: bool) -> np.ndarray:
     """float64 [size, size]: F.interpolate(mask[None, None], (size, size), mode="bilinear", align_corners=...) restated."""
-    m = _np(mask).astype(np.float64)
+    m = as_numpy(mask).astype(np.float64)
     if m.ndim != 2 or min(m.shape) < 1:
         raise ValueError(f"a mask must be [H, W] (got {list(m.shape)})")
-    axis = _resize_axis_corners64 if align_corners else _resize_axis_half64
+    axis = _resize_axis_corners64 if align_corners else resize_axis_half64
     (y0, y1, ly), (x0, x1, lx) = axis(m.shape[0], int(size)), axis(m.shape[1], int(size))
     top = (1 - lx) * m[y0][:, x0] + lx * m[y0][:, x1]
     bot = (1 - lx) * m[y1][:, x0] + lx * m[y1][:, x1]
@@ -76,8 +59,8 @@ def resize_mask64(mask, size: int, align_corners: bool) -> np.ndarray:
 
 
 def _linear_params(sd, name: str, n_out: int, n_in: int, p: dict):
-    p[f"{name}.weight"] = _f32(folded_weight64(sd, name, (n_out, n_in)))
-    p[f"{name}.bias"] = _checked(sd, f"{name}.bias", (n_out,))
+    p[f"{name}.weight"] = f32(folded_weight64(sd, name, (n_out, n_in)))
+    p[f"{name}.bias"] = checked(sd, f"{name}.bias", (n_out,))
 
 
 def _first_dim(sd, key: str, ndim: int, axis: int = 0) -> int:
@@ -99,12 +82,12 @@ def _down_ladder(sd, names, size: int, c_in: int, p: dict):
         if size < 2 or size % 2:
             raise ValueError(f"`{name}` would halve a {size} x {size} map: the ladder is too deep for the input size")
         c_out = _first_dim(sd, f"{name}.conv2", 4)
-        p[f"{name}.conv_resize.weight"] = _f32(folded_weight64(sd, f"{name}.conv_resize", (c_out, c_in, 1, 1))).reshape(c_out, c_in)
-        p[f"{name}.conv_resize.bias"] = _checked(sd, f"{name}.conv_resize.bias", (c_out,))
-        p[f"{name}.conv1.weight"] = _f32(folded_weight64(sd, f"{name}.conv1", (c_in, c_in, 3, 3)))
-        p[f"{name}.conv1.bias"] = _checked(sd, f"{name}.conv1.bias", (c_in, size, size))
-        p[f"{name}.conv2.weight"] = _f32(folded_weight64(sd, f"{name}.conv2", (c_out, c_in, 3, 3)))
-        p[f"{name}.conv2.bias"] = _checked(sd, f"{name}.conv2.bias", (c_out, size // 2, size // 2))
+        p[f"{name}.conv_resize.weight"] = f32(folded_weight64(sd, f"{name}.conv_resize", (c_out, c_in, 1, 1))).reshape(c_out, c_in)
+        p[f"{name}.conv_resize.bias"] = checked(sd, f"{name}.conv_resize.bias", (c_out,))
+        p[f"{name}.conv1.weight"] = f32(folded_weight64(sd, f"{name}.conv1", (c_in, c_in, 3, 3)))
+        p[f"{name}.conv1.bias"] = checked(sd, f"{name}.conv1.bias", (c_in, size, size))
+        p[f"{name}.conv2.weight"] = f32(folded_weight64(sd, f"{name}.conv2", (c_out, c_in, 3, 3)))
+        p[f"{name}.conv2.bias"] = checked(sd, f"{name}.conv2.bias", (c_out, size // 2, size // 2))
         specs.append((name, c_in, c_out, size))
         c_in, size = c_out, size // 2
     return specs, c_in, size
@@ -128,19 +111,19 @@ def linear(x, weight, bias=None, *, slope=None, out=None):
     window of a wider matrix is passed as it is); weight [O, I], already folded; bias [O] or None; slope None = no activation.
     out: an [N, O] float32 tensor with dense rows to write into (a column window of a wider matrix: the concatenations of the
     networks are written in place), default a new tensor.  Returns out."""
-    x = _gpu_f32(x, "x", "[N, I] with I >= 1", lambda s: len(s) == 2 and s[1] >= 1)
+    x = gpu_f32(x, "x", "[N, I] with I >= 1", lambda s: len(s) == 2 and s[1] >= 1)
     N, I = x.shape
     dev = x.device
     if x.stride(1) != 1 or (N > 1 and x.stride(0) < I):
         x = x.contiguous()
-    weight = _operand(weight, "weight", f"[O, {I}]", lambda s: len(s) == 2 and s[0] >= 1 and s[1] == I, dev)
+    weight = operand(weight, "weight", f"[O, {I}]", lambda s: len(s) == 2 and s[0] >= 1 and s[1] == I, dev)
     O = weight.shape[0]
     if bias is not None:
-        bias = _operand(bias, "bias", f"[{O}]", lambda s: s == (O,), dev)
+        bias = operand(bias, "bias", f"[{O}]", lambda s: s == (O,), dev)
     if out is None:
         out = torch.empty(N, O, dtype=torch.float32, device=dev)
     else:
-        out = _gpu_f32(out, "out", f"[{N}, {O}]", lambda s: s == (N, O))
+        out = gpu_f32(out, "out", f"[{N}, {O}]", lambda s: s == (N, O))
         if out.device != dev or out.stride(1) != 1 or (N > 1 and out.stride(0) < O):
             raise A2PError(f"out must be on {dev} with dense rows (got {out.device}, strides {list(out.stride())})")
     if N == 0:
@@ -160,19 +143,19 @@ def conv2d_down3_ub(h, x, w2, b2, wr, br=None, *, slope: float = LRELU_SLOPE):
     x [N, C_in, Hs, Ws] (channel windows of contiguous tensors are passed as they are); w2 [C_out, C_in, 3, 3] (stride 2, padding
     1), b2 [C_out, H, W] untied, wr [C_out, C_in] (or [.., 1, 1]; stride 2), br [C_out] or None.  Returns [N, C_out, H, W] with H =
     (Hs - 1) // 2 + 1, W = (Ws - 1) // 2 + 1."""
-    h, hs = _source(h, "h")
+    h, hs = source(h, "h")
     N, C_in, Hs, Ws = h.shape
     dev = h.device
-    x, xs = _source(x, "x")
+    x, xs = source(x, "x")
     if tuple(x.shape) != tuple(h.shape) or x.device != dev:
         raise A2PError(f"x is {list(x.shape)} on {x.device}; h is {list(h.shape)} on {dev}: they must agree")
     H, W = (Hs - 1) // 2 + 1, (Ws - 1) // 2 + 1
-    w2 = _operand(w2, "w2", f"[C_out, {C_in}, 3, 3]", lambda s: len(s) == 4 and s[0] >= 1 and s[1:] == (C_in, 3, 3), dev)
+    w2 = operand(w2, "w2", f"[C_out, {C_in}, 3, 3]", lambda s: len(s) == 4 and s[0] >= 1 and s[1:] == (C_in, 3, 3), dev)
     C_out = w2.shape[0]
-    b2 = _operand(b2, "b2", f"[{C_out}, {H}, {W}]", lambda s: s == (C_out, H, W), dev)
-    wr = _operand(wr, "wr", f"[{C_out}, {C_in}] or [{C_out}, {C_in}, 1, 1]", lambda s: s in ((C_out, C_in), (C_out, C_in, 1, 1)), dev)
+    b2 = operand(b2, "b2", f"[{C_out}, {H}, {W}]", lambda s: s == (C_out, H, W), dev)
+    wr = operand(wr, "wr", f"[{C_out}, {C_in}] or [{C_out}, {C_in}, 1, 1]", lambda s: s in ((C_out, C_in), (C_out, C_in, 1, 1)), dev)
     if br is not None:
-        br = _operand(br, "br", f"[{C_out}]", lambda s: s == (C_out,), dev)
+        br = operand(br, "br", f"[{C_out}]", lambda s: s == (C_out,), dev)
     out = torch.empty(N, C_out, H, W, dtype=torch.float32, device=dev)
     d = _lib.A2PDown3Desc()
     d.h, d.x, d.w2, d.b2, d.wr, d.br, d.out = hs, xs, _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(wr), _lib.ptr(br), _lib.ptr(out)
@@ -195,11 +178,11 @@ def conv_down_block(x, t, name: str):
 def face_tex_cond(raw, bias, mask):
     """One launch of a2p_face_tex_cond: (resize(255 (raw + bias + 0.5)) / 255 - 0.5) * mask with F.interpolate's bilinear rule
     (align_corners=False) at the mask's size.  raw [N, C, Hs, Ws]; bias [C, Hs, Ws]; mask [H, W].  Returns [N, C, H, W]."""
-    raw = _gpu_f32(raw, "raw", "[N, C, Hs, Ws]", lambda s: len(s) == 4 and min(s[1:]) >= 1).contiguous()
+    raw = gpu_f32(raw, "raw", "[N, C, Hs, Ws]", lambda s: len(s) == 4 and min(s[1:]) >= 1).contiguous()
     N, C, Hs, Ws = raw.shape
     dev = raw.device
-    bias = _operand(bias, "bias", f"[{C}, {Hs}, {Ws}]", lambda s: s == (C, Hs, Ws), dev)
-    mask = _operand(mask, "mask", "[H, W]", lambda s: len(s) == 2 and min(s) >= 1, dev)
+    bias = operand(bias, "bias", f"[{C}, {Hs}, {Ws}]", lambda s: s == (C, Hs, Ws), dev)
+    mask = operand(mask, "mask", "[H, W]", lambda s: len(s) == 2 and min(s) >= 1, dev)
     H, W = mask.shape
     out = torch.empty(N, C, H, W, dtype=torch.float32, device=dev)
     if N == 0:
@@ -211,20 +194,7 @@ def face_tex_cond(raw, bias, mask):
 
 
 # ------------------------------------------------------------------------------------------------ the networks
-class _Net:
-    """Host arrays in `params` (folded float32 weights under the reference's key names); device copies on first use, per device."""
-
-    def _tables(self, device):
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in self.params.items()}
-        return self._dev[key]
-
-    def __init__(self):
-        raise TypeError(f"use {type(self).__name__}.from_state_dict")
-
-
-class FaceDecoder(_Net):
+class FaceDecoder(HostNet):
     """FaceDecoderFrontal of nn/face.py: face codes [N, n_latent] to face_geom [N, V_f, 3] and the raw face texture."""
 
     @classmethod
@@ -242,7 +212,7 @@ class FaceDecoder(_Net):
             raise ValueError(f"`geommod.0` has {n_vert_out} outputs; three per vertex are expected")
         self.V = n_vert_out // 3
         self.n_view = _first_dim(sd, "viewmod.0", 2)
-        view = _np(_asset(assets, "face_frontal_view")).astype(np.float32).reshape(-1)
+        view = as_numpy(asset(assets, "face_frontal_view")).astype(np.float32).reshape(-1)
         _linear_params(sd, "encmod.0", self.n_hidden, self.n_latent, p)
         _linear_params(sd, "geommod.0", n_vert_out, self.n_hidden, p)
         _linear_params(sd, "viewmod.0", self.n_view, view.size, p)
@@ -259,13 +229,13 @@ class FaceDecoder(_Net):
         for name in layers:
             c_out = _first_dim(sd, name, 4, 1)
             p[f"{name}.weight"] = folded_weight_transposed(sd, name, (c, c_out, 4, 4))
-            p[f"{name}.bias"] = _checked(sd, f"{name}.bias", (c_out, 2 * s, 2 * s))
+            p[f"{name}.bias"] = checked(sd, f"{name}.bias", (c_out, 2 * s, 2 * s))
             self.layers.append((name, c, c_out, s))
             c, s = c_out, 2 * s
         if s > _lib.CONV_MAX_SIZE:
             raise ValueError(f"the texture ladder ends at {s} x {s}; a side is at most {_lib.CONV_MAX_SIZE}")
         self.tex_channels, self.tex_size = c, s
-        p["bias"] = _checked(sd, "bias", (c, s, s))
+        p["bias"] = checked(sd, "bias", (c, s, s))
         p["frontal_view"] = view.reshape(1, -1)
         self.params, self._dev = p, {}
         return self
@@ -290,7 +260,7 @@ class FaceDecoder(_Net):
     def forward(self, face_codes, return_tex: bool = False) -> dict:
         """face_codes [N, n_latent] -> {"face_geom": [N, V_f, 3], "face_tex_raw": [N, C, S, S]} and, with return_tex, "face_tex" =
         255 (face_tex_raw + bias + 0.5) (torch arithmetic, in the reference's order)."""
-        x = _gpu_f32(face_codes, "face_codes", f"[N, {self.n_latent}]", lambda s: len(s) == 2 and s[1] == self.n_latent)
+        x = gpu_f32(face_codes, "face_codes", f"[N, {self.n_latent}]", lambda s: len(s) == 2 and s[1] == self.n_latent)
         N, dev = x.shape[0], x.device
         t = self._tables(dev)
         with _lib.on_device_of(x):
@@ -309,7 +279,7 @@ class FaceDecoder(_Net):
     __call__ = forward
 
 
-class FaceEncoder(_Net):
+class FaceEncoder(HostNet):
     """FaceEncoder of mesh_vae_drivable.py in eval mode: face geometry and texture to the face embedding in body space."""
 
     @classmethod
@@ -337,10 +307,10 @@ class FaceEncoder(_Net):
         _linear_params(sd, "jointmod.0", self.n_joint, self.n_tex_enc + self.n_geom_enc, p)
         _linear_params(sd, "mu", self.n_embs, self.n_joint, p)
         _linear_params(sd, "logvar", self.n_embs, self.n_joint, p)
-        mask = _np(_asset(assets, "mugsy_face_mask"))
+        mask = as_numpy(asset(assets, "mugsy_face_mask"))
         if mask.ndim != 3 or min(mask.shape) < 1:
             raise ValueError(f"assets `mugsy_face_mask` must be [H, W, C] (got {list(mask.shape)})")
-        p["tex_cond_mask"] = _f32(resize_mask64(mask[..., 0], self.uv_size, True))
+        p["tex_cond_mask"] = f32(resize_mask64(mask[..., 0], self.uv_size, True))
         self.params, self._dev = p, {}
         return self
 
@@ -352,11 +322,11 @@ class FaceEncoder(_Net):
     def forward(self, face_geom, face_tex_raw, bias) -> dict:
         """face_geom [N, V_f, 3] (or [N, 3 V_f]), face_tex_raw [N, C, S, S] and the decoder's bias [C, S, S] -> {"face_embs",
         "face_embs_mu", "face_embs_logvar"} [N, n_embs] (face_embs is a copy of mu: eval mode) and "face_tex_cond"."""
-        g = _gpu_f32(face_geom, "face_geom", f"[N, {self.n_vert_in // 3}, 3] or [N, {self.n_vert_in}]",
+        g = gpu_f32(face_geom, "face_geom", f"[N, {self.n_vert_in // 3}, 3] or [N, {self.n_vert_in}]",
                      lambda s: len(s) in (2, 3) and int(np.prod(s[1:])) == self.n_vert_in)
         N, dev = g.shape[0], g.device
         C = self.tex_channels
-        raw = _gpu_f32(face_tex_raw, "face_tex_raw", f"[{N}, {C}, S, S]", lambda s: len(s) == 4 and s[:2] == (N, C))
+        raw = gpu_f32(face_tex_raw, "face_tex_raw", f"[{N}, {C}, S, S]", lambda s: len(s) == 4 and s[:2] == (N, C))
         if raw.device != dev:
             raise A2PError(f"face_tex_raw is on {raw.device}, face_geom on {dev}")
         t = self._tables(dev)
@@ -377,7 +347,7 @@ class FaceEncoder(_Net):
     __call__ = forward
 
 
-class BodyEncoder(_Net):
+class BodyEncoder(HostNet):
     """Encoder of mesh_vae_drivable.py in eval mode: the unposed vertex displacement to the body embedding."""
 
     @classmethod
@@ -398,8 +368,8 @@ class BodyEncoder(_Net):
         self.n_embs = _first_dim(sd, "mu", 2)
         _linear_params(sd, "mu", self.n_embs, self.n_flat, p)
         _linear_params(sd, "logvar", self.n_embs, self.n_flat, p)
-        face_mask = _np(_asset(assets, "face_mask")).astype(np.float64)
-        p["mask"] = _f32(resize_mask64(1.0 - face_mask, self.uv_size, False) != 0)
+        face_mask = as_numpy(asset(assets, "face_mask")).astype(np.float64)
+        p["mask"] = f32(resize_mask64(1.0 - face_mask, self.uv_size, False) != 0)
         self.params, self._dev = p, {}
         return self
 
@@ -410,7 +380,7 @@ class BodyEncoder(_Net):
 
     def forward(self, verts_unposed) -> dict:
         """verts_unposed [N, V, 3] -> {"embs", "embs_mu", "embs_logvar"} [N, n_embs] (embs is a copy of mu: eval mode)."""
-        v = _gpu_f32(verts_unposed, "verts_unposed", f"[N, {self.surface.V}, 3]", lambda s: len(s) == 3 and s[1:] == (self.surface.V, 3))
+        v = gpu_f32(verts_unposed, "verts_unposed", f"[N, {self.surface.V}, 3]", lambda s: len(s) == 3 and s[1:] == (self.surface.V, 3))
         N = v.shape[0]
         t = self._tables(v.device)
         with _lib.on_device_of(v):
@@ -433,30 +403,18 @@ def activation_bytes_per_frame(face_decoder: FaceDecoder, face_encoder: FaceEnco
     return 4 * n
 
 
-def _inputs(name, skeleton, face_decoder, face_encoder, body_encoder, poses, face_codes):
+def clip_inputs(name, skeleton, face_decoder, face_encoder, body_encoder, poses, face_codes):
     """(frames [N, P] and codes [N, n_latent] on the GPU, the leading axes) of a clip, after the checks the entry points share."""
-    from .skinning import motion_frames
     if skeleton.V != body_encoder.surface.V:
         raise A2PError(f"the skeleton skins V={skeleton.V} vertices; the encoder's surface has V={body_encoder.surface.V}")
     if 3 * face_decoder.V != face_encoder.n_vert_in or face_decoder.tex_channels != face_encoder.tex_channels:
         raise A2PError(f"the face decoder gives {face_decoder.V} vertices and {face_decoder.tex_channels} texture channels; the face "
                        f"encoder takes {face_encoder.n_vert_in // 3} and {face_encoder.tex_channels}")
-    frames, lead = motion_frames(poses, skeleton.P_pos)
-    if not torch.is_tensor(frames):
-        frames = torch.from_numpy(frames)
-    if not frames.is_cuda:
-        if not torch.cuda.is_available():
-            raise A2PError(f"{name} runs on the MI355X; there is no CPU implementation")
-        frames = frames.to("cuda")
-    frames = frames.to(torch.float32)
-    codes = torch.as_tensor(face_codes)
-    if tuple(codes.shape) != (*lead, face_decoder.n_latent):
-        raise A2PError(f"face_codes must be {[*lead, face_decoder.n_latent]} (got {list(codes.shape)})")
-    codes = codes.to(device=frames.device, dtype=torch.float32).reshape(frames.shape[0], face_decoder.n_latent).contiguous()
-    return frames, codes, lead
+    frames, lead = avatar.clip_frames(name, poses, skeleton.P_pos)
+    return frames, avatar.per_frame(face_codes, "face_codes", lead, (face_decoder.n_latent,), frames.device), lead
 
 
-def _encode_chunk(face_decoder, face_encoder, body_encoder, skeleton, frames, codes, geom, rest_embs):
+def encode_chunk(face_decoder, face_encoder, body_encoder, skeleton, frames, codes, geom, rest_embs):
     """(embs, face_embs) of one chunk of frames: AutoEncoder.encode.  rest_embs [1, n_embs] replaces the body branch."""
     face = face_decoder.forward(codes)
     face_embs = face_encoder.forward(face["face_geom"], face["face_tex_raw"], face_decoder.bias(frames.device))["face_embs"]
@@ -466,7 +424,7 @@ def _encode_chunk(face_decoder, face_encoder, body_encoder, skeleton, frames, co
     return body_encoder.forward(skeleton.unpose_vertices(frames, g))["embs"], face_embs
 
 
-def _rest_embs(body_encoder, skeleton, device):
+def rest_embs(body_encoder, skeleton, device):
     return body_encoder.forward(torch.zeros(1, skeleton.V, 3, dtype=torch.float32, device=device))["embs"]
 
 
@@ -479,24 +437,18 @@ def encode_motion(face_decoder: FaceDecoder, face_encoder: FaceEncoder, body_enc
     displacement once and broadcasts it (only with geom=None; see the module docstring).  Runs in chunks of frames whose
     activations (activation_bytes_per_frame) stay under max_bytes, at least one frame; a frame's result does not depend on the
     chunking."""
-    if body_embs not in ("per_frame", "rest"):
-        raise A2PError(f"body_embs={body_embs!r}: need 'per_frame' or 'rest'")
+    avatar.check_body_embs(body_embs)
     if body_embs == "rest" and geom is not None:
         raise A2PError("body_embs='rest' encodes the template: it takes no geom")
-    frames, codes, lead = _inputs("encode_motion", skeleton, face_decoder, face_encoder, body_encoder, poses, face_codes)
+    frames, codes, lead = clip_inputs("encode_motion", skeleton, face_decoder, face_encoder, body_encoder, poses, face_codes)
     N, dev, V = frames.shape[0], frames.device, skeleton.V
     if geom is not None:
-        geom = torch.as_tensor(geom)
-        if tuple(geom.shape) != (*lead, V, 3):
-            raise A2PError(f"geom must be {[*lead, V, 3]} (got {list(geom.shape)})")
-        geom = geom.to(device=dev, dtype=torch.float32).reshape(N, V, 3).contiguous()
+        geom = avatar.per_frame(geom, "geom", lead, (V, 3), dev)
     out = {"embs": torch.empty(N, body_encoder.n_embs, dtype=torch.float32, device=dev),
            "face_embs": torch.empty(N, face_encoder.n_embs, dtype=torch.float32, device=dev)}
-    rest = _rest_embs(body_encoder, skeleton, dev) if body_embs == "rest" and N else None
-    chunk = max(1, int(max_bytes) // activation_bytes_per_frame(face_decoder, face_encoder, body_encoder, skeleton))
-    for a in range(0, N, chunk):
-        b = min(N, a + chunk)
-        out["embs"][a:b], out["face_embs"][a:b] = _encode_chunk(face_decoder, face_encoder, body_encoder, skeleton, frames[a:b], codes[a:b],
+    rest = rest_embs(body_encoder, skeleton, dev) if body_embs == "rest" and N else None
+    for a, b in avatar.frame_chunks(N, max_bytes, activation_bytes_per_frame(face_decoder, face_encoder, body_encoder, skeleton)):
+        out["embs"][a:b], out["face_embs"][a:b] = encode_chunk(face_decoder, face_encoder, body_encoder, skeleton, frames[a:b], codes[a:b],
                                                                 None if geom is None else geom[a:b], rest)
     return {k: v.reshape(*lead, v.shape[1]) for k, v in out.items()}
 
@@ -513,49 +465,33 @@ def render_codes_motion(face_decoder: FaceDecoder, face_encoder: FaceEncoder, bo
     the chunking.  supersample and background as in texture.render_rgb_motion: s x s samples per pixel, and one display-space
     colour or [H, W, 3] / [3, H, W] panel in [0, 255] behind the avatar, the same for every camera; a pixel no sample covers holds
     the background's bytes exactly."""
-    from .render import camera_centre
     from .texture import display_background, display_frames
     supersample = rasterizer._supersample(supersample)
     background = display_background(background, rasterizer.height, rasterizer.width)
-    if body_embs not in ("per_frame", "rest"):
-        raise A2PError(f"body_embs={body_embs!r}: need 'per_frame' or 'rest'")
-    if skeleton.P_pos != 6 + decoder.n_pose_dims:
-        raise A2PError(f"the skeleton takes {skeleton.P_pos} pose parameters; the decoder 6 + n_pose_dims = {6 + decoder.n_pose_dims}")
-    if (body_encoder.n_embs, face_encoder.n_embs) != (decoder.n_embs, decoder.n_face_embs):
-        raise A2PError(f"the encoders give {body_encoder.n_embs} / {face_encoder.n_embs} embedding values; the decoder takes "
-                       f"{decoder.n_embs} / {decoder.n_face_embs}")
-    frames, codes, lead = _inputs("render_codes_motion", skeleton, face_decoder, face_encoder, body_encoder, poses, face_codes)
+    avatar.check_body_embs(body_embs)
+    avatar.check_pose_width(skeleton, decoder)
+    avatar.check_embedding_widths(body_encoder, face_encoder, decoder)
+    frames, codes, lead = clip_inputs("render_codes_motion", skeleton, face_decoder, face_encoder, body_encoder, poses, face_codes)
     N, dev = frames.shape[0], frames.device
-    K = torch.as_tensor(K).to(device=dev, dtype=torch.float32)
-    Rt = torch.as_tensor(Rt).to(device=dev, dtype=torch.float32)
-    if K.dim() != 3 or K.shape[1:] != (3, 3) or Rt.dim() != 3 or Rt.shape[1:] != (3, 4) or K.shape[0] != Rt.shape[0] or K.shape[0] < 1:
-        raise A2PError(f"K must be [C, 3, 3] and Rt [C, 3, 4] with C >= 1 cameras (got {list(K.shape)} and {list(Rt.shape)})")
-    C = K.shape[0]
-    camera_pos = camera_centre(Rt) if camera_pos is None else torch.as_tensor(camera_pos).to(device=dev, dtype=torch.float32)
-    if tuple(camera_pos.shape) != (C, 3):
-        raise A2PError(f"camera_pos must be [{C}, 3] (got {list(camera_pos.shape)})")
-    per_frame = activation_bytes_per_frame(face_decoder, face_encoder, body_encoder, skeleton)
-    chunk = max(1, int(max_bytes) // (per_frame + decoder.activation_bytes_per_frame() + texture.activation_bytes_per_frame()))
+    K, Rt, camera_pos, C = avatar.cameras(K, Rt, camera_pos, dev)
+    per_frame = (activation_bytes_per_frame(face_decoder, face_encoder, body_encoder, skeleton) + decoder.activation_bytes_per_frame()
+                 + texture.activation_bytes_per_frame())
     H, W = rasterizer.height, rasterizer.width
     background = tuple(None if x is None else x.to(dev) for x in background)
     out = torch.empty(N, H, C * W, 3, dtype=torch.uint8, device=dev)
-    rest = _rest_embs(body_encoder, skeleton, dev) if body_embs == "rest" and N else None
-    for a in range(0, N, chunk):
-        b = min(N, a + chunk)
-        embs, face_embs = _encode_chunk(face_decoder, face_encoder, body_encoder, skeleton, frames[a:b], codes[a:b], None, rest)
-        preds = decoder.forward(frames[a:b], embs.contiguous(), face_embs)
-        verts = skeleton.pose_vertices(frames[a:b], verts_unposed=preds["geom_delta_rec"])
+    rest = rest_embs(body_encoder, skeleton, dev) if body_embs == "rest" and N else None
+    for a, b in avatar.frame_chunks(N, max_bytes, per_frame):
+        embs, face_embs = encode_chunk(face_decoder, face_encoder, body_encoder, skeleton, frames[a:b], codes[a:b], None, rest)
+        preds, verts = avatar.decode_and_pose(decoder, skeleton, frames[a:b], embs.contiguous(), face_embs)
         for c in range(C):
             tex = texture.forward(verts, preds["tex_mean_rec"], camera_pos[c:c + 1], motion=frames[a:b] if texture.pose_shadow is not None else None)
             image = display_frames(rasterizer, verts, tex["tex_rec"], K[c:c + 1], Rt[c:c + 1], supersample, background)
-            out[a:b, :, c * W:(c + 1) * W] = image.permute(0, 2, 3, 1).clip(0, 255).to(torch.uint8)
+            out[a:b, :, c * W:(c + 1) * W] = avatar.uint8_panel(image)
     return out.reshape(*lead, H, C * W, 3)
 
 
-def main(argv=None) -> int:
+def parser():
     import argparse
-    import json
-    from . import render as R
     ap = argparse.ArgumentParser(
         prog="python -m audio2photoreal_amd.encoder",
         description="Video frames of sampler output: face codes and body poses to uint8 images, one panel per camera.")
@@ -565,71 +501,31 @@ def main(argv=None) -> int:
                     "mugsy_face_mask, face_mask")
     ap.add_argument("--checkpoint", required=True, help="the body model's state dict (encoder.*, encoder_face.*, decoder_face.*, decoder.*, ...)")
     ap.add_argument("--out", required=True, help="frames.npy: a uint8 array [R, T, H, C W, 3]")
-    cam = ap.add_mutually_exclusive_group()
+    cam = avatar.add_camera_arguments(ap, per="camera")
     cam.add_argument("--defaults", metavar="FILE", help="render_defaults_*.pth of the reference's demo: a dict whose `K` [C, 3, 3], `Rt` [C, 3, 4] and "
                      "(optional) `campos` [C, 3] are read as the cameras.  The file is not part of the reference's tree: that it holds these keys "
                      "in these shapes is an assumption")
-    cam.add_argument("--camera-json", metavar="FILE", help='{"K": 3 x 3, "Rt": 3 x 4} (OpenCV), or lists of them, one per camera')
-    cam.add_argument("--eye", type=float, nargs=3, metavar=("X", "Y", "Z"),
-                     help="camera position; default: in front of the first frame's bounding box along +z, far enough to see all of it")
-    ap.add_argument("--target", type=float, nargs=3, metavar=("X", "Y", "Z"), help="point looked at; default: the bounding box centre")
-    ap.add_argument("--up", type=float, nargs=3, default=(0.0, 1.0, 0.0), metavar=("X", "Y", "Z"), help="world direction shown upwards")
-    ap.add_argument("--fov", type=float, default=40.0, help="vertical field of view in degrees")
-    ap.add_argument("--size", type=int, nargs=2, default=(256, 256), metavar=("H", "W"), help="height and width of one camera's panel")
-    ap.add_argument("--frames", default=None, metavar="A:B", help="frames A..B-1 of the time axis only")
-    ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write frame_<sequence>_<frame>.png per frame")
-    ap.add_argument("--video", default=None, metavar="FILE", help="also write a Motion-JPEG AVI file, encoded on the GPU (video.py); R > 1 "
-                    "sequences go to <stem>_<r>.avi")
-    ap.add_argument("--audio", default=None, metavar="FILE", help="with --video: the recording's wav file, written as 16-bit PCM beside the frames")
-    ap.add_argument("--fps", type=float, default=30.0, help="with --video: frames per second")
-    ap.add_argument("--body-embs", choices=("per_frame", "rest"), default="per_frame", help="rest: encode the template once (not the reference's loop)")
-    ap.add_argument("--max-bytes", type=int, default=1 << 30, help="activation budget of one chunk of frames")
-    ap.add_argument("--supersample", type=int, default=1, metavar="S", choices=range(1, 5), help="anti-aliasing: S x S samples per pixel")
-    ap.add_argument("--background", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
-                    help="display colour in [0, 255] behind the avatar, in every panel (default: black)")
-    ap.add_argument("--uv-size", type=int, default=1024)
-    ap.add_argument("--encoder-uv-size", type=int, default=512)
-    ap.add_argument("--n-init-ftrs", type=int, default=8)
-    ap.add_argument("--upscale-n-ftrs", type=int, default=8)
-    ap.add_argument("--pose-to-shadow-dims", type=int, default=104)
-    for name, default in (("n-pose-enc-channels", 16), ("n-embs", 1024), ("n-embs-enc-channels", 32), ("n-face-embs", 256),
-                          ("n-init-channels", 64), ("n-min-channels", 4)):     # the decoder's configuration, as in decoder.main
-        ap.add_argument(f"--{name}", type=int, default=default)
-    args = ap.parse_args(argv)
+    avatar.add_render_arguments(ap, png="frame")
+    avatar.add_video_arguments(ap)
+    avatar.add_network_arguments(ap, encoders=True)
+    return ap
+
+
+def main(argv=None) -> int:
+    from . import render as R
+    from . import video
+    args = parser().parse_args(argv)
     if args.defaults is not None and args.target is not None:
         raise A2PError("--target goes with --eye, not with --defaults")
     if args.audio is not None and args.video is None:
         raise A2PError("--audio goes with --video")
-    from .decoder import BodyDecoder
-    from .skinning import BodySkeleton
-    from .surface import BodySurface
-    from .texture import BodyTexture
-    block = np.load(args.results, allow_pickle=True).item()
-    for key in ("pose", "face"):
-        if key not in block:
-            raise A2PError(f"{args.results} holds no `{key}` (keys: {sorted(block)})")
-    pose, face = np.asarray(block["pose"], np.float32), np.asarray(block["face"], np.float32)
+    pose, face = avatar.load_codes_clip(args.results)
     if pose.ndim != 3 or face.ndim != 3 or pose.shape[:2] != face.shape[:2]:
         raise A2PError(f"`pose` must be [R, T, P] and `face` [R, T, F] with the same R and T (got {list(pose.shape)} and {list(face.shape)})")
-    if args.frames is not None:
-        a, _, b = args.frames.partition(":")
-        window = slice(int(a) if a else None, int(b) if b else None)
-        pose, face = pose[:, window], face[:, window]
-    if not torch.cuda.is_available():
-        raise A2PError("the frames are rendered on the MI355X; there is no CPU implementation")
-    assets = torch.load(args.assets, map_location="cpu", weights_only=False)
-    state = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
-    surface = BodySurface.from_static_assets(assets, uv_size=args.uv_size)
-    decoder = BodyDecoder.from_state_dict(
-        state, assets, surface, uv_size=args.uv_size, n_pose_dims=args.pose_to_shadow_dims - 6, n_pose_enc_channels=args.n_pose_enc_channels,
-        n_embs=args.n_embs, n_embs_enc_channels=args.n_embs_enc_channels, n_face_embs=args.n_face_embs, n_init_channels=args.n_init_channels,
-        n_min_channels=args.n_min_channels)
-    texture = BodyTexture.from_state_dict(state, assets, surface, uv_size=args.uv_size, n_init_ftrs=args.n_init_ftrs,
-                                          upscale_n_ftrs=args.upscale_n_ftrs, pose_to_shadow_dims=args.pose_to_shadow_dims)
-    skeleton = BodySkeleton.from_static_assets(assets)
-    face_decoder = FaceDecoder.from_state_dict(state, assets)
-    face_encoder = FaceEncoder.from_state_dict(state, assets, uv_size=args.encoder_uv_size)
-    body_encoder = BodyEncoder.from_state_dict(state, assets, surface, uv_size=args.encoder_uv_size)
+    window = avatar.frame_window(args.frames)
+    pose, face = pose[:, window], face[:, window]
+    avatar.require_gpu("the frames are rendered")
+    person = avatar.load_avatar(args.assets, args.checkpoint, args)
     H, W = args.size
     poses = torch.from_numpy(pose).to("cuda")
     camera_pos = None
@@ -641,29 +537,21 @@ def main(argv=None) -> int:
         K, Rt = torch.as_tensor(d["K"]).float().reshape(-1, 3, 3), torch.as_tensor(d["Rt"]).float()[..., :3, :4].reshape(-1, 3, 4)
         camera_pos = torch.as_tensor(d["campos"]).float().reshape(-1, 3) if "campos" in d else None
     else:
-        rest = skeleton.pose_vertices(poses.reshape(-1, poses.shape[-1])[:1]).cpu().numpy()  # frames the default camera
+        rest = person.skeleton.pose_vertices(poses.reshape(-1, poses.shape[-1])[:1]).cpu().numpy()  # frames the default camera
         K, Rt = R._camera_from_args(args, rest, H, W)
-    on_gpu = render_codes_motion(face_decoder, face_encoder, body_encoder, decoder, texture, skeleton, R.BodyRasterizer(surface, H, W), poses,
-                                 face, K, Rt, camera_pos, body_embs=args.body_embs, max_bytes=args.max_bytes, supersample=args.supersample,
-                                 background=args.background)
+    on_gpu = render_codes_motion(*person[:6], R.BodyRasterizer(person.surface, H, W), poses, face, K, Rt, camera_pos, body_embs=args.body_embs,
+                                 max_bytes=args.max_bytes, supersample=args.supersample, background=args.background)
     frames = on_gpu.cpu().numpy()
     np.save(args.out, frames)
     print(f"{args.out}: frames {list(frames.shape)} uint8")
     if args.video is not None:
-        from . import video
-        audio, rate = video.wav_audio(args.audio) if args.audio is not None else (None, None)
+        audio, rate = avatar.video_audio(args)
         for r in range(on_gpu.shape[0]):
             path = video.sequence_path(args.video, r, on_gpu.shape[0])
             video.write_video(path, on_gpu[r], fps=args.fps, audio=audio, audio_rate=rate)
             print(f"{path}: {on_gpu.shape[1]} frames at {args.fps:g} fps")
     if args.png_dir is not None:
-        import os
-        from PIL import Image
-        os.makedirs(args.png_dir, exist_ok=True)
-        for r in range(frames.shape[0]):
-            for t in range(frames.shape[1]):
-                Image.fromarray(np.ascontiguousarray(frames[r, t]), "RGB").save(os.path.join(args.png_dir, f"frame_{r:02d}_{t:05d}.png"))
-        print(f"{args.png_dir}: {frames.shape[0] * frames.shape[1]} png files")
+        print(f"{args.png_dir}: {R.write_pngs({'frame': frames.transpose(0, 1, 4, 2, 3)}, args.png_dir)} png files")
     return 0
 
 

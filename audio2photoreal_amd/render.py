@@ -21,9 +21,9 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, avatar
 from ._lib import A2PError
-from .surface import BodySurface, _index_array
+from .surface import BodySurface, index_array
 
 OUTPUTS = {"depth": 1, "normals": 3, "view_cos": 1, "positions": 3, "mask": 1}     # render_motion's images and their channels
 
@@ -54,7 +54,7 @@ def look_at(eye, target, up, height: int, width: int, fov_degrees: float, device
     return torch.from_numpy(K.astype(np.float32)).to(device or "cpu"), torch.from_numpy(Rt.astype(np.float32)).to(device or "cpu")
 
 
-class _RenderArguments:
+class RenderArguments:
     """The argument checks and the chunking that BodyRasterizer and scene.SceneRasterizer share; both have a height and a width."""
 
     _tensor = staticmethod(BodySurface._tensor)
@@ -118,7 +118,7 @@ class _RenderArguments:
             yield a, min(N, a + step), proj, key
 
 
-class BodyRasterizer(_RenderArguments):
+class BodyRasterizer(RenderArguments):
     """A triangle mesh with a UV layout and an image size, ready to rasterise.  `surface_or_arrays` is a BodySurface or a tuple
     (vi [F, 3], vt [T, 2], vti [F, 3]) or (vi, vt, vti, n_verts).  flip_uv samples textures at v <- 1 - v (the meaning it has in BodySurface); a face with
     a corner nearer than `near` along the camera's z axis is dropped whole."""
@@ -156,8 +156,8 @@ class BodyRasterizer(_RenderArguments):
         V = int(n_verts) if n_verts is not None else int(raw_vi.max(initial=-1)) + 1
         if V < 1:
             raise ValueError(f"the mesh has V={V} vertices; need at least 1")
-        self._vi = _index_array("vi", raw_vi, 3, V, "V")
-        self._vti = _index_array("vti", vti, 3, self._vt.shape[0], "T")
+        self._vi = index_array("vi", raw_vi, 3, V, "V")
+        self._vti = index_array("vti", vti, 3, self._vt.shape[0], "T")
         if self._vi.shape[0] < 1 or self._vti.shape[0] != self._vi.shape[0]:
             raise ValueError(f"vi holds F={self._vi.shape[0]} faces and vti {self._vti.shape[0]}; need the same F >= 1")
         self.V, self.F, self.T = V, self._vi.shape[0], self._vt.shape[0]
@@ -421,20 +421,10 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--geometry", required=True, help="geometry.npy of audio2photoreal_amd.skinning (key `vertices` [B, T, V, 3])")
     ap.add_argument("--assets", required=True, help="static_assets.pt: topology with vi, vt, vti, v2uv")
     ap.add_argument("--out", required=True, help="frames.npy: a pickled dict of float32 arrays [B, T, C, H, W]")
-    ap.add_argument("--size", type=int, nargs=2, default=(256, 256), metavar=("H", "W"), help="image height and width")
-    cam = ap.add_mutually_exclusive_group()
-    cam.add_argument("--camera-json", metavar="FILE", help='{"K": 3 x 3, "Rt": 3 x 4} (OpenCV), or lists of them, one per frame')
-    cam.add_argument("--eye", type=float, nargs=3, metavar=("X", "Y", "Z"),
-                     help="camera position; default: in front of the vertices' bounding box along +z, far enough to see all of it")
-    ap.add_argument("--target", type=float, nargs=3, metavar=("X", "Y", "Z"), help="point looked at; default: the bounding box centre")
-    ap.add_argument("--up", type=float, nargs=3, default=(0.0, 1.0, 0.0), metavar=("X", "Y", "Z"), help="world direction shown upwards")
-    ap.add_argument("--fov", type=float, default=40.0, help="vertical field of view in degrees")
-    ap.add_argument("--outputs", nargs="+", default=["depth", "normals", "view_cos", "mask"], choices=sorted(OUTPUTS))
-    ap.add_argument("--frames", default=None, metavar="A:B", help="frames A..B-1 of the time axis only")
-    ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write <output>_<sequence>_<frame>.png per frame")
-    ap.add_argument("--max-bytes", type=int, default=1 << 30, help="byte budget of one chunk of frames")
-    ap.add_argument("--supersample", type=int, default=1, metavar="S", choices=range(1, _lib.RENDER_MAX_SUPERSAMPLE + 1),
-                    help="anti-aliasing: S x S samples per pixel; the mask is then the coverage and the other images are premultiplied by it")
+    ap.add_argument("--outputs", nargs="+", default=["depth", "normals", "view_cos", "mask"], choices=sorted(OUTPUTS),
+                    help="with --supersample above 1 the mask is the coverage and the other images are premultiplied by it")
+    avatar.add_camera_arguments(ap, eye_help="in front of the vertices' bounding box along +z, far enough to see all of it")
+    avatar.add_render_arguments(ap, png="<output>", background=False)
     return ap
 
 
@@ -492,16 +482,8 @@ def write_pngs(images: dict, directory: str, first: int = 0) -> int:
 def main(argv=None) -> int:
     args = parser().parse_args(argv)
     H, W = args.size
-    block = np.load(args.geometry, allow_pickle=True).item()
-    if "vertices" not in block:
-        raise A2PError(f"{args.geometry} holds no `vertices` (keys: {sorted(block)}); run the skinning command without --joints-only")
-    verts = np.asarray(block["vertices"], np.float32)
-    if args.frames is not None:
-        a, _, b = args.frames.partition(":")
-        window = slice(int(a) if a else None, int(b) if b else None)
-        verts = verts[:, window] if verts.ndim == 4 else verts[window]
-    if not torch.cuda.is_available():
-        raise A2PError("the images are rendered on the MI355X; there is no CPU implementation")
+    verts = avatar.load_vertices(args.geometry, args.frames)
+    avatar.require_gpu("the images are rendered")
     surface = BodySurface.from_static_assets(torch.load(args.assets, map_location="cpu", weights_only=False))
     rasterizer = BodyRasterizer(surface, H, W)
     K, Rt = _camera_from_args(args, verts, H, W)

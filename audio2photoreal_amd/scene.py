@@ -15,14 +15,14 @@ from __future__ import annotations
 import argparse
 import copy
 import sys
-from typing import NamedTuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, avatar
 from ._lib import A2PError
-from .render import BodyRasterizer, _RenderArguments, camera_centre
+from .avatar import Avatar, load_avatar  # noqa: F401  (this module's names for them)
+from .render import BodyRasterizer, RenderArguments
 from .surface import BodySurface
 
 MAX_BODIES = _lib.SCENE_MAX_BODIES
@@ -94,7 +94,7 @@ def _as_rasterizer(body, p: int, height: int, width: int, near: float) -> BodyRa
     return BodyRasterizer(body if isinstance(body, BodySurface) else tuple(body), height, width, bool(flip), near)
 
 
-class SceneRasterizer(_RenderArguments):
+class SceneRasterizer(RenderArguments):
     """1 to 4 triangle meshes with UV layouts and one image size, ready to rasterise together.  Each entry of `bodies` is a
     BodySurface (whose validated topology tables are shared, not copied), a BodyRasterizer (its tables and flip_uv) or a tuple (vi
     [F, 3], vt [T, 2], vti [F, 3][, n_verts]); `(entry, flip_uv)` or {"body": entry, "flip_uv": bool} sets the body's flip.  The
@@ -191,17 +191,6 @@ class SceneRasterizer(_RenderArguments):
         return out
 
 # ------------------------------------------------------------------------------------------------ people
-class Avatar(NamedTuple):
-    """One person's networks and mesh, as encoder.render_codes_motion takes them; `surface` is the BodySurface the scene rasterises."""
-    face_decoder: object
-    face_encoder: object
-    body_encoder: object
-    decoder: object
-    texture: object
-    skeleton: object
-    surface: object
-
-
 def conversation_inputs(result, repetition: int = 0):
     """(poses, face_codes, audio) of sample.conversation.generate_conversation's return value for the two functions below: per
     person the repetition's `pose` [T, .] and `face` [T, .], and audio float64 [samples, 2], channel p person p's own microphone as
@@ -262,8 +251,7 @@ def render_conversation_motion(avatars, poses, face_codes, placements, K, Rt, he
     from .texture import display_background, linear_to_display
     P = _people(avatars, poses, face_codes, placements)
     H, W = int(height), int(width)
-    if body_embs not in ("per_frame", "rest"):
-        raise A2PError(f"body_embs={body_embs!r}: need 'per_frame' or 'rest'")
+    avatar.check_body_embs(body_embs)
     leads = [tuple(torch.as_tensor(x).shape[:-1]) for x in face_codes]           # each person's poses are held against these below
     if len(set(leads)) != 1:
         raise A2PError(f"the people of a conversation share their frames: face_codes have leading axes {[list(ld) for ld in leads]}")
@@ -273,15 +261,11 @@ def render_conversation_motion(avatars, poses, face_codes, placements, K, Rt, he
     s = scene._supersample(supersample)
     frames, codes, lead = [], [], None
     for p, a in enumerate(avatars):
-        if a.skeleton.P_pos != 6 + a.decoder.n_pose_dims:
-            raise A2PError(f"avatars[{p}]: the skeleton takes {a.skeleton.P_pos} pose parameters; the decoder 6 + n_pose_dims = "
-                           f"{6 + a.decoder.n_pose_dims}")
-        if (a.body_encoder.n_embs, a.face_encoder.n_embs) != (a.decoder.n_embs, a.decoder.n_face_embs):
-            raise A2PError(f"avatars[{p}]: the encoders give {a.body_encoder.n_embs} / {a.face_encoder.n_embs} embedding values; the decoder "
-                           f"takes {a.decoder.n_embs} / {a.decoder.n_face_embs}")
+        avatar.check_pose_width(a.skeleton, a.decoder, f"avatars[{p}]: ")
+        avatar.check_embedding_widths(a.body_encoder, a.face_encoder, a.decoder, f"avatars[{p}]: ")
         if a.surface.V != a.skeleton.V:
             raise A2PError(f"avatars[{p}]: the skeleton skins V={a.skeleton.V} vertices; the surface has V={a.surface.V}")
-        f, c, ld = E._inputs("render_conversation_motion", a.skeleton, a.face_decoder, a.face_encoder, a.body_encoder, poses[p], face_codes[p])
+        f, c, ld = E.clip_inputs("render_conversation_motion", a.skeleton, a.face_decoder, a.face_encoder, a.body_encoder, poses[p], face_codes[p])
         if lead is not None and tuple(ld) != tuple(lead):
             raise A2PError(f"the people of a conversation share their frames: person 0 has {list(lead)}, person {p} {list(ld)}")
         lead = ld
@@ -290,30 +274,20 @@ def render_conversation_motion(avatars, poses, face_codes, placements, K, Rt, he
     for p, m in enumerate(host_place):
         if m is not None and m.ndim == 3 and m.shape[0] not in (1, N):
             raise A2PError(f"placements[{p}] must be [3, 4] or [{N} or 1, 3, 4] (got {list(m.shape)})")
-    K = torch.as_tensor(K).to(device=dev, dtype=torch.float32)
-    Rt = torch.as_tensor(Rt).to(device=dev, dtype=torch.float32)
-    if K.dim() != 3 or K.shape[1:] != (3, 3) or Rt.dim() != 3 or Rt.shape[1:] != (3, 4) or K.shape[0] != Rt.shape[0] or K.shape[0] < 1:
-        raise A2PError(f"K must be [C, 3, 3] and Rt [C, 3, 4] with C >= 1 cameras (got {list(K.shape)} and {list(Rt.shape)})")
-    C = K.shape[0]
-    camera_pos = camera_centre(Rt) if camera_pos is None else torch.as_tensor(camera_pos).to(device=dev, dtype=torch.float32)
-    if tuple(camera_pos.shape) != (C, 3):
-        raise A2PError(f"camera_pos must be [{C}, 3] (got {list(camera_pos.shape)})")
+    K, Rt, camera_pos, C = avatar.cameras(K, Rt, camera_pos, dev)
     place = [None if m is None else torch.from_numpy(np.ascontiguousarray(m.reshape(-1, 3, 4), np.float32)).to(dev) for m in host_place]
     per_frame = sum(E.activation_bytes_per_frame(a.face_decoder, a.face_encoder, a.body_encoder, a.skeleton)
                     + a.decoder.activation_bytes_per_frame() + a.texture.activation_bytes_per_frame() for a in avatars)
-    chunk = max(1, int(max_bytes) // per_frame)
     shown, linear = (None if x is None else x.to(dev) for x in (shown, linear))
     out = torch.empty(N, H, C * W, 3, dtype=torch.uint8, device=dev)
-    rest = [E._rest_embs(a.body_encoder, a.skeleton, dev) if body_embs == "rest" and N else None for a in avatars]
-    for lo in range(0, N, chunk):
-        hi = min(N, lo + chunk)
+    rest = [E.rest_embs(a.body_encoder, a.skeleton, dev) if body_embs == "rest" and N else None for a in avatars]
+    for lo, hi in avatar.frame_chunks(N, max_bytes, per_frame):
         verts, preds, here = [], [], []
         for p, a in enumerate(avatars):
-            embs, face_embs = E._encode_chunk(a.face_decoder, a.face_encoder, a.body_encoder, a.skeleton, frames[p][lo:hi], codes[p][lo:hi],
+            embs, face_embs = E.encode_chunk(a.face_decoder, a.face_encoder, a.body_encoder, a.skeleton, frames[p][lo:hi], codes[p][lo:hi],
                                               None, rest[p])
-            pr = a.decoder.forward(frames[p][lo:hi], embs.contiguous(), face_embs)
-            verts.append(a.skeleton.pose_vertices(frames[p][lo:hi], verts_unposed=pr["geom_delta_rec"]))
-            preds.append(pr)
+            pr, posed = avatar.decode_and_pose(a.decoder, a.skeleton, frames[p][lo:hi], embs.contiguous(), face_embs)
+            verts.append(posed), preds.append(pr)
             here.append(None if place[p] is None else (place[p][lo:hi] if place[p].shape[0] == N and N != 1 else place[p][0]))
         for c in range(C):
             tex = []
@@ -325,7 +299,7 @@ def render_conversation_motion(avatars, poses, face_codes, placements, K, Rt, he
             image = linear_to_display(got["render"])
             if shown is not None:
                 image = torch.where(got["alpha"] == 0, shown, image)
-            out[lo:hi, :, c * W:(c + 1) * W] = image.permute(0, 2, 3, 1).clip(0, 255).to(torch.uint8)
+            out[lo:hi, :, c * W:(c + 1) * W] = avatar.uint8_panel(image)
     return out.reshape(*lead, H, C * W, 3)
 
 
@@ -369,54 +343,13 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--yaw", type=float, nargs="+", default=None, help="per person the rotation about --up in degrees (default 0)")
     ap.add_argument("--position", type=float, nargs="+", default=None, help="per person x y z: the translation after the rotation (default 0 0 0)")
     ap.add_argument("--pivot", type=float, nargs="+", default=None, help="per person x y z: the point the rotation goes through (default 0 0 0)")
-    ap.add_argument("--up", type=float, nargs=3, default=(0.0, 1.0, 0.0), metavar=("X", "Y", "Z"), help="world direction shown upwards; the yaw axis")
     ap.add_argument("--repetition", type=int, default=0, help="which of the R sequences of every results.npy")
     ap.add_argument("--out", required=True, help="frames.npy: a uint8 array [T, H, C W, 3]")
-    cam = ap.add_mutually_exclusive_group()
-    cam.add_argument("--camera-json", metavar="FILE", help='{"K": 3 x 3, "Rt": 3 x 4} (OpenCV), or lists of them, one per camera')
-    cam.add_argument("--eye", type=float, nargs=3, metavar=("X", "Y", "Z"),
-                     help="camera position; default: in front of the first frame's bounding box along +z, far enough to see everyone")
-    ap.add_argument("--target", type=float, nargs=3, metavar=("X", "Y", "Z"), help="point looked at; default: the bounding box centre")
-    ap.add_argument("--fov", type=float, default=40.0, help="vertical field of view in degrees")
-    ap.add_argument("--size", type=int, nargs=2, default=(256, 256), metavar=("H", "W"), help="height and width of one camera's panel")
-    ap.add_argument("--frames", default=None, metavar="A:B", help="frames A..B-1 of the time axis only")
-    ap.add_argument("--video", default=None, metavar="FILE", help="also write a Motion-JPEG AVI file, encoded on the GPU (video.py)")
-    ap.add_argument("--audio", default=None, metavar="FILE", help="with --video: the conversation's wav file, every channel written as 16-bit PCM")
-    ap.add_argument("--fps", type=float, default=30.0, help="with --video: frames per second")
-    ap.add_argument("--body-embs", choices=("per_frame", "rest"), default="per_frame")
-    ap.add_argument("--max-bytes", type=int, default=1 << 30, help="activation budget of one chunk of frames")
-    ap.add_argument("--supersample", type=int, default=1, metavar="S", choices=range(1, _lib.RENDER_MAX_SUPERSAMPLE + 1),
-                    help="anti-aliasing: S x S samples per pixel")
-    ap.add_argument("--background", type=float, nargs=3, default=None, metavar=("R", "G", "B"), help="display colour in [0, 255] behind the people")
-    ap.add_argument("--uv-size", type=int, default=1024)
-    ap.add_argument("--encoder-uv-size", type=int, default=512)
-    ap.add_argument("--n-init-ftrs", type=int, default=8)
-    ap.add_argument("--upscale-n-ftrs", type=int, default=8)
-    ap.add_argument("--pose-to-shadow-dims", type=int, default=104)
-    for name, default in (("n-pose-enc-channels", 16), ("n-embs", 1024), ("n-embs-enc-channels", 32), ("n-face-embs", 256),
-                          ("n-init-channels", 64), ("n-min-channels", 4)):     # the decoder's configuration, as in encoder.main
-        ap.add_argument(f"--{name}", type=int, default=default)
+    avatar.add_camera_arguments(ap, per="camera", eye_help="in front of the first frame's bounding box along +z, far enough to see everyone")
+    avatar.add_render_arguments(ap)
+    avatar.add_video_arguments(ap)
+    avatar.add_network_arguments(ap, encoders=True)
     return ap
-
-
-def load_avatar(assets_path: str, checkpoint_path: str, args) -> Avatar:
-    """The networks of one person from static_assets.pt and the body model's state dict, configured by the command line's flags."""
-    from .decoder import BodyDecoder
-    from .encoder import BodyEncoder, FaceDecoder, FaceEncoder
-    from .skinning import BodySkeleton
-    from .texture import BodyTexture
-    assets = torch.load(assets_path, map_location="cpu", weights_only=False)
-    state = torch.load(checkpoint_path, map_location="cpu", weights_only=False)
-    surface = BodySurface.from_static_assets(assets, uv_size=args.uv_size)
-    decoder = BodyDecoder.from_state_dict(
-        state, assets, surface, uv_size=args.uv_size, n_pose_dims=args.pose_to_shadow_dims - 6, n_pose_enc_channels=args.n_pose_enc_channels,
-        n_embs=args.n_embs, n_embs_enc_channels=args.n_embs_enc_channels, n_face_embs=args.n_face_embs, n_init_channels=args.n_init_channels,
-        n_min_channels=args.n_min_channels)
-    texture = BodyTexture.from_state_dict(state, assets, surface, uv_size=args.uv_size, n_init_ftrs=args.n_init_ftrs,
-                                          upscale_n_ftrs=args.upscale_n_ftrs, pose_to_shadow_dims=args.pose_to_shadow_dims)
-    return Avatar(FaceDecoder.from_state_dict(state, assets), FaceEncoder.from_state_dict(state, assets, uv_size=args.encoder_uv_size),
-                  BodyEncoder.from_state_dict(state, assets, surface, uv_size=args.encoder_uv_size), decoder, texture,
-                  BodySkeleton.from_static_assets(assets), surface)
 
 
 def main(argv=None) -> int:
@@ -435,24 +368,15 @@ def main(argv=None) -> int:
         raise A2PError("--audio goes with --video")
     poses, faces = [], []
     for path in args.results:
-        block = np.load(path, allow_pickle=True).item()
-        for key in ("pose", "face"):
-            if key not in block:
-                raise A2PError(f"{path} holds no `{key}` (keys: {sorted(block)})")
-        pose, face = np.asarray(block["pose"], np.float32), np.asarray(block["face"], np.float32)
+        pose, face = avatar.load_codes_clip(path)
         if pose.ndim != 3 or face.ndim != 3 or pose.shape[:2] != face.shape[:2] or not 0 <= args.repetition < pose.shape[0]:
             raise A2PError(f"{path}: `pose` must be [R, T, P] and `face` [R, T, F] with the same R > {args.repetition} and T (got "
                            f"{list(pose.shape)} and {list(face.shape)})")
-        pose, face = pose[args.repetition], face[args.repetition]
-        if args.frames is not None:
-            a, _, b = args.frames.partition(":")
-            window = slice(int(a) if a else None, int(b) if b else None)
-            pose, face = pose[window], face[window]
-        poses.append(pose), faces.append(face)
+        window = avatar.frame_window(args.frames)
+        poses.append(pose[args.repetition][window]), faces.append(face[args.repetition][window])
     if len({len(x) for x in poses}) != 1:
         raise A2PError(f"the people have {[len(x) for x in poses]} frames: need the same number")
-    if not torch.cuda.is_available():
-        raise A2PError("the frames are rendered on the MI355X; there is no CPU implementation")
+    avatar.require_gpu("the frames are rendered")
     avatars = [load_avatar(a, c, args) for a, c in zip(args.assets, args.checkpoint)]
     places = [placement(yaw[p], position[3 * p:3 * p + 3], args.up, pivot[3 * p:3 * p + 3]).numpy() for p in range(P)]
     H, W = args.size
@@ -465,8 +389,7 @@ def main(argv=None) -> int:
     np.save(args.out, frames)
     print(f"{args.out}: frames {list(frames.shape)} uint8, {P} people")
     if args.video is not None:
-        from . import video
-        audio, rate = video.wav_audio(args.audio) if args.audio is not None else (None, None)
+        audio, rate = avatar.video_audio(args)
         render_conversation_video(avatars, poses_gpu, faces, places, K, Rt, H, W, args.video, audio=audio, audio_rate=rate, fps=args.fps, **kw)
         print(f"{args.video}: {frames.shape[0]} frames at {args.fps:g} fps")
     return 0

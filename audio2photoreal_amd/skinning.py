@@ -24,7 +24,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, avatar
 from ._lib import A2PError
 
 CHANNELS = 7   # tx ty tz rx ry rz sc per joint
@@ -553,13 +553,7 @@ def pose_motion(skeleton: BodySkeleton, motion, vertices: bool = True, device=No
     entry the generators return [B, T, 104] (numpy or tensor), the sampler layout [B, 104, 1, T] -- UN-NORMALISED first, see the
     module docstring -- or flat frames [N, 104] (then the outputs are [N, J, 3] / [N, V, 3]).  The scales are the skeleton's
     lbs_scale.  vertices=False skips the mesh.  A numpy input goes to `device` (default: the current GPU)."""
-    frames, lead = motion_frames(motion, skeleton.P_pos)
-    if not torch.is_tensor(frames):
-        frames = torch.from_numpy(frames)
-    if not frames.is_cuda:
-        if not torch.cuda.is_available():
-            raise A2PError("pose_motion runs on the MI355X; there is no CPU implementation")
-        frames = frames.to(device if device is not None else "cuda")
+    frames, lead = avatar.clip_frames("pose_motion", motion, skeleton.P_pos, device)
     g = torch.from_numpy(skeleton.global_scaling).to(frames.device)
     if not vertices:
         return {"joints": (skeleton.joint_states(frames)[:, :, 0:3] * g).reshape(*lead, skeleton.J, 3)}
@@ -568,18 +562,19 @@ def pose_motion(skeleton: BodySkeleton, motion, vertices: bool = True, device=No
             "vertices": skeleton.skin(mats).reshape(*lead, skeleton.V, 3)}
 
 
-def main(argv=None) -> int:
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m audio2photoreal_amd.skinning",
                                  description="Pose the body mesh for the motions of a results.npy (un-normalised body poses).")
     ap.add_argument("--results", required=True, help="results.npy of sample.generate (key `motions` [B, 104, 1, T])")
     ap.add_argument("--assets", required=True, help="static_assets.pt: lbs_model_json, lbs_config_dict, lbs_template_verts, lbs_scale, global_scaling")
     ap.add_argument("--out", required=True, help="geometry.npy: a pickled dict of float32 arrays `joints` (and `vertices`)")
     ap.add_argument("--joints-only", action="store_true", help="skip the mesh")
-    args = ap.parse_args(argv)
-    block = np.load(args.results, allow_pickle=True).item()
-    motions = block.get("motions", block.get("motion"))
-    if motions is None:
-        raise A2PError(f"{args.results} holds neither `motions` nor `motion` (keys: {sorted(block)})")
+    return ap
+
+
+def main(argv=None) -> int:
+    args = parser().parse_args(argv)
+    (motions,) = avatar.load_block(args.results, ("motions", "motion"))
     skeleton = BodySkeleton.from_static_assets(torch.load(args.assets, map_location="cpu", weights_only=False))
     out = pose_motion(skeleton, np.asarray(motions), vertices=not args.joints_only)
     np.save(args.out, {k: v.cpu().numpy() for k, v in out.items()})

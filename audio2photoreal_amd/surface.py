@@ -19,12 +19,12 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, avatar
 from ._lib import A2PError
 
 
 # ------------------------------------------------------------------------------------------------ host preparation
-def _index_array(name: str, a, cols: int, bound: int, what: str, lowest: int = 0) -> np.ndarray:
+def index_array(name: str, a, cols: int, bound: int, what: str, lowest: int = 0) -> np.ndarray:
     """[., cols] int64 with every entry inside [lowest, bound), or a ValueError naming the first offending element."""
     raw = np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
     if raw.ndim != 2 or raw.shape[1] != cols or not (np.issubdtype(raw.dtype, np.integer) or raw.size == 0):
@@ -90,8 +90,8 @@ class BodySurface:
         V = int(n_verts) if n_verts is not None else (given.shape[0] if given is not None else int(raw_vi.max(initial=-1)) + 1)
         if V < 1:
             raise ValueError(f"the mesh has V={V} vertices; need at least 1")
-        self.vi = _index_array("vi", raw_vi, 3, V, "V")
-        self.vti = _index_array("vti", vti, 3, T, "T")
+        self.vi = index_array("vi", raw_vi, 3, V, "V")
+        self.vti = index_array("vti", vti, 3, T, "T")
         F = self.vi.shape[0]
         if F < 1 or self.vti.shape[0] != F:
             raise ValueError(f"vi holds F={F} faces and vti {self.vti.shape[0]}; need the same F >= 1")
@@ -101,7 +101,7 @@ class BodySurface:
         if given is None:
             self.v2uv = compute_v2uv(V, self.vi, self.vti)
         else:
-            self.v2uv = _index_array("v2uv", given, 4, T, "T")
+            self.v2uv = index_array("v2uv", given, 4, T, "T")
             if self.v2uv.shape[0] != V:
                 raise ValueError(f"v2uv holds {self.v2uv.shape[0]} vertices; the mesh has V={V}")
         self.inc_ptr, self.inc_face = incidence_table(V, self.vi)
@@ -298,7 +298,7 @@ def surface_maps(surface: BodySurface, vertices, camera_pos=None) -> dict:
     return out
 
 
-def main(argv=None) -> int:
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m audio2photoreal_amd.surface",
                                  description="Normals and UV maps for the posed vertices of a geometry.npy.")
     ap.add_argument("--geometry", required=True, help="geometry.npy of audio2photoreal_amd.skinning (key `vertices` [B, T, V, 3])")
@@ -307,17 +307,13 @@ def main(argv=None) -> int:
     ap.add_argument("--uv-size", type=int, default=256, help="side of the UV maps (N C H H 4 bytes of output)")
     ap.add_argument("--camera", type=float, nargs=3, metavar=("X", "Y", "Z"), help="camera position: adds view_cos and view_cos_uv")
     ap.add_argument("--frames", default=None, metavar="A:B", help="frames A..B-1 of the time axis only")
-    args = ap.parse_args(argv)
-    block = np.load(args.geometry, allow_pickle=True).item()
-    if "vertices" not in block:
-        raise A2PError(f"{args.geometry} holds no `vertices` (keys: {sorted(block)}); run the skinning command without --joints-only")
-    verts = np.asarray(block["vertices"], np.float32)
-    if args.frames is not None:
-        a, _, b = args.frames.partition(":")
-        window = slice(int(a) if a else None, int(b) if b else None)
-        verts = verts[:, window] if verts.ndim == 4 else verts[window]
-    if not torch.cuda.is_available():
-        raise A2PError("the surface maps run on the MI355X; there is no CPU implementation")
+    return ap
+
+
+def main(argv=None) -> int:
+    args = parser().parse_args(argv)
+    verts = avatar.load_vertices(args.geometry, args.frames)
+    avatar.require_gpu("the surface maps run")
     surface = BodySurface.from_static_assets(torch.load(args.assets, map_location="cpu", weights_only=False), uv_size=args.uv_size)
     camera = None if args.camera is None else torch.tensor([args.camera], dtype=torch.float32, device="cuda")
     out = surface_maps(surface, torch.from_numpy(np.ascontiguousarray(verts)).to("cuda"), camera)

@@ -30,9 +30,10 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, avatar
 from ._lib import A2PError
-from .decoder import LRELU_SLOPE, SeamSampler, _asset, _checked, _gpu_f32, _np, _source, conv2d_ub
+from .avatar import HostNet, as_numpy, asset, checked, f32, gpu_f32, operand, resize_axis_half64, source
+from .decoder import LRELU_SLOPE, SeamSampler, conv2d_ub
 
 WB_SCALE = (1.05, 0.95, 1.45)          # linear2displayBatch's white balance
 DISPLAY_GAMMA, DISPLAY_BLACK = 1.5, 5.0 / 255.0
@@ -42,7 +43,7 @@ DISPLAY_GAMMA, DISPLAY_BLACK = 1.5, 5.0 / 255.0
 def fold_weight_norm64(weight_v, weight_g) -> np.ndarray:
     """float64 w = weight_v * (weight_g / ||weight_v||) with the norm over the WHOLE weight_v; weight_g broadcasts against weight_v,
     so it serves g_dim = 0 ([C_out, 1, ...]) and the transposed layers' g_dim = 1 ([1, C_out, 1, 1]) alike."""
-    v, g = _np(weight_v).astype(np.float64), _np(weight_g).astype(np.float64)
+    v, g = as_numpy(weight_v).astype(np.float64), as_numpy(weight_g).astype(np.float64)
     return v * (g / np.sqrt((v * v).sum()))
 
 
@@ -51,9 +52,9 @@ def folded_weight64(state_dict, name: str, shape, g_axis: int = 0) -> np.ndarray
     (1 everywhere but shape[g_axis] on axis g_axis) and `name.weight_v`.  A missing key or a wrong shape is a ValueError naming it."""
     shape = tuple(int(s) for s in shape)
     if f"{name}.weight" in state_dict:
-        return _checked(state_dict, f"{name}.weight", shape).astype(np.float64)
+        return checked(state_dict, f"{name}.weight", shape).astype(np.float64)
     g_shape = tuple(s if a == g_axis else 1 for a, s in enumerate(shape))
-    return fold_weight_norm64(_checked(state_dict, f"{name}.weight_v", shape), _checked(state_dict, f"{name}.weight_g", g_shape))
+    return fold_weight_norm64(checked(state_dict, f"{name}.weight_v", shape), checked(state_dict, f"{name}.weight_g", g_shape))
 
 
 def folded_weight_transposed(state_dict, name: str, shape) -> np.ndarray:
@@ -61,20 +62,10 @@ def folded_weight_transposed(state_dict, name: str, shape) -> np.ndarray:
     return np.ascontiguousarray(folded_weight64(state_dict, name, shape, g_axis=1), np.float32)
 
 
-def _f32(a) -> np.ndarray:
-    return np.ascontiguousarray(a, np.float32)
-
-
-def _resize_axis64(n_in: int, n_out: int):
-    src = np.maximum((np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5, 0.0)
-    i0 = np.minimum(src.astype(np.int64), n_in - 1)
-    return i0, i0 + (i0 < n_in - 1), src - i0
-
-
 def gaussian_blur(x, kernel_size: int = 11) -> np.ndarray:
     """float64 [.., H, W]: torchvision's gaussian_blur with its default sigma 0.3 ((k - 1) / 2 - 1) + 0.8, restated: the 1-D kernel
     exp(-x^2 / 2 sigma^2) at x = -(k - 1) / 2 .. (k - 1) / 2, normalised; its outer product; reflect padding."""
-    x = _np(x).astype(np.float64)
+    x = as_numpy(x).astype(np.float64)
     k, r = int(kernel_size), int(kernel_size) // 2
     if k % 2 != 1 or min(x.shape[-2:]) <= r:
         raise ValueError(f"gaussian_blur: kernel_size={k} must be odd and the map ({list(x.shape[-2:])}) larger than {r} (reflect padding)")
@@ -94,28 +85,21 @@ def gaussian_blur(x, kernel_size: int = 11) -> np.ndarray:
 def prepare_tex_mean(tex_mean, size: int) -> np.ndarray:
     """float32 [1, 3, size, size]: AutoEncoder.__init__'s F.interpolate(gaussian_blur(tex_mean[None], kernel_size=11), (size, size),
     mode="bilinear") in float64 numpy, rounded to float32 once.  tex_mean is the assets' [C, H, W]."""
-    a = _np(tex_mean)
+    a = as_numpy(tex_mean)
     if a.ndim != 3:
         raise ValueError(f"tex_mean must be [C, H, W] (got {list(a.shape)})")
     if not np.isfinite(a).all():
         raise ValueError("tex_mean holds non-finite values")
     b = gaussian_blur(a[None], 11)
-    (y0, y1, ly), (x0, x1, lx) = _resize_axis64(b.shape[2], int(size)), _resize_axis64(b.shape[3], int(size))
+    (y0, y1, ly), (x0, x1, lx) = resize_axis_half64(b.shape[2], int(size)), resize_axis_half64(b.shape[3], int(size))
     top = (1 - lx) * b[:, :, y0][:, :, :, x0] + lx * b[:, :, y0][:, :, :, x1]
     bot = (1 - lx) * b[:, :, y1][:, :, :, x0] + lx * b[:, :, y1][:, :, :, x1]
-    return _f32((1 - ly)[:, None] * top + ly[:, None] * bot)
+    return f32((1 - ly)[:, None] * top + ly[:, None] * bot)
 
 
 # ------------------------------------------------------------------------------------------------ the four launches
-def _operand(t, name: str, shape_text: str, ok, dev):
-    t = _gpu_f32(t, name, shape_text, ok)
-    if t.device != dev:
-        raise A2PError(f"{name} is on {t.device}, x on {dev}")
-    return t.contiguous()
-
-
 def _strided(entry: str, x, weight, bias, slope, sigmoid_beta, skip, transposed: bool):
-    x, xs = _source(x, "x")
+    x, xs = source(x, "x")
     N, C_in, Hs, Ws = x.shape
     dev = x.device
     if not transposed and min(Hs, Ws) < 2:
@@ -124,13 +108,13 @@ def _strided(entry: str, x, weight, bias, slope, sigmoid_beta, skip, transposed:
         raise A2PError(f"x is {Hs} x {Ws}: the output side may not exceed {_lib.CONV_MAX_SIZE}")
     H, W = (2 * Hs, 2 * Ws) if transposed else ((Hs - 2) // 2 + 1, (Ws - 2) // 2 + 1)
     w_text = "[C_in, C_out, 4, 4]" if transposed else "[C_out, C_in, 4, 4]"
-    weight = _operand(weight, "weight", w_text, lambda s: len(s) == 4 and s[2:] == (4, 4) and s[0 if transposed else 1] == C_in, dev)
+    weight = operand(weight, "weight", w_text, lambda s: len(s) == 4 and s[2:] == (4, 4) and s[0 if transposed else 1] == C_in, dev)
     C_out = weight.shape[1 if transposed else 0]
     d = _lib.A2PTexConvDesc()
     d.x, d.weight, d.N, d.C_out = xs, _lib.ptr(weight), N, C_out
     keep = [x, weight]
     if bias is not None:
-        bias = _operand(bias, "bias", f"[{C_out}] or [{C_out}, {H}, {W}]", lambda s: s in ((C_out,), (C_out, H, W)), dev)
+        bias = operand(bias, "bias", f"[{C_out}] or [{C_out}, {H}, {W}]", lambda s: s in ((C_out,), (C_out, H, W)), dev)
         keep.append(bias)
         d.bias, d.bias_mode = _lib.ptr(bias), _lib.CONV_BIAS_TIED if bias.dim() == 1 else _lib.CONV_BIAS_UNTIED
     if slope is not None and sigmoid_beta is not None:
@@ -140,7 +124,7 @@ def _strided(entry: str, x, weight, bias, slope, sigmoid_beta, skip, transposed:
     if sigmoid_beta is not None:
         d.act, d.beta = _lib.TEX_ACT_SIGMOID, float(sigmoid_beta)
     if skip is not None:
-        skip = _operand(skip, "skip", f"[{N}, {C_out}, {H}, {W}]", lambda s: s == (N, C_out, H, W), dev)
+        skip = operand(skip, "skip", f"[{N}, {C_out}, {H}, {W}]", lambda s: s == (N, C_out, H, W), dev)
         keep.append(skip)
         d.skip = _lib.ptr(skip)
     out = torch.empty(N, C_out, H, W, dtype=torch.float32, device=dev)
@@ -168,7 +152,7 @@ def conv_transpose2d_ub(x, weight, bias=None, *, slope=None, sigmoid_beta=None, 
 
 def resize_bilinear(x, size):
     """F.interpolate(x, size, mode="bilinear", align_corners=False) of x [N, C, Hs, Ws], any ratio up or down: a new tensor."""
-    x = _gpu_f32(x, "x", "[N, C, Hs, Ws] with Hs, Ws >= 1", lambda s: len(s) == 4 and min(s[2:]) >= 1).contiguous()
+    x = gpu_f32(x, "x", "[N, C, Hs, Ws] with Hs, Ws >= 1", lambda s: len(s) == 4 and min(s[2:]) >= 1).contiguous()
     H, W = int(size[0]), int(size[1])
     if not (1 <= H <= _lib.CONV_MAX_SIZE and 1 <= W <= _lib.CONV_MAX_SIZE):
         raise A2PError(f"size {H} x {W} is outside [1, {_lib.CONV_MAX_SIZE}]")
@@ -185,14 +169,14 @@ def resize_bilinear(x, size):
 def compose_texture(t, u, tex_mean, tex_std, shadow=None):
     """One launch of a2p_texture_compose: ((resize_bilinear(t, 2x) + pixel_shuffle(u, 2)) * tex_std + tex_mean) * shadow.  t [N, C,
     Sh, Sw]; u [N, 4 C, Sh, Sw]; tex_mean [C, 2 Sh, 2 Sw] (or [1, C, ..]); tex_std a number; shadow [N or 1, 1, 2 Sh, 2 Sw] or None."""
-    t = _gpu_f32(t, "t", "[N, C, Sh, Sw]", lambda s: len(s) == 4 and min(s[1:]) >= 1).contiguous()
+    t = gpu_f32(t, "t", "[N, C, Sh, Sw]", lambda s: len(s) == 4 and min(s[1:]) >= 1).contiguous()
     N, C, Sh, Sw = t.shape
     dev = t.device
-    u = _operand(u, "u", f"[{N}, {4 * C}, {Sh}, {Sw}]", lambda s: s == (N, 4 * C, Sh, Sw), dev)
-    tex_mean = _operand(tex_mean, "tex_mean", f"[{C}, {2 * Sh}, {2 * Sw}]", lambda s: s in ((C, 2 * Sh, 2 * Sw), (1, C, 2 * Sh, 2 * Sw)), dev)
+    u = operand(u, "u", f"[{N}, {4 * C}, {Sh}, {Sw}]", lambda s: s == (N, 4 * C, Sh, Sw), dev)
+    tex_mean = operand(tex_mean, "tex_mean", f"[{C}, {2 * Sh}, {2 * Sw}]", lambda s: s in ((C, 2 * Sh, 2 * Sw), (1, C, 2 * Sh, 2 * Sw)), dev)
     frames = 0
     if shadow is not None:
-        shadow = _operand(shadow, "shadow", f"[{N} or 1, 1, {2 * Sh}, {2 * Sw}]",
+        shadow = operand(shadow, "shadow", f"[{N} or 1, 1, {2 * Sh}, {2 * Sw}]",
                           lambda s: len(s) == 4 and s[0] in (1, N) and s[1:] == (1, 2 * Sh, 2 * Sw), dev)
         frames = shadow.shape[0]
     out = torch.empty(N, C, 2 * Sh, 2 * Sw, dtype=torch.float32, device=dev)
@@ -205,23 +189,13 @@ def compose_texture(t, u, tex_mean, tex_std, shadow=None):
 
 
 # ------------------------------------------------------------------------------------------------ the networks
-class _Net:
-    """Host arrays in `params` (float32, folded, under the reference's key names); device copies per device on first use."""
-
-    def _tables(self, device):
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in self.params.items()}
-        return self._dev[key]
-
-
 def _positive(**values):
     for name, v in values.items():
         if not 1 <= int(v) <= _lib.CONV_MAX_CHANNELS:
             raise ValueError(f"{name}={v} is outside [1, {_lib.CONV_MAX_CHANNELS}]")
 
 
-class ViewUNet(_Net):
+class ViewUNet(HostNet):
     """UNetWB(in_channels, out_channels, size, n_init_ftrs, out_scale) of nn/unet.py from the keys down1.0.weight_v / weight_g /
     bias ... down5.0.*, up1.0.* ... up5.0.*, out.* (a fused `weight` is accepted in place of a pair): five down launches, five
     transposed launches (up1 .. up4 add their skip inside the launch) and one conv2d_ub launch for `out` over cat([x, x1])."""
@@ -238,16 +212,16 @@ class ViewUNet(_Net):
         p = {}
         for i in range(1, 6):
             s = size >> i
-            p[f"down{i}.0.weight"] = _f32(folded_weight64(sd, f"down{i}.0", (ch[i], ch[i - 1], 4, 4)))
-            p[f"down{i}.0.bias"] = _checked(sd, f"down{i}.0.bias", (ch[i], s, s))
+            p[f"down{i}.0.weight"] = f32(folded_weight64(sd, f"down{i}.0", (ch[i], ch[i - 1], 4, 4)))
+            p[f"down{i}.0.bias"] = checked(sd, f"down{i}.0.bias", (ch[i], s, s))
         up = [16 * F, 8 * F, 4 * F, 2 * F, F, F]
         for i in range(1, 6):
             s = size >> (5 - i)
             p[f"up{i}.0.weight"] = folded_weight_transposed(sd, f"up{i}.0", (up[i - 1], up[i], 4, 4))
-            p[f"up{i}.0.bias"] = _checked(sd, f"up{i}.0.bias", (up[i], s, s))
+            p[f"up{i}.0.bias"] = checked(sd, f"up{i}.0.bias", (up[i], s, s))
         w = folded_weight64(sd, "out", (self.out_channels, F + self.in_channels, 1, 1)) * self.out_scale
-        p["out.weight_x"], p["out.weight_x1"] = _f32(w[:, :F]), _f32(w[:, F:, 0, 0])
-        p["out.bias"] = _f32(_checked(sd, "out.bias", (self.out_channels, size, size)).astype(np.float64) * self.out_scale)
+        p["out.weight_x"], p["out.weight_x1"] = f32(w[:, :F]), f32(w[:, F:, 0, 0])
+        p["out.bias"] = f32(checked(sd, "out.bias", (self.out_channels, size, size)).astype(np.float64) * self.out_scale)
         self.params, self._dev = p, {}
 
     def activation_floats_per_frame(self) -> int:
@@ -259,7 +233,7 @@ class ViewUNet(_Net):
         """x [N, in_channels, size, size] -> [N, out_channels, size, size]; `keep` (a dict) receives the intermediates down1 .. down5
         and up1 .. up5."""
         s = self.size
-        x1 = _gpu_f32(x, "x", f"[N, {self.in_channels}, {s}, {s}]", lambda sh: len(sh) == 4 and sh[1:] == (self.in_channels, s, s))
+        x1 = gpu_f32(x, "x", f"[N, {self.in_channels}, {s}, {s}]", lambda sh: len(sh) == 4 and sh[1:] == (self.in_channels, s, s))
         t = self._tables(x1.device)
         downs = [x1]
         for i in range(1, 6):
@@ -277,7 +251,7 @@ class ViewUNet(_Net):
     __call__ = forward
 
 
-class PoseShadow(_Net):
+class PoseShadow(HostNet):
     """PoseToShadow(n_pose_dims, uv_size, beta) of nn/shadow.py from fc_block.0.* and conv_block.0/2/4/6/8.*: the linear layer
     through conv2d_ub on a 1 x 1 plane, five transposed launches at 8 .. 128 (the last with the sigmoid), resize_bilinear."""
     LAYERS = ((0, 256, 256, 8), (2, 256, 128, 16), (4, 128, 128, 32), (6, 128, 64, 64), (8, 64, 1, 128))
@@ -288,11 +262,11 @@ class PoseShadow(_Net):
             raise ValueError(f"uv_size={uv_size} is outside [1, {_lib.CONV_MAX_SIZE}]")
         self.n_pose_dims, self.uv_size, self.beta = int(n_pose_dims), int(uv_size), float(beta)
         sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
-        p = {"fc_block.0.weight": _f32(folded_weight64(sd, "fc_block.0", (256 * 4 * 4, self.n_pose_dims)))[:, :, None, None],
-             "fc_block.0.bias": _checked(sd, "fc_block.0.bias", (256 * 4 * 4,))}
+        p = {"fc_block.0.weight": f32(folded_weight64(sd, "fc_block.0", (256 * 4 * 4, self.n_pose_dims)))[:, :, None, None],
+             "fc_block.0.bias": checked(sd, "fc_block.0.bias", (256 * 4 * 4,))}
         for i, cin, cout, s in self.LAYERS:
             p[f"conv_block.{i}.weight"] = folded_weight_transposed(sd, f"conv_block.{i}", (cin, cout, 4, 4))
-            p[f"conv_block.{i}.bias"] = _checked(sd, f"conv_block.{i}.bias", (cout, s, s))
+            p[f"conv_block.{i}.bias"] = checked(sd, f"conv_block.{i}.bias", (cout, s, s))
         self.params, self._dev = p, {}
 
     def activation_floats_per_frame(self) -> int:
@@ -300,7 +274,7 @@ class PoseShadow(_Net):
 
     def forward(self, motion, keep=None):
         """motion [N, n_pose_dims] -> shadow_map [N, 1, uv_size, uv_size]; `keep` receives shadow_map_lowres [N, 1, 128, 128]."""
-        motion = _gpu_f32(motion, "motion", f"[N, {self.n_pose_dims}]", lambda s: len(s) == 2 and s[1] == self.n_pose_dims).contiguous()
+        motion = gpu_f32(motion, "motion", f"[N, {self.n_pose_dims}]", lambda s: len(s) == 2 and s[1] == self.n_pose_dims).contiguous()
         t = self._tables(motion.device)
         x = conv2d_ub(motion[:, :, None, None], t["fc_block.0.weight"], t["fc_block.0.bias"], slope=LRELU_SLOPE)
         x = x.reshape(motion.shape[0], 256, 4, 4)
@@ -315,7 +289,7 @@ class PoseShadow(_Net):
     __call__ = forward
 
 
-class UpscaleNet(_Net):
+class UpscaleNet(HostNet):
     """UpscaleNet(in_channels, out_channels, n_ftrs, size, upscale_factor=2) of mesh_vae_drivable.py without its pixel shuffle
     (compose_texture applies it): conv_block.0 (k = 3, LeakyReLU) and out_block (k = 1), two conv2d_ub launches."""
 
@@ -324,10 +298,10 @@ class UpscaleNet(_Net):
         self.in_channels, self.out_channels, self.n_ftrs, self.size = int(in_channels), int(out_channels), int(n_ftrs), int(size)
         sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
         s = self.size
-        self.params = {"conv_block.0.weight": _f32(folded_weight64(sd, "conv_block.0", (self.n_ftrs, self.in_channels, 3, 3))),
-                       "conv_block.0.bias": _checked(sd, "conv_block.0.bias", (self.n_ftrs, s, s)),
-                       "out_block.weight": _f32(folded_weight64(sd, "out_block", (4 * self.out_channels, self.n_ftrs, 1, 1))),
-                       "out_block.bias": _checked(sd, "out_block.bias", (4 * self.out_channels, s, s))}
+        self.params = {"conv_block.0.weight": f32(folded_weight64(sd, "conv_block.0", (self.n_ftrs, self.in_channels, 3, 3))),
+                       "conv_block.0.bias": checked(sd, "conv_block.0.bias", (self.n_ftrs, s, s)),
+                       "out_block.weight": f32(folded_weight64(sd, "out_block", (4 * self.out_channels, self.n_ftrs, 1, 1))),
+                       "out_block.bias": checked(sd, "out_block.bias", (4 * self.out_channels, s, s))}
         self._dev = {}
 
     def activation_floats_per_frame(self) -> int:
@@ -350,26 +324,23 @@ def forward_tex(upscale_net: UpscaleNet, seam_sampler: SeamSampler, seam_sampler
     compose_texture; impaint and two resamples of the result.  tex_mean_rec, tex_view_rec [N, C, S, S]; tex_mean [C, 2 S, 2 S] on the
     GPU; shadow_map [N or 1, 1, 2 S, 2 S] or None (no shadow).  No input is modified.  Returns [N, C, 2 S, 2 S]."""
     S = seam_sampler.H
-    tex_mean_rec = _gpu_f32(tex_mean_rec, "tex_mean_rec", f"[N, C, {S}, {S}]", lambda s: len(s) == 4 and s[2:] == (S, S))
+    tex_mean_rec = gpu_f32(tex_mean_rec, "tex_mean_rec", f"[N, C, {S}, {S}]", lambda s: len(s) == 4 and s[2:] == (S, S))
     N, C = tex_mean_rec.shape[:2]
-    tex_view_rec = _gpu_f32(tex_view_rec, "tex_view_rec", f"[{N}, {C}, {S}, {S}]", lambda s: s == (N, C, S, S))
+    tex_view_rec = gpu_f32(tex_view_rec, "tex_view_rec", f"[{N}, {C}, {S}, {S}]", lambda s: s == (N, C, S, S))
     k = seam_sampler_2k
     with _lib.on_device_of(tex_mean_rec):
         t = seam_sampler.resample(seam_sampler.impaint(tex_mean_rec + tex_view_rec))
         u = upscale_net(torch.cat([tex_mean_rec, tex_view_rec], dim=1))
         if shadow_map is not None:
-            shadow_map = _gpu_f32(shadow_map, "shadow_map", f"[{N} or 1, 1, {2 * S}, {2 * S}]",
+            shadow_map = gpu_f32(shadow_map, "shadow_map", f"[{N} or 1, 1, {2 * S}, {2 * S}]",
                                   lambda s: len(s) == 4 and s[0] in (1, N) and s[1:] == (1, 2 * S, 2 * S))
             shadow_map = k.resample(k.resample(k.impaint(shadow_map.clone())))
         tex = compose_texture(t, u, tex_mean, tex_std, shadow_map)
         return k.resample(k.resample(k.impaint(tex)))
 
 
-class BodyTexture:
+class BodyTexture(HostNet):
     """The texture half of AutoEncoder.forward: UNetViewDecoder, PoseToShadow, UpscaleNet and forward_tex."""
-
-    def __init__(self):
-        raise TypeError("use BodyTexture.from_state_dict")
 
     @classmethod
     def from_state_dict(cls, state_dict, assets, surface, *, uv_size: int = 1024, n_init_ftrs: int = 8, upscale_n_ftrs: int = 8,
@@ -392,31 +363,28 @@ class BodyTexture:
         if any(k.startswith("pose_to_shadow.") for k in sd):
             self.pose_shadow = PoseShadow(sd, pose_to_shadow_dims, 2 * S, shadow_beta, prefix="pose_to_shadow.")
         if "tex_mean" in sd:
-            self.tex_mean = _checked(sd, "tex_mean", (1, 3, 2 * S, 2 * S))[0]
+            self.tex_mean = checked(sd, "tex_mean", (1, 3, 2 * S, 2 * S))[0]
         else:
-            self.tex_mean = prepare_tex_mean(_asset_of(assets, "tex_mean"), 2 * S)[0]
+            self.tex_mean = prepare_tex_mean(asset(assets, "tex_mean"), 2 * S)[0]
             if self.tex_mean.shape[0] != 3:
                 raise ValueError(f"assets `tex_mean` has {self.tex_mean.shape[0]} channels; the texture has 3")
         self.tex_std = 64.0
         if (hasattr(assets, "keys") and "tex_var" in assets) or (not hasattr(assets, "keys") and hasattr(assets, "tex_var")):
-            var = _np(_asset(assets, "tex_var"))
+            var = as_numpy(asset(assets, "tex_var"))
             if var.size != 1:
                 raise ValueError(f"assets `tex_var` has shape {list(var.shape)}; the configuration expects a scalar")
             self.tex_std = float(var.reshape(()))
         if not np.isfinite(self.tex_std):
             raise ValueError(f"assets `tex_var` is not finite ({self.tex_std})")
-        self.seam_sampler, self.seam_sampler_2k = SeamSampler(_asset_of(assets, "seam_data_1024")), SeamSampler(_asset_of(assets, "seam_data_2048"))
+        self.seam_sampler, self.seam_sampler_2k = SeamSampler(asset(assets, "seam_data_1024")), SeamSampler(asset(assets, "seam_data_2048"))
         for key, seam, side in (("seam_data_1024", self.seam_sampler, S), ("seam_data_2048", self.seam_sampler_2k, 2 * S)):
             if (seam.H, seam.W) != (side, side):
                 raise ValueError(f"assets `{key}` is for {seam.H} x {seam.W} maps; the configuration expects {side} x {side}")
-        self._dev = {}
+        self.params, self._dev = {"tex_mean": self.tex_mean}, {}
         return self
 
     def _tex_mean(self, device):
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = torch.from_numpy(np.ascontiguousarray(self.tex_mean)).to(device)
-        return self._dev[key]
+        return self._tables(device)["tex_mean"]
 
     def activation_bytes_per_frame(self) -> int:
         """An upper bound of the bytes one frame's forward allocates (every intermediate counted as if none were freed)."""
@@ -429,7 +397,7 @@ class BodyTexture:
     def forward_tex(self, tex_mean_rec, tex_view_rec, shadow_map=None):
         """forward_tex (below) with this object's networks, seam tables, tex_mean and tex_std."""
         S = self.uv_size
-        tex_mean_rec = _gpu_f32(tex_mean_rec, "tex_mean_rec", f"[N, 3, {S}, {S}]", lambda s: len(s) == 4 and s[1:] == (3, S, S))
+        tex_mean_rec = gpu_f32(tex_mean_rec, "tex_mean_rec", f"[N, 3, {S}, {S}]", lambda s: len(s) == 4 and s[1:] == (3, S, S))
         return forward_tex(self.upscale_net, self.seam_sampler, self.seam_sampler_2k, self._tex_mean(tex_mean_rec.device), self.tex_std,
                            tex_mean_rec, tex_view_rec, shadow_map)
 
@@ -443,7 +411,7 @@ class BodyTexture:
         if motion is not None and self.pose_shadow is None:
             raise A2PError("motion was given but the state dict held no pose_to_shadow.* weights")
         S = self.uv_size
-        tex_mean_rec = _gpu_f32(tex_mean_rec, "tex_mean_rec", f"[N, 3, {S}, {S}]", lambda s: len(s) == 4 and s[1:] == (3, S, S))
+        tex_mean_rec = gpu_f32(tex_mean_rec, "tex_mean_rec", f"[N, 3, {S}, {S}]", lambda s: len(s) == 4 and s[1:] == (3, S, S))
         with _lib.on_device_of(tex_mean_rec):
             view_cos_uv = self.surface.to_uv(self.surface.view_cos(geom, camera_pos)[..., None])
             cond_view = torch.cat([view_cos_uv, tex_mean_rec], dim=1)
@@ -454,13 +422,6 @@ class BodyTexture:
         return {"tex_rec": tex_rec, "tex_view_rec": tex_view_rec, "cond_view": cond_view, "shadow_map": shadow_map}
 
     __call__ = forward
-
-
-def _asset_of(assets, key):
-    try:
-        return _asset(assets, key)
-    except ValueError:
-        raise ValueError(f"the assets hold no `{key}`") from None
 
 
 # ------------------------------------------------------------------------------------------------ frames
@@ -540,128 +501,62 @@ def render_rgb_motion(decoder, texture: BodyTexture, skeleton, rasterizer, poses
     under the avatar in linear light, where coverage is a fraction of light, and passed through linear_to_display with it; a
     pixel no sample covers holds the given value itself.  With the defaults the calls are those made without the two keywords."""
     from .render import camera_centre
-    from .skinning import motion_frames
     supersample = rasterizer._supersample(supersample)
     background = display_background(background, rasterizer.height, rasterizer.width)
-    if skeleton.P_pos != 6 + decoder.n_pose_dims:
-        raise A2PError(f"the skeleton takes {skeleton.P_pos} pose parameters; the decoder 6 + n_pose_dims = {6 + decoder.n_pose_dims}")
-    frames, lead = motion_frames(poses, skeleton.P_pos)
-    if not torch.is_tensor(frames):
-        frames = torch.from_numpy(frames)
-    if not frames.is_cuda:
-        if not torch.cuda.is_available():
-            raise A2PError("render_rgb_motion runs on the MI355X; there is no CPU implementation")
-        frames = frames.to("cuda")
+    avatar.check_pose_width(skeleton, decoder)
+    frames, lead = avatar.clip_frames("render_rgb_motion", poses, skeleton.P_pos)
     N, dev = frames.shape[0], frames.device
-
-    def flat(x, name, width):
-        x = torch.as_tensor(x)
-        if tuple(x.shape) != (*lead, width):
-            raise A2PError(f"{name} must be {[*lead, width]} (got {list(x.shape)})")
-        return x.to(device=dev, dtype=torch.float32).reshape(N, width).contiguous()
-
-    embs, face_embs = flat(embs, "embs", decoder.n_embs), flat(face_embs, "face_embs", decoder.n_face_embs)
+    embs = avatar.per_frame(embs, "embs", lead, (decoder.n_embs,), dev)
+    face_embs = avatar.per_frame(face_embs, "face_embs", lead, (decoder.n_face_embs,), dev)
     K, k_per = rasterizer._camera(K, "K", 3, N, dev)
     Rt, rt_per = rasterizer._camera(Rt, "Rt", 4, N, dev)
     camera_pos = camera_centre(Rt) if camera_pos is None else torch.as_tensor(camera_pos).to(device=dev, dtype=torch.float32).reshape(-1, 3)
     if camera_pos.shape[0] not in (1, N):
         raise A2PError(f"camera_pos must be [{N} or 1, 3] (got {list(camera_pos.shape)})")
     cam_per = camera_pos.shape[0] == N and N != 1
-    chunk = max(1, int(max_bytes) // (decoder.activation_bytes_per_frame() + texture.activation_bytes_per_frame()))
     H, W = rasterizer.height, rasterizer.width
     background = tuple(None if x is None else x.to(dev) for x in background)
     out = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
-    for a in range(0, N, chunk):
-        b = min(N, a + chunk)
+    for a, b in avatar.frame_chunks(N, max_bytes, decoder.activation_bytes_per_frame() + texture.activation_bytes_per_frame()):
         part = lambda x, per: x[a:b] if per else x
-        preds = decoder.forward(frames[a:b], embs[a:b], face_embs[a:b])
-        verts = skeleton.pose_vertices(frames[a:b], verts_unposed=preds["geom_delta_rec"])
+        preds, verts = avatar.decode_and_pose(decoder, skeleton, frames[a:b], embs[a:b], face_embs[a:b])
         tex = texture.forward(verts, preds["tex_mean_rec"], part(camera_pos, cam_per),
                               motion=frames[a:b] if texture.pose_shadow is not None else None)
         out[a:b] = display_frames(rasterizer, verts, tex["tex_rec"], part(K, k_per), part(Rt, rt_per), supersample, background)
     return out.reshape(*lead, 3, H, W)
 
 
-def main(argv=None) -> int:
-    from . import render as R
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="python -m audio2photoreal_amd.texture", description="Display RGB frames of the motions of a results.npy.")
-    ap.add_argument("--assets", required=True, help="static_assets.pt: topology, the skinning model, the decoder's masks, tex_mean, both seam tables")
-    ap.add_argument("--out", required=True, help="frames.npy: a float32 array [B, T, 3, H, W] in [0, 255]")
-    ap.add_argument("--size", type=int, nargs=2, default=(256, 256), metavar=("H", "W"), help="image height and width")
-    cam = ap.add_mutually_exclusive_group()                                   # the camera arguments of audio2photoreal_amd.render
-    cam.add_argument("--camera-json", metavar="FILE", help='{"K": 3 x 3, "Rt": 3 x 4} (OpenCV), or lists of them, one per frame')
-    cam.add_argument("--eye", type=float, nargs=3, metavar=("X", "Y", "Z"),
-                     help="camera position; default: in front of the first frame's bounding box along +z, far enough to see all of it")
-    ap.add_argument("--target", type=float, nargs=3, metavar=("X", "Y", "Z"), help="point looked at; default: the bounding box centre")
-    ap.add_argument("--up", type=float, nargs=3, default=(0.0, 1.0, 0.0), metavar=("X", "Y", "Z"), help="world direction shown upwards")
-    ap.add_argument("--fov", type=float, default=40.0, help="vertical field of view in degrees")
-    ap.add_argument("--frames", default=None, metavar="A:B", help="frames A..B-1 of the time axis only")
-    ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write rgb_<sequence>_<frame>.png per frame")
-    ap.add_argument("--max-bytes", type=int, default=1 << 30, help="activation budget of one chunk of frames")
-    ap.add_argument("--supersample", type=int, default=1, metavar="S", choices=range(1, _lib.RENDER_MAX_SUPERSAMPLE + 1),
-                    help="anti-aliasing: S x S samples per pixel")
-    ap.add_argument("--background", type=float, nargs=3, default=None, metavar=("R", "G", "B"),
-                    help="display colour in [0, 255] behind the avatar (default: black, the linear image's 0)")
     ap.add_argument("--results", required=True, help="results.npy of sample.generate (key `motions` [B, P, 1, T], un-normalised)")
     ap.add_argument("--embeddings", required=True, help=".npz with `embs` [B, T, n_embs] and `face_embs` [B, T, n_face_embs]")
+    ap.add_argument("--assets", required=True, help="static_assets.pt: topology, the skinning model, the decoder's masks, tex_mean, both seam tables")
     ap.add_argument("--checkpoint", required=True, help="the body model's state dict (decoder.*, decoder_view.*, upscale_net.*, ...)")
-    ap.add_argument("--uv-size", type=int, default=1024)
-    ap.add_argument("--n-init-ftrs", type=int, default=8)
-    ap.add_argument("--upscale-n-ftrs", type=int, default=8)
-    ap.add_argument("--pose-to-shadow-dims", type=int, default=104)
-    for name, default in (("n-pose-enc-channels", 16), ("n-embs", 1024), ("n-embs-enc-channels", 32), ("n-face-embs", 256),
-                          ("n-init-channels", 64), ("n-min-channels", 4)):     # the rest of the decoder's configuration, as in decoder.main
-        ap.add_argument(f"--{name}", type=int, default=default)
-    args = ap.parse_args(argv)
-    from .decoder import BodyDecoder
-    from .skinning import BodySkeleton
-    from .surface import BodySurface
-    block = np.load(args.results, allow_pickle=True).item()
-    motions = block.get("motions", block.get("motion"))
-    if motions is None:
-        raise A2PError(f"{args.results} holds neither `motions` nor `motion` (keys: {sorted(block)})")
-    motions = np.asarray(motions, np.float32)
-    e = np.load(args.embeddings)
-    for key in ("embs", "face_embs"):
-        if key not in e.files:
-            raise A2PError(f"{args.embeddings} holds no `{key}` (keys: {sorted(e.files)})")
-    embs, face_embs = np.asarray(e["embs"], np.float32), np.asarray(e["face_embs"], np.float32)
-    if motions.ndim == 4:
-        motions = np.ascontiguousarray(motions[:, :, 0].transpose(0, 2, 1))               # [B, T, P]
-    if args.frames is not None:
-        a, _, b = args.frames.partition(":")
-        window = slice(int(a) if a else None, int(b) if b else None)
-        motions, embs, face_embs = motions[:, window], embs[:, window], face_embs[:, window]
-    if not torch.cuda.is_available():
-        raise A2PError("the frames are rendered on the MI355X; there is no CPU implementation")
-    assets = torch.load(args.assets, map_location="cpu", weights_only=False)
-    state = torch.load(args.checkpoint, map_location="cpu", weights_only=False)
-    surface = BodySurface.from_static_assets(assets, uv_size=args.uv_size)
-    decoder = BodyDecoder.from_state_dict(
-        state, assets, surface, uv_size=args.uv_size, n_pose_dims=args.pose_to_shadow_dims - 6, n_pose_enc_channels=args.n_pose_enc_channels,
-        n_embs=args.n_embs, n_embs_enc_channels=args.n_embs_enc_channels, n_face_embs=args.n_face_embs, n_init_channels=args.n_init_channels,
-        n_min_channels=args.n_min_channels)
-    texture = BodyTexture.from_state_dict(state, assets, surface, uv_size=args.uv_size, n_init_ftrs=args.n_init_ftrs,
-                                          upscale_n_ftrs=args.upscale_n_ftrs, pose_to_shadow_dims=args.pose_to_shadow_dims)
-    skeleton = BodySkeleton.from_static_assets(assets)
+    ap.add_argument("--out", required=True, help="frames.npy: a float32 array [B, T, 3, H, W] in [0, 255]")
+    avatar.add_camera_arguments(ap)
+    avatar.add_render_arguments(ap, png="rgb")
+    avatar.add_network_arguments(ap)
+    return ap
+
+
+def main(argv=None) -> int:
+    from . import render as R
+    args = parser().parse_args(argv)
+    motions, embs, face_embs = avatar.load_motion_clip(args.results, args.embeddings, args.frames)
+    avatar.require_gpu("the frames are rendered")
+    person = avatar.load_avatar(args.assets, args.checkpoint, args)
     H, W = args.size
     poses = torch.from_numpy(motions).to("cuda")
-    rest = skeleton.pose_vertices(poses.reshape(-1, poses.shape[-1])[:1]).cpu().numpy()  # frames the default camera
+    rest = person.skeleton.pose_vertices(poses.reshape(-1, poses.shape[-1])[:1]).cpu().numpy()  # frames the default camera
     K, Rt = R._camera_from_args(args, rest, H, W)
-    rgb = render_rgb_motion(decoder, texture, skeleton, R.BodyRasterizer(surface, H, W), poses, embs, face_embs, K.to("cuda"),
-                            Rt.to("cuda"), max_bytes=args.max_bytes, supersample=args.supersample, background=args.background).cpu().numpy()
+    rgb = render_rgb_motion(person.decoder, person.texture, person.skeleton, R.BodyRasterizer(person.surface, H, W), poses, embs, face_embs,
+                            K.to("cuda"), Rt.to("cuda"), max_bytes=args.max_bytes, supersample=args.supersample,
+                            background=args.background).cpu().numpy()
     np.save(args.out, rgb)
     print(f"{args.out}: rgb {list(rgb.shape)}")
-    if args.png_dir is not None:
-        from PIL import Image
-        import os
-        os.makedirs(args.png_dir, exist_ok=True)
-        flat = rgb.reshape((-1,) + rgb.shape[-4:]) if rgb.ndim == 5 else rgb[None]
-        for b in range(flat.shape[0]):
-            for t in range(flat.shape[1]):
-                pix = np.clip(np.rint(flat[b, t]), 0, 255).astype(np.uint8).transpose(1, 2, 0)
-                Image.fromarray(np.ascontiguousarray(pix), "RGB").save(os.path.join(args.png_dir, f"rgb_{b:02d}_{t:05d}.png"))
-        print(f"{args.png_dir}: {flat.shape[0] * flat.shape[1]} png files")
+    if args.png_dir is not None:                                              # rounded here: write_pngs writes a uint8 image as it is
+        count = R.write_pngs({"rgb": np.clip(np.rint(rgb), 0, 255).astype(np.uint8)}, args.png_dir)
+        print(f"{args.png_dir}: {count} png files")
     return 0
 
 

@@ -27,7 +27,7 @@ import struct
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, avatar
 from ._lib import A2PError
 
 # ------------------------------------------------------------------------------------------------ the standard's tables (ITU-T T.81)
@@ -999,7 +999,7 @@ def sequence_path(path: str, index: int, count: int) -> str:
     return f"{stem}_{index:02d}{ext}"
 
 
-def _extract_main(argv) -> int:
+def extract_parser():
     """--extract clip.avi --out frames.npy [--frames A:B] [--png-dir DIR] [--wav out.wav]: the frames of an AVI file, decoded on the GPU."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m audio2photoreal_amd.video --extract",
@@ -1010,14 +1010,15 @@ def _extract_main(argv) -> int:
     ap.add_argument("--png-dir", default=None, metavar="DIR", help="also write frame_00_<frame>.png per frame")
     ap.add_argument("--wav", default=None, metavar="FILE", help="also write the audio as a 16-bit PCM wav file")
     ap.add_argument("--slice-frames", type=int, default=64, help="frames on the GPU at a time")
-    args = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        raise A2PError("the frames are decoded on the MI355X; there is no CPU implementation")
+    return ap
+
+
+def _extract_main(argv) -> int:
+    args = extract_parser().parse_args(argv)
+    avatar.require_gpu("the frames are decoded")
     with MJPEGReader(args.extract, args.slice_frames) as r:
-        a, b = 0, len(r)
-        if args.frames is not None:
-            lo, _, hi = args.frames.partition(":")
-            a, b = int(lo) if lo else 0, int(hi) if hi else len(r)
+        window = avatar.frame_window(args.frames)
+        a, b = window.start or 0, len(r) if window.stop is None else window.stop
         if not (0 <= a <= b <= len(r)) or r.size is None:
             raise A2PError(f"--frames {args.frames}: {args.extract} holds {len(r)} frames")
         frames = np.lib.format.open_memmap(args.out, mode="w+", dtype=np.uint8, shape=(b - a, r.size[0], r.size[1], 3))
@@ -1044,12 +1045,8 @@ def _extract_main(argv) -> int:
     return 0
 
 
-def main(argv=None) -> int:
+def parser():
     import argparse
-    import sys
-    argv = sys.argv[1:] if argv is None else list(argv)
-    if any(a == "--extract" or a.startswith("--extract=") for a in argv):
-        return _extract_main(argv)
     ap = argparse.ArgumentParser(prog="python -m audio2photoreal_amd.video",
                                  description="uint8 frames (and a wav file) to a Motion-JPEG AVI file, encoded on the MI355X.")
     ap.add_argument("--frames", required=True, help="frames.npy: uint8 [T, H, W, 3] or [R, T, H, W, 3] (what python -m "
@@ -1060,12 +1057,19 @@ def main(argv=None) -> int:
     ap.add_argument("--quality", type=int, default=90)
     ap.add_argument("--subsampling", choices=("420", "444"), default="420")
     ap.add_argument("--slice-frames", type=int, default=64, help="frames on the GPU at a time")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None) -> int:
+    import sys
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if any(a == "--extract" or a.startswith("--extract=") for a in argv):
+        return _extract_main(argv)
+    args = parser().parse_args(argv)
     frames = np.load(args.frames, mmap_mode="r")
     if frames.dtype != np.uint8 or frames.ndim not in (4, 5) or frames.shape[-1] != 3:
         raise A2PError(f"{args.frames} must hold uint8 [T, H, W, 3] or [R, T, H, W, 3] (got {frames.dtype} {list(frames.shape)})")
-    if not torch.cuda.is_available():
-        raise A2PError("the frames are encoded on the MI355X; there is no CPU implementation")
+    avatar.require_gpu("the frames are encoded")
     if frames.ndim == 4:
         frames = frames[None]
     audio, rate = wav_audio(args.audio) if args.audio is not None else (None, None)
